@@ -10,9 +10,14 @@ dropout 0.5 (configs/deepfm/base_config.yaml of the reference), B=4096, seeded s
 resident in HBM before the timed region.  A step = model(x) -> BCEWithLogits -> backward
 (the metric is fwd+bwd; no optimizer step), gradients of the two tables in row (COO) form.
 
-One JSON line on rank 0: the contract fields + `roofline` (the slower of the two gather+FM
-kernels, HIP-event timed inside the timed region, algorithmic bytes per SURVEY.md §8d) +
-`cpu_baseline` (the oracle's restatement of the reference op sequence on the host cores).
+One JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  A plain run sets up, warms up, times the K steps and prints that line; with
+--full the line also carries `roofline` (the slower of the two gather+FM kernels, HIP-event
+timed inside the timed region, algorithmic bytes per SURVEY.md §8d), the per-kernel eager table,
+`ms_per_step_windows`, `train_step` and `cpu_baseline` (the oracle's restatement of the reference
+op sequence on the host cores).  --dump-outputs DIR writes what the last timed step returned
+(logits, loss, gradients, BatchNorm running statistics) as DIR/<name>.npy; the inputs are seeded,
+so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -533,6 +538,38 @@ def kernel_table(kt):
     return {k: {"avg_us": round(v["avg_us"], 3), "min_us": round(v["min_us"], 3), "launches": v["count"]} for k, v in kt.summary().items()}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(dirname, outputs, model):
+    """--dump-outputs: `outputs` ({name: tensor}, what the step returned to its caller) and the model's BatchNorm running
+    statistics as DIR/<name>.npy.  Row-form (COO) gradients are coalesced first (rows sorted, duplicates summed) and written as
+    <name>.rows (float64: row indices are exact in it) + <name>.values; everything else as float32."""
+    import numpy as np
+
+    arrays = {}
+    for name, t in outputs.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.is_sparse:
+            t = t.coalesce()
+            arrays[name + ".rows"] = t.indices()[0].cpu().numpy().astype(np.float64)
+            arrays[name + ".values"] = t.values().float().cpu().numpy()
+        else:
+            arrays[name] = t.float().cpu().numpy()
+    for name, b in model.named_buffers():
+        if b.is_floating_point() and ("running_mean" in name or "running_var" in name):
+            arrays["buffer." + name] = b.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {dirname}", file=sys.stderr, flush=True)
+
+
 def emit(out, real_stdout):
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
@@ -579,14 +616,16 @@ def bench_c3(args, real_stdout):
     elapsed = time_graphed([step_on(xb, yb) for xb, yb in batches], args, world, dev)
     pkg.check_index_errors()
     n_prof = min(args.steps, 50)
-    with KernelTimer(capacity=96 * n_prof + 64) as kt:
-        for _ in range(n_prof):
-            step()
-            L.load().mi_prof_empty_launch(256, 256, L.stream_ptr(dev))
-        torch.cuda.synchronize()
+    kernels = {}
+    if args.full:
+        with KernelTimer(capacity=96 * n_prof + 64) as kt:
+            for _ in range(n_prof):
+                step()
+                L.load().mi_prof_empty_launch(256, 256, L.stream_ptr(dev))
+            torch.cuda.synchronize()
+        kernels = kernel_table(kt)
     if rank != 0:
         return
-    kernels = kernel_table(kt)
     flops_step = 3.0 * nl * (E * (2 * d * r + 2 * r * r + 2 * r * d) + 2 * E * d) * B
     tail_wgrad = 0.0
     if _mlp.FUSED_TAIL:      # the own MLP tail runs its weight gradients as a multi-problem launch too: same kernel name, so its
@@ -617,7 +656,7 @@ def bench_c3(args, real_stdout):
                                   f"(one hipGraph per resident batch)",
                       "global_batch": B * world, "parallelism": "single" if world == 1 else f"{world} independent replicas"},
            "roofline": roofline, "kernels": kernels}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_c3(model, dims, D, nl, len(hidden), B)
     emit(out, real_stdout)
 
@@ -704,23 +743,25 @@ def bench_c5(args, real_stdout):
     elapsed = time_graphed(step, args, world, dev)
     pkg.check_index_errors()
     n_prof = min(args.steps, 50)
-    with KernelTimer(capacity=64 * n_prof + 64) as kt:
-        for _ in range(n_prof):
-            step()
-            L.load().mi_prof_empty_launch(256, 256, L.stream_ptr(dev))
-        torch.cuda.synchronize()
-    # roofline leg: FULL layers only (in the step one backward layer skips the zero rows of its operand and — unless
-    # --full-last-layer — the last forward layer computes the batch's rows only: both move fewer bytes than a layer's
-    # algorithmic count), each the product of the whole adjacency with a dense [N, D] operand
-    Xfull = torch.randn(N, D, device=dev)
-    with torch.no_grad(), KernelTimer(capacity=4 * n_prof + 16) as kt_full:
-        for _ in range(n_prof):
-            Xfull = _kernels_spmm(adj, Xfull)
-        torch.cuda.synchronize()
+    kernels, full = {}, {}
+    if args.full:
+        with KernelTimer(capacity=64 * n_prof + 64) as kt:
+            for _ in range(n_prof):
+                step()
+                L.load().mi_prof_empty_launch(256, 256, L.stream_ptr(dev))
+            torch.cuda.synchronize()
+        # roofline leg: FULL layers only (in the step one backward layer skips the zero rows of its operand and — unless
+        # --full-last-layer — the last forward layer computes the batch's rows only: both move fewer bytes than a layer's
+        # algorithmic count), each the product of the whole adjacency with a dense [N, D] operand
+        Xfull = torch.randn(N, D, device=dev)
+        with torch.no_grad(), KernelTimer(capacity=4 * n_prof + 16) as kt_full:
+            for _ in range(n_prof):
+                Xfull = _kernels_spmm(adj, Xfull)
+            torch.cuda.synchronize()
+        kernels = kernel_table(kt)
+        full = kernel_table(kt_full)
     if rank != 0:
         return
-    kernels = kernel_table(kt)
-    full = kernel_table(kt_full)
     alg = 8 * nnz + 4 * (N + 1) + 8 * N * D
     kname = next((n for n in ("spmm_sliced", "spmm_tiled", "spmm_csr") if n in full), "spmm_csr")
     k = full.get(kname)
@@ -747,7 +788,7 @@ def bench_c5(args, real_stdout):
                                    ("" if args.full_last_layer else ", last layer at the rows the losses read (the batch's)")),
                       "global_batch": B * world, "parallelism": "single" if world == 1 else f"{world} independent replicas (the path does not shard: SURVEY.md §8e)"},
            "roofline": roofline, "kernels": kernels}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_c5(model, adj_cpu, users.cpu(), pos.cpu(), neg.cpu(), U, nl, B)
     emit(out, real_stdout)
 
@@ -1044,11 +1085,21 @@ def main():
                     "Cache; with this flag the steps know nothing of the next batch")
     ap.add_argument("--infer", action="store_true", help="the reference's own timing harnesses (scripts/deepfm/infer_deepfm.py, "
                     "scripts/lightgcn/infer_lightgcn.py): eval-mode forward latency at B=64 / 4096, LightGCN request phases, CPU oracle beside")
-    ap.add_argument("--windows", type=int, default=10, help="extra windows of --steps replays after the timed region, for "
-                    "ms_per_step_windows {min, median, max}")
+    ap.add_argument("--windows", type=int, default=None, help="extra windows of --steps replays after the timed region, for "
+                    "ms_per_step_windows {min, median, max} (default: 10 with --full, none without)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure as well: CPU baselines, the "
+                    "per-kernel eager pass, the roofline legs and batch sweep, the train_step lines, the sharded phases and the "
+                    "windows; without it a run sets up, warms up, times the --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned to its caller (logits, loss, every gradient — row-form table gradients coalesced, as row "
+                    "indices + values — and the BatchNorm running statistics) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--dry-launch", action="store_true", help="launch-contract check without a GPU: the ranks join a gloo "
                     "all-reduce and rank 0 prints a JSON line with no measurement in it (tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 10 if args.full else 0
+    if args.dump_outputs and (args.infer or args.config != "c2" or args.gpus > 1 or args.sharded or args.c4):
+        raise SystemExit("bench: --dump-outputs covers the single-GPU C2 step (the headline workload) only")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` with no launcher around it: this process has made no GPU call yet, so it
@@ -1176,11 +1227,28 @@ def main():
         cur.copy_(ring[state["i"] % len(ring)])
         state["i"] += 1
 
+    # --dump-outputs: what each step form returns to its caller (logits, loss, gradients), kept per step form
+    held = {}
+
+    def step_outputs(logits, loss):
+        # (detached: a kept loss must not keep its autograd graph alive into the next capture)
+        return {"logits": logits.detach(), "loss": loss.detach(),
+                **{"grad." + n: p.grad for n, p in model.named_parameters() if p.grad is not None}}
+
+    def fwd_loss(xb, yb):
+        """(loss, logits): the logits are kept only for --dump-outputs (a plain run frees them as soon as the loss exists)"""
+        if not args.dump_outputs:
+            return lossf(fwd(xb, yb), yb), None
+        logits = fwd(xb, yb)
+        return lossf(logits, yb), logits
+
     def eager_step():
         next_batch()
         model.zero_grad(set_to_none=True)
-        loss = lossf(fwd(x, y), y)
+        loss, logits = fwd_loss(x, y)
         loss.backward()
+        if args.dump_outputs:
+            held["eager"] = step_outputs(logits, loss)
         if sharded:
             model.allreduce_dense_grads()
 
@@ -1275,10 +1343,15 @@ def main():
                     from recsys_benchmark_amd import _lib as _pl
                     _pl.load().mi_prof_empty_launch(1, 256, _pl.stream_ptr(dev))
                     _pl.load().mi_prof_empty_launch(2, 256, _pl.stream_ptr(dev))
-                lossf(fwd(xb, yb), yb).backward(one)
+                loss, logits = fwd_loss(xb, yb)
+                loss.backward(one)
                 if args.probe_empties:
                     _pl.load().mi_prof_empty_launch(3, 256, _pl.stream_ptr(dev))
             pool = g.pool()
+            if args.dump_outputs:
+                # the graph's output buffers stay its own (valid right after its replay: the graphs share one pool)
+                held[gi] = step_outputs(logits, loss)
+            del logits, loss
             graphs.append(g)
         # the FIRST replay of a captured graph uploads it to the device: part of building the step, like the capture — with
         # 16 per-batch graphs and W = 5 warm-up steps eleven of those uploads used to fall inside the timed region (0.276 ms
@@ -1309,7 +1382,11 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    # the timed region above is the contract's; the same K replays a few more times give it an error bar
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, read before anything else runs (the graphs' buffers are only valid until the next replay)
+        last = held["eager"] if not use_graph else held[0] if args.copy_batch else held[(state["i"] - 1) % len(graphs)]
+        write_outputs(args.dump_outputs, last, model)
+    # the timed region above is the contract's; the same K replays a few more times give it an error bar (--full)
     window_ms = []
     for _ in range(max(0, args.windows)):
         fence()
@@ -1340,7 +1417,7 @@ def main():
     from recsys_benchmark_amd import _lib as _mlib
 
     ks = {}
-    if not args.no_eager_leg:
+    if args.full and not args.no_eager_leg:
         with KernelTimer(capacity=48 * n_prof + 64) as kt:
             for _ in range(n_prof):
                 eager_step()
@@ -1349,7 +1426,7 @@ def main():
         ks = kt.summary()
     # Roofline leg: the two gather+FM kernels inside replayed hipGraphs (how the timed region runs them), wall per kernel.
     ingraph = sweep = None
-    if not sharded and not args.no_gather_leg:
+    if args.full and not sharded and not args.no_gather_leg:
         xs_ring = [blob[:nx].view(torch.int64).view(B, F) for blob in ring]
         xs_ring += [synth_batch(dims, B, 31337 + i, dev, args.ids)[0] for i in range(max(0, 64 - len(xs_ring)))]
         ingraph = gather_in_graph_us(model, xs_ring, B, F, D, dev, copies=64)
@@ -1357,9 +1434,10 @@ def main():
         ingraph["prefetched"] = prefetched_gather_us(model, xs_ring, B, F, D, hidden, dev) if prefetching else None
         if not args.no_sweep and rank == 0:
             sweep = batch_sweep(model, dims, F, D, dev, args.ids)
-    sharded_dgrad = dgrad_epilogue_us(B, F, D, hidden[0], dev) if (sharded and rank == 0 and not args.no_gather_leg) else None
+    sharded_dgrad = (dgrad_epilogue_us(B, F, D, hidden[0], dev) if (args.full and sharded and rank == 0 and not args.no_gather_leg)
+                     else None)
     sharded_phases = None
-    if sharded and graphed_local:
+    if args.full and sharded and graphed_local:
         sharded_phases = timed_phases()          # every rank runs them (collectives inside); rank 0 reports its own
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -1519,9 +1597,9 @@ def main():
                                "the timed region (the host stays ahead of the device); phases_us_synced: the same with a host "
                                "sync after every step (every phase then includes the host's launch latency: rounds 1-4's "
                                "figure); at world=1 the all-to-alls are one-rank copies"}
-        if not args.no_train_step and world == 1 and not sharded:
+        if args.full and not args.no_train_step and world == 1 and not sharded:
             out["train_step"] = train_step_lines(dims, D, hidden, p_drop, B, dev, args.ids, args.layout)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(dims, D, hidden, B, p_drop)
         elif world == 1:
             out["cpu_baseline"] = None

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/${1:-pmc_c5}; mkdir -p $OUT; cd /tmp; expo
 for pmc in "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY" "SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAVES"; do
   tag=$(echo $pmc | tr ' ' '+')
   for form in 1 0; do
-    MI_SPMM_SLICED=$form timeout -k 10 200 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/p_${form}_$tag -- python3 $R/bench.py --config c5 --steps 3 --warmup 1 --windows 0 --no-cpu-baseline --no-graph > /dev/null 2> $OUT/p_${form}_$tag.err || echo "pass $tag $form failed"
+    MI_SPMM_SLICED=$form timeout -k 10 200 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/p_${form}_$tag -- python3 $R/bench.py --full --config c5 --steps 3 --warmup 1 --windows 0 --no-cpu-baseline --no-graph > /dev/null 2> $OUT/p_${form}_$tag.err || echo "pass $tag $form failed"
   done
 done
 python3 - <<PY
