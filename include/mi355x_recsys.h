@@ -732,6 +732,41 @@ MI_API int mi_mask_topk_rows(float *scores, int64_t ld, int64_t nrows, int64_t n
                              const int64_t *users, const int64_t *crow, const int64_t *col, int32_t k,
                              int64_t *out_idx, float *out_val, void *stream);
 
+/* ---- NeuMF (GMF + MLP): src/models/mlp.py:11-344, trained by src/trainer/nmf.py:446-499 --------------
+ * Four tables of width D = emb_size / 2: GU / GI (gmf-user / gmf-item), MU / MI (mlp-user / mlp-item).
+ * flags: bit 0 = MLP, bit 1 = GMF (ModelFlag, mlp.py:11-14); at least one bit.  D <= 256.
+ *
+ * mi_neumf_fwd: mlp.py:82-101, 255-274 and 318-344 up to the tower: for sample s (u = users[s], i = items[s])
+ *   y_gmf[s] = sum_k GU[u,k] GI[i,k] w[k] + b[0]   (gmf_fc; GMF only, else y_gmf unused)
+ *   X0[s]    = [MU[u] ; MI[i]]  ([S, 2D]; the MLP tower's input, MLP only, else X0 unused)
+ *   An id outside its table ORs MI_IDX_OUT_OF_RANGE into *err and reads as a zero row.               */
+MI_API int mi_neumf_fwd(const int64_t *users, const int64_t *items, int64_t S, const float *GU, const float *GI,
+                        const float *MU, const float *MI, int32_t D, int64_t nU, int64_t nI, const float *w, const float *b,
+                        int32_t flags, float *y_gmf, float *X0, int32_t *err, void *stream);
+/* mi_neumf_bwd: the backward of mi_neumf_fwd given dy [S] (GMF) and the tower's input gradient dX0 [S, 2D] (MLP):
+ *   dGU[u] += dy[s] w * GI[i], dGI[i] += dy[s] w * GU[u], dMU[u] += dX0[s, :D], dMI[i] += dX0[s, D:]
+ *   mode 0: the four outputs are dense [n, D] gradients, caller-zeroed, duplicates joined by float atomics;
+ *   mode 1: they are row-form values [S, D] (row s belongs to users[s] / items[s]), written, no atomics.
+ *   dw[k] = sum_s dy[s] GU[u,k] GI[i,k], db[0] = sum_s dy[s]: written (not accumulated) in a fixed order through
+ *   `workspace` (mi_neumf_bwd_parts(S, D) * (D + 1) floats) and one finishing launch.                  */
+MI_API int mi_neumf_bwd_parts(int64_t S, int32_t D);
+MI_API int mi_neumf_bwd(const int64_t *users, const int64_t *items, int64_t S, const float *GU, const float *GI, int32_t D,
+                        int64_t nU, int64_t nI, const float *w, int32_t flags, const float *dy, const float *dX0, int32_t mode,
+                        float *dGU, float *dGI, float *dMU, float *dMI, float *dw, float *db, float *workspace,
+                        void *stream);
+/* mi_neumf_score_all: src/trainer/nmf.py:501-582 (the model over every item of a user batch) as one kernel:
+ *   scores[b * ld + i] = mlp_fc(h_L(b, i)) + gmf_fc(GU[users[b]] * GI[i]),  b < B, i < N
+ *   with h_1 = relu(P[b] + Q[i]) (P = MU[users] W1_u^T [B, h_1], Q = MI W1_i^T + b1 [N, h_1]: the caller's GEMMs)
+ *   and h_l = relu(W[l-2] h_{l-1} + bias[l-2]) on v_mfma_f32_16x16x4_f32.  `hidden` (host, nhidden entries),
+ *   W and bias (host arrays of nhidden - 1 device pointers).  Unused halves (flags) may be NULL.
+ *   Supported (mi_neumf_score_supported != 0): 1..4 hidden layers, each <= 128 wide, the hidden weights within
+ *   64 KiB of LDS once padded to 16-wide tiles, D <= 128; otherwise MI_ERR_UNSUPPORTED.               */
+MI_API int mi_neumf_score_supported(int32_t nhidden, const int32_t *hidden, int32_t D, int32_t flags);
+MI_API int mi_neumf_score_all(const float *P, const float *Q, int64_t B, int64_t N, int32_t nhidden, const int32_t *hidden,
+                              const float *const *W, const float *const *bias, const float *wf, const float *bf,
+                              const int64_t *users, const float *GU, const float *GI, int32_t D, int64_t nU, const float *wg,
+                              const float *bg, int32_t flags, float *scores, int64_t ld, int32_t *err, void *stream);
+
 /* ---- §8e: device-side routing of the row-sharded DeepFM lookup -------------------------------
  * No reference counterpart (the reference keeps one table on one device,
  * src/models/embeddings/base.py:52-57); the arithmetic either side of the exchange is the

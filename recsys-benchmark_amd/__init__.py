@@ -11,6 +11,7 @@ from .factory import (get_ctr_model, get_graph_model, load_ctr_model, load_graph
                       save_ctr_checkpoint)
 from .lightgcn import LightGCN, SingleLightGCN
 from .losses import BCEWithLogitsLoss
+from .neumf import ModelFlag, NeuMF
 
 
 
@@ -46,5 +47,5 @@ __all__ = [
     "DeepFM", "IEmbedding", "VanillaEmbedding", "NAME_TO_CLS", "get_embedding",
     "LightGCN", "SingleLightGCN", "get_ctr_model", "get_graph_model", "load_ctr_model", "load_graph_model",
     "save_cf_emb_checkpoint", "save_ctr_checkpoint", "MI355XLibraryError", "check_index_errors", "use_deterministic_algorithms",
-    "BCEWithLogitsLoss",
+    "BCEWithLogitsLoss", "NeuMF", "ModelFlag",
 ]

@@ -528,3 +528,90 @@ def validate_epoch_cf(train_dataset, val_loader, model, device="cuda", k=20, fil
     if metrics is not None and "ndcg" in metrics and "recall" in metrics:
         return {"ndcg": ndcg, "recall": recall}
     return {"ndcg": ndcg}
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# NeuMF: reference src/trainer/nmf.py:232-281, 446-582
+def nmf_step_losses(model, users, pos_items, neg_items, weight_decay: float = 0):
+    """(loss, rec_loss, reg_loss) of one NeuMF batch as `_train_step` forms them (src/trainer/nmf.py:446-486):
+    `users.repeat(n_neg + 1)` against `cat([pos, neg])` in ONE forward, BCE(pos, 1) + BCE(neg, 0) (each a mean) and
+    `weight_decay * get_reg_loss`.  `neg_items` is [B] or a list of [B] tensors.  No host sync, no shape that depends
+    on data: capturable in torch.cuda.graph."""
+    n_repeat = 1
+    if isinstance(neg_items, (list, tuple)):
+        n_repeat = len(neg_items)
+        neg_items = torch.cat(list(neg_items))
+    y_hat = model(users.repeat(n_repeat + 1), torch.cat([pos_items, neg_items]))
+    B = pos_items.shape[0]
+    y_pos, y_neg = y_hat[:B], y_hat[B:]
+    bce = losses.BCEWithLogitsLoss()
+    rec_loss = bce(y_pos, torch.ones_like(y_pos)) + bce(y_neg, torch.zeros_like(y_neg))
+    if weight_decay > 0:
+        reg_loss = model.get_reg_loss(users, pos_items, neg_items)
+        loss = rec_loss + weight_decay * reg_loss
+    else:
+        reg_loss = torch.zeros((), device=rec_loss.device)
+        loss = rec_loss
+    return loss, rec_loss, reg_loss
+
+
+def train_epoch_nmf(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None) -> Dict[str, float]:
+    """src/trainer/nmf.py:232-281 (`train_epoch`): {"loss", "rec_loss", "reg_loss"} averaged over the batches; the sums
+    stay on the device and are read back at the logging steps only."""
+    model.train()
+    model.to(device)
+    sums = torch.zeros(3, dtype=torch.float32, device=device)
+    one = losses.unit_scalar(device)
+    idx = -1
+    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
+        users, pos_items = users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True)
+        if isinstance(neg_items, (list, tuple)):
+            neg_items = [n.to(device, non_blocking=True) for n in neg_items]
+        else:
+            neg_items = neg_items.to(device, non_blocking=True)
+        loss, rec_loss, reg_loss = nmf_step_losses(model, users, pos_items, neg_items, weight_decay)
+        optimizer.zero_grad()
+        loss.backward(one)
+        optimizer.step()
+        sums += torch.stack([loss.detach(), rec_loss.detach(), reg_loss.detach().float()])
+        if log_step and idx % log_step == 0:
+            avg = (sums / (idx + 1)).tolist()
+            logger.info("Idx: %d - loss: %.2g - rec_loss: %.2g - reg_loss: %.2g", idx, *avg)
+            _lib.check_index_errors()
+        if profiler:
+            profiler.step()
+    avg = (sums / max(idx + 1, 1)).tolist()
+    _lib.check_index_errors()
+    return {"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2]}
+
+
+@torch.no_grad()
+def validate_epoch_nmf(train_dataset, val_loader, model, device="cuda", k=20, filter_item_on_train=True, profiler=None,
+                       metrics: Optional[List[str]] = None) -> Dict[str, float]:
+    """src/trainer/nmf.py:501-582 (`validate_epoch`): {"ndcg"} or {"ndcg", "recall"}.  Every user of a batch is scored
+    against every item by `neumf.score_all_items`, the train items are masked and the top-k taken by mi_mask_topk_rows
+    (a CSR of `train_dataset.get_graph()` built once), the metric runs on the device."""
+    from .neumf import score_all_items
+
+    graph = train_dataset.get_graph()
+    model.eval()
+    model = model.to(device)
+    csr = train_items_csr(graph, model.num_user, device) if filter_item_on_train else None
+    crow, col = (None, None) if csr is None else csr
+    preds, truths = [], []
+    for users, pos_items in val_loader:
+        users = torch.as_tensor(users).to(device).to(torch.int64)
+        scores = score_all_items(model, users)
+        out = torch.empty((users.numel(), k), dtype=torch.int64, device=device)
+        _lib.check(_lib.load().mi_mask_topk_rows(scores.data_ptr(), scores.stride(0), scores.shape[0], scores.shape[1],
+                                                 users.data_ptr(), _lib.ptr(crow), _lib.ptr(col), k, out.data_ptr(), None,
+                                                 _lib.stream_ptr(scores.device)), "mi_mask_topk_rows")
+        preds.append(out)
+        truths.extend(pos_items)
+        if profiler:
+            profiler.step()
+    ndcg, recall = ndcg_recall_at_k(torch.cat(preds), truths, k)
+    _lib.check_index_errors()
+    if metrics is not None and "ndcg" in metrics and "recall" in metrics:
+        return {"ndcg": ndcg, "recall": recall}
+    return {"ndcg": ndcg}
