@@ -277,6 +277,30 @@ MI_API int mi_optembed_bwd(const int64_t *idx, const float *W, const float *t, c
                            int32_t F, const int64_t *dmax, int32_t norm, const float *g, float *dW,
                            float *dt, int64_t n, int32_t D, int64_t N, void *stream);
 
+/* ---- OptEmbed supernet for the CF tables (table form, no index array) ------------------------------
+ * OptEmbed.get_weight of src/models/embeddings/lightgcn_opt_embed.py:121-177, _MaskEmbeddingModule and BinaryStep
+ * (optembed_utils.py:25-86), the dimension draws of _sampling_by_weight (optembed_utils.py:181-202) and of the field
+ * mode (lightgcn_opt_embed.py:138-152):
+ *   out[r,:] = W[r,:] * [ ||W[r]||_norm - t(r) > 0 ] * [j <= k_r]
+ * t(r) = t[field of r] (t_per_field; fields are the row ranges field_off[F+1]) or t[r]; t NULL = no row mask.
+ * k_r = k[field of r] (k_per_field) or k[r]; k NULL = every dimension.  draw != 0: k is WRITTEN, one width per row
+ * ([N]) or per field ([F]): law 0 uniform on [0, law_hi), law 1 P(k <= j) = cdf[j] (float64 [D]); the generator is
+ * keyed by (seed[0], salt, row or field); seed is int64[2] on the device (seed word, zero ticket) and the launch adds
+ * 1 to seed[0].  W NULL (with draw) = draw only.  A given k outside [0, D) ORs MI_IDX_OUT_OF_RANGE into *err.
+ * D <= 1024 (D % 4 == 0) or D <= 256.                                                                       */
+MI_API int mi_optembed_cf_fwd(const float *W, const float *t, int32_t t_per_field, const int64_t *field_off,
+                              int32_t F, int64_t *k, int32_t k_per_field, int32_t draw, int32_t law, int32_t law_hi,
+                              const double *cdf, int64_t *seed, int64_t salt, int32_t norm, float *out, int64_t N,
+                              int32_t D, int32_t *err, void *stream);
+/* Backward of mi_optembed_cf_fwd (lightgcn_opt_embed.py:121-177 through BinaryStep.backward, optembed_utils.py:34-43):
+ *   dW[r] = G*s_r + c_r*a(u_r)*d||W[r]||/dW[r],  G = g*[j <= k_r],  c_r = sum_j G_j W_j,  u_r = ||W[r]|| - t(r)
+ *   dt = -c_r*a(u_r), per row straight into dt, per field summed in a fixed order through dt_rows (float [N]).
+ * Every dW / dt element is written once with a plain store (no zero fill, no atomics, bit-reproducible).
+ * dW, dt nullable; k as given to (or drawn by) the forward.                                                  */
+MI_API int mi_optembed_cf_bwd(const float *W, const float *t, int32_t t_per_field, const int64_t *field_off,
+                              int32_t F, const int64_t *k, int32_t k_per_field, int32_t norm, const float *g,
+                              float *dW, float *dt, float *dt_rows, int64_t N, int32_t D, void *stream);
+
 /* ---- a11: CSR-pruned table rows (numba kernels K1/K2) ------------------------
  * src/models/embeddings/pruned_embedding.py:136-204: out[i,:] = dense row ids[i] of the
  * CSR matrix (values fp32, crow/col int64).  out fp32[n,D] need not be pre-zeroed.

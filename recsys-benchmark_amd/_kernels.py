@@ -5,7 +5,7 @@ arithmetic step of the hot path runs in libmi355x_recsys.so.
 """
 import collections
 import ctypes as _ctypes
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -1754,3 +1754,83 @@ class SlotFM(torch.autograd.Function):
 
 def slot_fm(buf, slot, bias):
     return SlotFM.apply(buf, slot, bias)
+
+
+# ---- OptEmbed supernet for the CF tables (csrc/optembed_cf.hip) -------------------------------------------------------
+_cf_seeds: Dict[int, list] = {}
+
+
+def optembed_cf_seed(dev: torch.device) -> torch.Tensor:
+    """int64 [2] on `dev`: the seed word of the CF OptEmbed draws and the launch ticket (kept zero between launches).
+    Started from torch.initial_seed(), and restarted when that changes (outside a graph capture), so torch.manual_seed
+    makes the draws reproducible; every drawing launch adds 1 to the word on the device (mlp._seed_word's scheme)."""
+    i = dev.index if dev.index is not None else torch.cuda.current_device()
+    init = torch.initial_seed() & 0x7FFFFFFFFFFF
+    ent = _cf_seeds.get(i)
+    if ent is None:
+        ent = [init, torch.tensor([init, 0], dtype=torch.int64, device=torch.device("cuda", i))]
+        _cf_seeds[i] = ent
+    elif ent[0] != init and not torch.cuda.is_current_stream_capturing():
+        ent[1][0].fill_(init)
+        ent[0] = init
+    return ent[1]
+
+
+class OptEmbedCF(torch.autograd.Function):
+    """out = mi_optembed_cf_fwd over the whole table (row mask x dimension mask).  `k`: int64 widths given per row
+    ([N]) or per field ([F], k_field), or the buffer the draw fills (draw = (law, hi, cdf, salt)); None keeps every
+    dimension.  The backward is mi_optembed_cf_bwd: plain stores, fixed-order sums, no atomics."""
+
+    @staticmethod
+    def forward(ctx, W, t, t_field: bool, off, k, k_field: bool, norm: int, draw):
+        dev = _lib.require_gpu(W, t, off, k)
+        Wc = _f32c(W)
+        tc = None if t is None else _f32c(t)
+        N, D = Wc.shape
+        out = torch.empty_like(Wc)
+        law, hi, cdf, salt = draw if draw is not None else (0, D, None, 0)
+        seed = optembed_cf_seed(dev) if draw is not None else None
+        _lib.check(_lib.load().mi_optembed_cf_fwd(Wc.data_ptr(), _lib.ptr(tc), int(t_field), off.data_ptr(), off.numel() - 1,
+                                                  _lib.ptr(k), int(k_field), int(draw is not None), law, hi, _lib.ptr(cdf),
+                                                  _lib.ptr(seed), salt, norm, out.data_ptr(), N, D,
+                                                  _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)), "mi_optembed_cf_fwd")
+        ctx.save_for_backward(Wc, tc, off, k)
+        ctx.meta = (bool(t_field), bool(k_field), norm)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Wc, tc, off, k = ctx.saved_tensors
+        t_field, k_field, norm = ctx.meta
+        g = _f32c(g)
+        N, D = Wc.shape
+        dW = torch.empty_like(Wc) if ctx.needs_input_grad[0] else None
+        dt = torch.empty_like(tc) if (tc is not None and ctx.needs_input_grad[1]) else None
+        dt_rows = torch.empty(N, dtype=torch.float32, device=g.device) if (dt is not None and t_field) else None
+        if dW is not None or dt is not None:
+            _lib.check(_lib.load().mi_optembed_cf_bwd(Wc.data_ptr(), _lib.ptr(tc), int(t_field), off.data_ptr(),
+                                                      off.numel() - 1, _lib.ptr(k), int(k_field), norm, g.data_ptr(),
+                                                      _lib.ptr(dW), _lib.ptr(dt), _lib.ptr(dt_rows), N, D,
+                                                      _lib.stream_ptr(g.device)), "mi_optembed_cf_bwd")
+        return dW, dt, None, None, None, None, None, None
+
+
+def optembed_cf(W, t, t_field: bool, off, norm: int, k=None, k_field: bool = False, draw=None):
+    """(masked table [N, D], widths).  draw = (law, hi, cdf, salt): the widths are drawn on the device into a fresh int64
+    buffer ([F] when k_field, else [N]) that is returned with the table; otherwise `k` is returned as given."""
+    if draw is not None:
+        k = torch.empty(off.numel() - 1 if k_field else W.shape[0], dtype=torch.int64, device=W.device)
+    elif k is not None:
+        k = _i64c(k)
+    return OptEmbedCF.apply(W, t, t_field, off, k, k_field, norm, draw), k
+
+
+def optembed_cf_draw(n: int, D: int, law: int, hi: int, cdf, salt: int, device) -> torch.Tensor:
+    """n widths (int64, on the device) drawn by mi_optembed_cf_fwd's draw-only mode: the candidate masks of the search."""
+    device = torch.device(device)
+    k = torch.empty(n, dtype=torch.int64, device=device)
+    off = torch.tensor([0, n], dtype=torch.int64, device=device)
+    _lib.check(_lib.load().mi_optembed_cf_fwd(None, None, 0, off.data_ptr(), 1, k.data_ptr(), 0, 1, law, hi, _lib.ptr(cdf),
+                                              optembed_cf_seed(device).data_ptr(), salt, 1, None, n, D, None,
+                                              _lib.stream_ptr(device)), "mi_optembed_cf_fwd")
+    return k

@@ -3,7 +3,7 @@
 Same registry keys, same `get_embedding(embedding_config, field_dims, hidden_size,
 mode, field_name)` contract (config deep-copied, "name" popped and restored,
 `field_name` forwarded to pep*/cerp* classes).  Keys whose class is outside the
-hot-path scope (the OptEmbed search classes, the FBTT CUDA extension) raise
+hot-path scope (DeepFM's OptEmbed retraining class, the FBTT CUDA extension) raise
 NotImplementedError with the reason instead of silently substituting something.
 """
 import copy
@@ -11,6 +11,7 @@ from typing import Any, Dict, List, Optional, Tuple, Union
 
 from .base import IEmbedding, VanillaEmbedding
 from .cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
+from .cf_opt_embed import OptEmbed, RetrainOptEmbed
 from .deepfm_opt_embed import OptEmbed as DeepFMOptEmbed
 from .dh_embedding import DHEmbedding
 from .pep_embedding import PepEmbeeding, RetrainPepEmbedding
@@ -32,16 +33,19 @@ _REGISTRY = (
     ("qat", QAT_EmbInt, {}, False),
     ("deepfm_optembed", DeepFMOptEmbed, {}, False),
     ("deepfm_optembed_d", DeepFMOptEmbed, {"t_init": None}, False),   # mask E disabled (reference __init__.py:65-67)
+    ("optembed", OptEmbed, {}, False),
+    ("optembed_d", OptEmbed, {"t_init": None}, False),                  # mask E disabled (reference __init__.py:65-67)
+    ("optembed_retrain", RetrainOptEmbed, {}, False),
+    ("optembed_d_retrain", RetrainOptEmbed, {"t_init": None}, False),
 )
 NAME_TO_CLS: Dict[str, type] = {key: cls for key, cls, _, _ in _REGISTRY}
 _FORCED = {key: forced for key, _, forced, _ in _REGISTRY}
 _WANTS_FIELD_NAME = {key for key, _, _, named in _REGISTRY if named}
 
 # registry keys of the reference that this build deliberately does not cover
-_SEARCH = "OptEmbed search / retraining classes (SURVEY.md §2.1 #7); the supernet lookup is 'deepfm_optembed'"
 OUT_OF_SCOPE = {
-    **{key: _SEARCH for key in ("optembed_d", "optembed_d_retrain", "optembed", "optembed_retrain",
-                                "deepfm_optembed_retrain")},
+    "deepfm_optembed_retrain": "DeepFM's OptEmbed retraining class and its search (evol_search_deepfm); the DeepFM supernet "
+                               "is 'deepfm_optembed', the CF retraining table 'optembed_retrain'",
     "tt_emb": "FBTT-Embedding CUDA extension, not in the reference tree (SURVEY.md §2.3 K3-K12); use 'tt_emb_torch'",
 }
 
@@ -76,5 +80,5 @@ def detect_special(config: Dict[str, Any]) -> Tuple[Optional[str], bool]:
     return None, False
 
 
-__all__ = ["IEmbedding", "VanillaEmbedding", "QRHashingEmbedding", "CerpEmbedding", "RetrainCerpEmbedding",
+__all__ = ["IEmbedding", "VanillaEmbedding", "OptEmbed", "RetrainOptEmbed", "QRHashingEmbedding", "CerpEmbedding", "RetrainCerpEmbedding",
            "DHEmbedding", "PrunedEmbedding", "TTRecTorch", "PepEmbeeding", "RetrainPepEmbedding", "NAME_TO_CLS", "get_embedding", "detect_special"]

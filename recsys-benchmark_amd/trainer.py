@@ -479,6 +479,63 @@ def train_epoch_pep(dataloader, model, optimizer, device="cuda", log_step=10, we
     return dict({"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2], "cl_loss": avg[3]}, **extra)
 
 
+def train_epoch_optembed(dataloader, model, optimizers, device="cuda", log_step=10, weight_decay=0, profiler=None,
+                         info_nce_weight=0, alpha=0) -> Dict[str, float]:
+    """src/trainer/lightgcn.py:162-290: a LightGCN / SingleLightGCN epoch on OptEmbed tables, eager, with a list of
+    optimizers; loss = bpr + weight_decay * reg + info_nce + alpha * sum of the tables' get_l_s().  Each training
+    get_weight draws its dimension mask on the device.  Returns the averaged "loss", "reg_loss" (unweighted),
+    "rec_loss", "cl_loss" (weighted), "loss_s", and "sparsity" / "n_params" after the epoch."""
+    from .embeddings.cf_opt_embed import IOptEmbed
+    from .lightgcn import get_sparsity_and_param
+
+    if not isinstance(optimizers, (list, tuple)):
+        optimizers = [optimizers]
+    adj = dataloader.dataset.get_norm_adj().to(device)
+    model.train()
+    model.to(device)
+    tables = [emb for _, emb in model.get_embs()]
+    assert all(isinstance(t, IOptEmbed) for t in tables), "train_epoch_optembed needs OptEmbed tables"
+    sums = torch.zeros(5, dtype=torch.float32, device=device)          # loss, reg_loss, rec_loss, cl_loss, loss_s
+    one = losses.unit_scalar(device)
+    zero = torch.zeros((), device=device)
+    idx = -1
+    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
+        users, pos_items = users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True)
+        neg_items = neg_items.to(device, non_blocking=True)
+        all_user_emb, all_item_emb = model(adj)
+        rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items)
+        reg_loss = model.get_reg_loss(users, pos_items, neg_items) if weight_decay > 0 else zero
+        cl_loss = zero
+        if info_nce_weight > 0:        # the batch's distinct users and positives (repeats masked out, no unique())
+            view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
+            valid = torch.cat([losses.first_occurrence(users, all_user_emb.shape[0]),
+                               losses.first_occurrence(pos_items, all_item_emb.shape[0])])
+            cl_loss = losses.info_nce(view, view, 0.2, valid=valid) * info_nce_weight
+        loss_s = zero
+        for t in tables:
+            loss_s = loss_s + t.get_l_s().to(device)
+        loss = rec_loss + weight_decay * reg_loss + cl_loss + alpha * loss_s
+        for opt in optimizers:
+            opt.zero_grad()
+        loss.backward(one)
+        for opt in optimizers:
+            opt.step()
+        sums += torch.stack([loss.detach(), reg_loss.detach(), rec_loss.detach(), cl_loss.detach(), loss_s.detach()])
+        if log_step and idx % log_step == 0:
+            sparsity, n_params = get_sparsity_and_param(model)
+            avg = (sums / (idx + 1)).tolist()
+            logger.info("Idx: %d - sparsity=%.4f - n_params=%d - loss: %.4g - loss_s: %.4g", idx, sparsity, n_params,
+                        avg[0], avg[4])
+            _lib.check_index_errors()
+        if profiler:
+            profiler.step()
+    avg = (sums / max(idx + 1, 1)).tolist()
+    _lib.check_index_errors()
+    sparsity, n_params = get_sparsity_and_param(model)
+    return {"loss": avg[0], "reg_loss": avg[1], "rec_loss": avg[2], "cl_loss": avg[3], "loss_s": avg[4],
+            "sparsity": sparsity, "n_params": n_params}
+
+
 def ndcg_recall_at_k(y_pred: torch.Tensor, y_true: Sequence[Union[Sequence[int], set]], k: int = 20) -> Tuple[float, float]:
     """src/metrics.py:9-43, 70-108 (`get_ndcg`, `get_ndcg_recall`) for a [users, >=k] tensor of recommended item ids:
     the relevance test is one broadcast comparison against the padded true-item lists on y_pred's device, float64."""
