@@ -3,10 +3,11 @@
 replayed as ONE hipGraph.
 
 At the headline shape the eager step is bound by the host (≈0.85 ms of Python / autograd / launch work around ≈0.45 ms of
-kernels); a captured step has no host work beyond two input copies and one graph launch.  What makes the whole step
-capturable: the lookup kernels emit row-form gradients without host syncs, `optim.SparseAdam(capturable=True)` keeps its
-step count on the device, `optim.Adam` steps from device-side counts too (`optim.get_optimizers` builds both on a GPU),
-dropout seeds and BatchNorm counters advance inside kernels.
+kernels); a captured step has no host work beyond its input copies (ids and labels, plus the next batch's ids when the
+model prefetches) and one graph launch.  What makes the whole step capturable: the lookup kernels emit row-form gradients
+without host syncs, `optim.SparseAdam(capturable=True)` keeps its step count on the device, `optim.Adam` steps from
+device-side counts too (`optim.get_optimizers` builds both on a GPU), dropout seeds and BatchNorm counters advance inside
+kernels.
 
 `train_epoch` / `validate_epoch` keep the reference's signatures and return values; the loss is accumulated on the device
 and read back at the logging steps only (the reference calls `.item()` every batch).
@@ -20,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib, losses
-from .lightgcn import score_topk, train_items_csr
+from .lightgcn import get_sparsity_and_param, score_topk, train_items_csr
 
 logger = logging.getLogger("recsys_benchmark_amd.trainer")
 now = datetime.datetime.now
@@ -66,6 +67,53 @@ def _capturable(optimizers) -> bool:
     return all(group.get("capturable", True) for opt in optimizers for group in opt.param_groups)
 
 
+class _Replayed:
+    """body(*tensors) for ONE input shape: the first `warmup` calls of a shape run eagerly (the count restarts when the
+    shape changes), the next call of that shape is captured as a hipGraph and from then on replayed — the inputs are
+    copied into static clones and the static output is returned.  Calls of any other shape run `body` eagerly and leave
+    the graph alone.  A capture that raises is warned about and never tried again (`enabled` turns False)."""
+
+    def __init__(self, body, warmup: int, what: str, before_capture=None, enabled: bool = True, eager: str = "steps"):
+        """before_capture(*static_inputs) runs between cloning the inputs and the capture; what / eager: the warning's nouns."""
+        self.body, self.warmup, self.what, self.before_capture, self.eager = body, warmup, what, before_capture, eager
+        self.enabled = enabled
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._static, self._out, self._key, self._seen = (), None, None, 0
+
+    def ready(self, *tensors) -> bool:
+        """True when `replay(*tensors)` can serve this call; counts the warm-up calls and captures when they are done."""
+        key = tuple((t.shape, t.dtype) for t in tensors)
+        if self.graph is not None:
+            return key == self._key
+        if self.enabled and self._seen >= self.warmup and key == self._key:
+            try:
+                static = tuple(t.clone() for t in tensors)
+                if self.before_capture is not None:
+                    self.before_capture(*static)
+                graph = torch.cuda.CUDAGraph()
+                with _capture(graph):
+                    out = self.body(*static)
+                self.graph, self._static, self._out = graph, static, out
+                return True
+            except Exception as exc:               # leave the caller running on the eager HIP path
+                warnings.warn(f"hipGraph capture of {self.what} failed ({exc!r}); continuing with eager {self.eager}")
+                torch.cuda.synchronize()
+                self.enabled = False
+        if key != self._key:
+            self._key, self._seen = key, 0
+        self._seen += 1
+        return False
+
+    def replay(self, *tensors):
+        for dst, src in zip(self._static, tensors):
+            dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+        return self._out
+
+    def __call__(self, *tensors):
+        return self.replay(*tensors) if self.ready(*tensors) else self.body(*tensors)
+
+
 class GraphedTrainStep:
     """step(inputs, labels): one optimisation step of `model` on the batch, in the reference's order (forward, loss,
     zero_grad, backward, optimizer steps).  The first `warmup` calls run eagerly (they are ordinary training steps and
@@ -89,21 +137,21 @@ class GraphedTrainStep:
                                    and "labels" in inspect.signature(model.forward).parameters)
         self._prefetches = callable(getattr(model, "prefetch_next", None))
         self._static_next = None
-        self.warmup = warmup
         self.clip_grad = clip_grad
         # clip_grad_norm_ reads the norm back on some paths and row-form gradients have no dense norm: eager only
-        self.use_graph = use_graph and not clip_grad
-        if self.use_graph and not _capturable(self.optimizers):
+        use_graph = use_graph and not clip_grad
+        if use_graph and not _capturable(self.optimizers):
             warnings.warn("an optimizer keeps its step count on the host (capturable=False): the training step runs "
                           "eagerly; build the optimizers with recsys_benchmark_amd.optim.get_optimizers / optim.Adam")
-            self.use_graph = False
+            use_graph = False
         self.steps = 0
         self.loss_sum: Optional[torch.Tensor] = None
         self.last_loss: Optional[torch.Tensor] = None
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._static = None
-        self._shape = None
-        self._seen = 0
+        self._replayed = _Replayed(self._body, warmup, "the training step", self._before_capture, use_graph)
+
+    warmup = property(lambda self: self._replayed.warmup)
+    use_graph = property(lambda self: self._replayed.enabled)
+    _graph = property(lambda self: self._replayed.graph)
 
     def _body(self, inputs, labels):
         labels = labels.float()
@@ -127,19 +175,14 @@ class GraphedTrainStep:
         self.loss_sum += loss
         return loss
 
-    def _capture(self, inputs, labels):
-        static_in, static_lab = inputs.clone(), labels.clone()
+    def _before_capture(self, static_in, static_lab):
         # a model that can use the NEXT batch's ids (DeepFM.prefetch_next: the step's weight-gradient launch touches that
         # batch's table rows in extra workgroups) reads them from a static buffer the caller refreshes per step
-        static_next = inputs.clone() if self._prefetches else None
+        self._static_next = static_in.clone() if self._prefetches else None
         for opt in self.optimizers:
             opt.zero_grad(set_to_none=True)        # the captured backward allocates the gradients in the graph's pool
-        graph = torch.cuda.CUDAGraph()
-        if static_next is not None:
-            self.model.prefetch_next(static_next)
-        with _capture(graph):
-            static_loss = self._body(static_in, static_lab)
-        self._graph, self._static, self._static_next = graph, (static_in, static_lab, static_loss), static_next
+        if self._static_next is not None:
+            self.model.prefetch_next(self._static_next)
 
     def __call__(self, inputs: torch.Tensor, labels: torch.Tensor, next_inputs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """next_inputs (optional): the batch of the FOLLOWING step, already on the device — a loop that is one batch ahead of
@@ -151,30 +194,14 @@ class GraphedTrainStep:
             self.extra_sum = torch.zeros((), dtype=torch.float32, device=inputs.device)
             self._one = losses.unit_scalar(inputs.device)
         self.steps += 1
-        shape = (tuple(inputs.shape), inputs.dtype, tuple(labels.shape), labels.dtype)
-        if self.use_graph and self._graph is None and self._seen >= self.warmup and self._shape == shape:
-            try:
-                self._capture(inputs, labels)
-            except Exception as exc:               # leave training running on the eager HIP path
-                warnings.warn(f"hipGraph capture of the training step failed ({exc!r}); continuing with eager steps")
-                torch.cuda.synchronize()
-                self.use_graph, self._graph = False, None
-        if self._graph is not None and self._shape == shape:
-            static_in, static_lab, static_loss = self._static
-            static_in.copy_(inputs, non_blocking=True)
-            static_lab.copy_(labels, non_blocking=True)
+        if self._replayed.ready(inputs, labels):
             if self._static_next is not None and next_inputs is not None and next_inputs.shape == self._static_next.shape:
                 self._static_next.copy_(next_inputs, non_blocking=True)
-            self._graph.replay()
-            self.last_loss = static_loss
-            return static_loss
-        if self._graph is None:
-            if self._shape != shape:
-                self._shape, self._seen = shape, 0
-            self._seen += 1
-        if self._prefetches and next_inputs is not None and next_inputs.shape == inputs.shape:
-            self.model.prefetch_next(next_inputs)
-        self.last_loss = self._body(inputs, labels)
+            self.last_loss = self._replayed.replay(inputs, labels)
+        else:
+            if self._prefetches and next_inputs is not None and next_inputs.shape == inputs.shape:
+                self.model.prefetch_next(next_inputs)
+            self.last_loss = self._body(inputs, labels)
         return self.last_loss
 
 
@@ -194,15 +221,15 @@ def train_epoch(dataloader, model, optimizers: Union[List[torch.optim.Optimizer]
     idx = -1
     # one batch ahead of the step (the DataLoader's workers are anyway): the step is told the next batch's ids
     batches = iter(dataloader)
-    ahead = next(batches, None)
-    if ahead is not None:
-        ahead = (ahead[0].to(device, non_blocking=True), ahead[1].to(device, non_blocking=True))
+
+    def fetch():
+        batch = next(batches, None)
+        return None if batch is None else (batch[0].to(device, non_blocking=True), batch[1].to(device, non_blocking=True))
+
+    ahead = fetch()
     while ahead is not None:
         idx += 1
-        inputs, labels = ahead
-        ahead = next(batches, None)
-        if ahead is not None:
-            ahead = (ahead[0].to(device, non_blocking=True), ahead[1].to(device, non_blocking=True))
+        (inputs, labels), ahead = ahead, fetch()
         load_data_time += now() - start
         start_train = now()
         step(inputs, labels, next_inputs=ahead[0] if ahead is not None else None)
@@ -222,6 +249,30 @@ def train_epoch(dataloader, model, optimizers: Union[List[torch.optim.Optimizer]
     return loss_dict
 
 
+def _run_epoch(dataloader, device, log_step, profiler, step, log=None) -> int:
+    """What the training loops share: `step(*batch)` for every batch of the loader, its tensors (or lists of tensors:
+    NeuMF's negatives) moved to the device; at the logging steps `log(idx)` (a true return ends the epoch there) and the
+    deferred index check; the profiler stepped.  Returns the number of batches stepped."""
+    n = 0
+    for idx, batch in enumerate(dataloader):
+        step(*[[t.to(device, non_blocking=True) for t in part] if isinstance(part, (list, tuple))
+               else part.to(device, non_blocking=True) for part in batch])
+        n = idx + 1
+        if log_step and idx % log_step == 0:
+            stop = log is not None and log(idx)
+            _lib.check_index_errors()
+            if stop:
+                break
+        if profiler:
+            profiler.step()
+    return n
+
+
+def _mean_since(sums: torch.Tensor, first: Optional[torch.Tensor], n: int) -> List[float]:
+    """The running device sums, less what they held when the epoch began (`first`; None: nothing), over n batches."""
+    return ((sums - first if first is not None else sums) / max(n, 1)).tolist()
+
+
 def train_epoch_cerp(dataloader, model, optimizer, device="cuda", log_step=10, profiler=None, clip_grad=0,
                      target_sparsity=0.8, prune_loss_weight=0, step: Optional[GraphedTrainStep] = None) -> Dict[str, float]:
     """src/trainer/deepfm.py:142-248: `train_epoch` plus `prune_loss_weight * model.embedding.get_prune_loss()` in the
@@ -232,30 +283,28 @@ def train_epoch_cerp(dataloader, model, optimizer, device="cuda", log_step=10, p
     if step is None:
         step = GraphedTrainStep(model, optimizer, clip_grad=clip_grad, extra_loss=lambda: model.embedding.get_prune_loss(),
                                 extra_weight=prune_loss_weight)
-    first_steps = step.steps
     first = (float(step.loss_sum), float(step.extra_sum)) if step.loss_sum is not None else (0.0, 0.0)
+    early = {}
 
     def sums():
         log_loss, prune = float(step.loss_sum) - first[0], float(step.extra_sum) - first[1]
         return {"loss": log_loss + prune_loss_weight * prune, "prune_loss": prune, "log_loss": log_loss}
 
-    idx = -1
-    for idx, (inputs, labels) in enumerate(dataloader):
-        step(inputs.to(device, non_blocking=True), labels.to(device, non_blocking=True))
-        if log_step and idx % log_step == 0:
-            sparsity, num_params = model.embedding.get_sparsity(get_n_params=True)
-            running = sums()
-            _lib.check_index_errors()
-            logger.info("Idx: %d - loss: %.4g - sparsity: %.4g - num_params: %d", idx, running["loss"] / (idx + 1), sparsity,
-                        num_params)
-            if sparsity >= target_sparsity:
-                return dict(running, sparsity=sparsity, num_params=num_params)
-        if profiler:
-            profiler.step()
-    n = max(step.steps - first_steps, 1)
+    def log(idx):
+        sparsity, num_params = model.embedding.get_sparsity(get_n_params=True)
+        running = sums()
+        logger.info("Idx: %d - loss: %.4g - sparsity: %.4g - num_params: %d", idx, running["loss"] / (idx + 1), sparsity,
+                    num_params)
+        if sparsity >= target_sparsity:
+            early.update(running, sparsity=sparsity, num_params=num_params)
+        return bool(early)
+
+    n = _run_epoch(dataloader, device, log_step, profiler, step, log)
+    if early:
+        return early
     sparsity, num_params = model.embedding.get_sparsity(get_n_params=True)
     _lib.check_index_errors()
-    return dict({k: v / n for k, v in sums().items()}, sparsity=sparsity, num_params=num_params)
+    return dict({k: v / max(n, 1) for k, v in sums().items()}, sparsity=sparsity, num_params=num_params)
 
 
 def binary_auc(y_true: torch.Tensor, y_score: torch.Tensor) -> float:
@@ -279,33 +328,19 @@ class GraphedForward:
 
     def __init__(self, model: torch.nn.Module, use_graph: bool = True):
         self.model, self.use_graph = model, use_graph
-        self._graphs: Dict[tuple, object] = {}
+        self._graphs: Dict[tuple, _Replayed] = {}
 
     @torch.no_grad()
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        key = (tuple(x.shape), x.dtype)
-        entry = self._graphs.get(key)
         if not self.use_graph or not x.is_cuda:
             return self.model(x)
-        if entry is None:
-            self._graphs[key] = "seen"
-            return self.model(x)
-        if entry == "seen":
-            try:
-                static_in = x.clone()
-                graph = torch.cuda.CUDAGraph()
-                with _capture(graph):
-                    static_out = self.model(static_in)
-                entry = self._graphs[key] = (graph, static_in, static_out)
-            except Exception as exc:
-                warnings.warn(f"hipGraph capture of the forward failed ({exc!r}); continuing with eager launches")
-                torch.cuda.synchronize()
-                self.use_graph = False
-                return self.model(x)
-        graph, static_in, static_out = entry
-        static_in.copy_(x, non_blocking=True)
-        graph.replay()
-        return static_out
+        key = (tuple(x.shape), x.dtype)
+        forward = self._graphs.get(key)
+        if forward is None:
+            forward = self._graphs[key] = _Replayed(self.model, 1, "the forward", eager="launches")
+        out = forward(x)
+        self.use_graph = forward.enabled          # a failed capture turns the graphs of every shape off
+        return out
 
 
 @torch.no_grad()
@@ -331,6 +366,43 @@ def validate_epoch(val_loader, model, device="cuda") -> Dict[str, float]:
 
 # --------------------------------------------------------------------------------------------------------------------
 # collaborative filtering (LightGCN): reference src/trainer/lightgcn.py:14-165, 378-421
+def cf_step_losses(model, adj, users, pos_items, neg_items, weight_decay: float = 0, info_nce_weight: float = 0,
+                   fused_reg: bool = True, zero: Optional[torch.Tensor] = None):
+    """(loss, rec_loss, reg_loss, cl_loss) of one LightGCN batch as the reference's `_train_step` forms them
+    (src/trainer/lightgcn.py:378-421): propagate, BPR over the batch rows, `weight_decay * get_reg_loss`, optional InfoNCE
+    (`cl_loss` comes weighted).  fused_reg: with a weight decay, let a model that has `forward_with_reg_loss` compute the
+    regulariser inside the propagation and add it inside the BPR launch.  zero: a resident 0-dim zero of the caller's, to
+    save the fill.  No host sync, no shape that depends on data."""
+    fused = fused_reg and weight_decay > 0 and hasattr(model, "forward_with_reg_loss")
+    if fused:      # propagation + regulariser as one node: the regulariser's gradient rows join the propagation's; every
+        # term below reads the propagated tables at the batch's rows only, so the last layer computes only those
+        all_user_emb, all_item_emb, reg_loss = model.forward_with_reg_loss(adj, users, pos_items, neg_items,
+                                                                           batch_rows_only=True)
+        # rec_loss + weight_decay * reg_loss out of the BPR launch itself (no scale / add launches)
+        loss, rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items, plus=reg_loss,
+                                              plus_weight=weight_decay, return_parts=True)
+    else:
+        all_user_emb, all_item_emb = model(adj)
+        rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items)
+    if zero is None:
+        zero = torch.zeros((), device=rec_loss.device)
+    if not fused:
+        reg_loss = model.get_reg_loss(users, pos_items, neg_items) if weight_decay > 0 else zero
+    cl_loss = zero
+    if info_nce_weight > 0:           # SGL without augmentation (src/trainer/lightgcn.py:405-417)
+        # view1 = rows of the batch's DISTINCT users and positives; here: all batch rows, repeats masked out (the loss is
+        # a mean over rows of a softmax over columns: the order of the rows is immaterial), so no shape depends on data
+        view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
+        valid = torch.cat([losses.first_occurrence(users, all_user_emb.shape[0]),
+                           losses.first_occurrence(pos_items, all_item_emb.shape[0])])
+        cl_loss = losses.info_nce(view, view, 0.2, valid=valid) * info_nce_weight
+    if not fused:
+        loss = rec_loss + weight_decay * reg_loss + cl_loss
+    elif info_nce_weight > 0:
+        loss = loss + cl_loss
+    return loss, rec_loss, reg_loss, cl_loss
+
+
 class GraphedCFTrainStep:
     """step(users, pos_items, neg_items): one LightGCN optimisation step as the reference's `_train_step` does it —
     propagate, BPR over the batch rows, `weight_decay * get_reg_loss`, optional InfoNCE on the batch's distinct rows,
@@ -343,44 +415,22 @@ class GraphedCFTrainStep:
                  use_graph: bool = True):
         self.model, self.adj, self.optimizer = model, adj, optimizer
         self.weight_decay, self.info_nce_weight = weight_decay, info_nce_weight
-        self.warmup = warmup
-        self.use_graph = use_graph
-        if self.use_graph and not _capturable([optimizer]):
+        if use_graph and not _capturable([optimizer]):
             warnings.warn("the optimizer keeps its step count on the host (capturable=False): the LightGCN step runs "
                           "eagerly; use recsys_benchmark_amd.optim.Adam")
-            self.use_graph = False
+            use_graph = False
         self.steps = 0
         self.sums: Optional[torch.Tensor] = None
-        self._graph, self._static, self._shape, self._seen = None, None, None, 0
+        self._replayed = _Replayed(self._body, warmup, "the LightGCN step",
+                                   lambda *static: self.optimizer.zero_grad(set_to_none=True), use_graph)
+
+    warmup = property(lambda self: self._replayed.warmup)
+    use_graph = property(lambda self: self._replayed.enabled)
+    _graph = property(lambda self: self._replayed.graph)
 
     def _body(self, users, pos_items, neg_items):
-        fused = self.weight_decay > 0 and hasattr(self.model, "forward_with_reg_loss")
-        if fused:      # propagation + regulariser as one node: the regulariser's gradient rows join the propagation's; every
-            # term below reads the propagated tables at the batch's rows only, so the last layer computes only those
-            all_user_emb, all_item_emb, reg_loss = self.model.forward_with_reg_loss(self.adj, users, pos_items, neg_items,
-                                                                                    batch_rows_only=True)
-        else:
-            all_user_emb, all_item_emb = self.model(self.adj)
-        if fused:      # rec_loss + weight_decay * reg_loss out of the BPR launch itself (no scale / add launches)
-            rec_plus_reg, rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items,
-                                                          plus=reg_loss, plus_weight=self.weight_decay, return_parts=True)
-        else:
-            rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items)
-        zero = torch.zeros((), device=rec_loss.device)
-        if not fused:
-            reg_loss = self.model.get_reg_loss(users, pos_items, neg_items) if self.weight_decay > 0 else zero
-        cl_loss = zero
-        if self.info_nce_weight > 0:           # SGL without augmentation (src/trainer/lightgcn.py:405-417)
-            # view1 = rows of the batch's DISTINCT users and positives; here: all batch rows, repeats masked out (the loss is
-            # a mean over rows of a softmax over columns: the order of the rows is immaterial), so no shape depends on data
-            view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
-            valid = torch.cat([losses.first_occurrence(users, all_user_emb.shape[0]),
-                               losses.first_occurrence(pos_items, all_item_emb.shape[0])])
-            cl_loss = losses.info_nce(view, view, 0.2, valid=valid) * self.info_nce_weight
-        if fused:
-            loss = rec_plus_reg + cl_loss if self.info_nce_weight > 0 else rec_plus_reg
-        else:
-            loss = rec_loss + self.weight_decay * reg_loss + cl_loss
+        loss, rec_loss, reg_loss, cl_loss = cf_step_losses(self.model, self.adj, users, pos_items, neg_items,
+                                                            self.weight_decay, self.info_nce_weight, fused_reg=True)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward(self._one)
         self.optimizer.step()
@@ -393,57 +443,32 @@ class GraphedCFTrainStep:
             self.sums = torch.zeros(4, dtype=torch.float32, device=users.device)
             self._one = losses.unit_scalar(users.device)
         self.steps += 1
-        shape = (tuple(users.shape), users.dtype)
-        if self.use_graph and self._graph is None and self._seen >= self.warmup and self._shape == shape:
-            try:
-                static = (users.clone(), pos_items.clone(), neg_items.clone())
-                self.optimizer.zero_grad(set_to_none=True)
-                graph = torch.cuda.CUDAGraph()
-                with _capture(graph):
-                    parts = self._body(*static)
-                self._graph, self._static = graph, static + (parts,)
-            except Exception as exc:
-                warnings.warn(f"hipGraph capture of the LightGCN step failed ({exc!r}); continuing with eager steps")
-                torch.cuda.synchronize()
-                self.use_graph, self._graph = False, None
-        if self._graph is not None and self._shape == shape:
-            for dst, src in zip(self._static[:3], (users, pos_items, neg_items)):
-                dst.copy_(src, non_blocking=True)
-            self._graph.replay()
-            return self._static[3]
-        if self._graph is None:
-            if self._shape != shape:
-                self._shape, self._seen = shape, 0
-            self._seen += 1
-        return self._body(users, pos_items, neg_items)
+        return self._replayed(users, pos_items, neg_items)
+
+
+def _cf_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, info_nce_weight, step, log=None):
+    """train_epoch_cf, with `log(idx)` (see _run_epoch) in the place of its logging line when one is given."""
+    model.train()
+    model.to(device)
+    if step is None:
+        adj = dataloader.dataset.get_norm_adj().to(device)
+        step = GraphedCFTrainStep(model, adj, optimizer, weight_decay, info_nce_weight)
+    first = step.sums.clone() if step.sums is not None else None
+
+    def log_losses(idx):
+        logger.info("Idx: %d - loss: %.2g - rec_loss: %.2g", idx, *_mean_since(step.sums, first, idx + 1)[:2])
+
+    n = _run_epoch(dataloader, device, log_step, profiler, step, log or log_losses)
+    avg = _mean_since(step.sums, first, n) if step.sums is not None else [0.0] * 4
+    _lib.check_index_errors()
+    return {"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2], "cl_loss": avg[3]}
 
 
 def train_epoch_cf(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None,
                    info_nce_weight=0, step: Optional[GraphedCFTrainStep] = None) -> Dict[str, float]:
     """src/trainer/lightgcn.py:14-77 (`train_epoch`): {"loss", "reg_loss", "rec_loss", "cl_loss"} averaged over the
     batches.  `dataloader.dataset.get_norm_adj()` supplies the normalised adjacency, as in the reference."""
-    model.train()
-    model.to(device)
-    if step is None:
-        adj = dataloader.dataset.get_norm_adj().to(device)
-        step = GraphedCFTrainStep(model, adj, optimizer, weight_decay, info_nce_weight)
-    first_steps = step.steps
-    first = step.sums.clone() if step.sums is not None else None
-    idx = -1
-    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
-        step(users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True),
-             neg_items.to(device, non_blocking=True))
-        if log_step and idx % log_step == 0:
-            done = (step.sums - first if first is not None else step.sums) / (idx + 1)
-            logger.info("Idx: %d - loss: %.2g - rec_loss: %.2g", idx, float(done[0]), float(done[1]))
-            _lib.check_index_errors()
-        if profiler:
-            profiler.step()
-    n = step.steps - first_steps
-    total = (step.sums - first if first is not None else step.sums) if n else torch.zeros(4)
-    avg = (total / max(n, 1)).tolist()
-    _lib.check_index_errors()
-    return {"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2], "cl_loss": avg[3]}
+    return _cf_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, info_nce_weight, step)
 
 
 def train_epoch_pep(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None,
@@ -451,32 +476,18 @@ def train_epoch_pep(dataloader, model, optimizer, device="cuda", log_step=10, we
     """src/trainer/lightgcn.py:294-375: `train_epoch` for a LightGCN on PEP tables — the tables' sparsity is read at the
     logging steps (`get_sparsity_and_param`) and the epoch ends early once it exceeds `target_sparsity`.  Returns the
     four averaged losses plus "sparsity" / "num_params" of the last check."""
-    from .lightgcn import get_sparsity_and_param
-
-    model.train()
-    model.to(device)
-    if step is None:
-        step = GraphedCFTrainStep(model, dataloader.dataset.get_norm_adj().to(device), optimizer, weight_decay, info_nce_weight)
-    first_steps = step.steps
-    first = step.sums.clone() if step.sums is not None else None
     extra = {}
-    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
-        step(users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True),
-             neg_items.to(device, non_blocking=True))
-        if log_step and idx % log_step == 0:
-            sparsity, num_params = get_sparsity_and_param(model)
-            extra = {"sparsity": sparsity, "num_params": num_params}
-            logger.info("Idx: %d - sparsity: %.2f - num_params: %d", idx, sparsity, num_params)
-            _lib.check_index_errors()
-            if sparsity > target_sparsity:
-                logger.info("Found target sparsity")
-                break
-        if profiler:
-            profiler.step()
-    n = max(step.steps - first_steps, 1)
-    avg = ((step.sums - first if first is not None else step.sums) / n).tolist() if step.sums is not None else [0.0] * 4
-    _lib.check_index_errors()
-    return dict({"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2], "cl_loss": avg[3]}, **extra)
+
+    def log(idx):
+        sparsity, num_params = get_sparsity_and_param(model)
+        extra.update(sparsity=sparsity, num_params=num_params)
+        logger.info("Idx: %d - sparsity: %.2f - num_params: %d", idx, sparsity, num_params)
+        if sparsity > target_sparsity:
+            logger.info("Found target sparsity")
+            return True
+
+    avg = _cf_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, info_nce_weight, step, log)
+    return dict(avg, **extra)
 
 
 def train_epoch_optembed(dataloader, model, optimizers, device="cuda", log_step=10, weight_decay=0, profiler=None,
@@ -486,7 +497,6 @@ def train_epoch_optembed(dataloader, model, optimizers, device="cuda", log_step=
     get_weight draws its dimension mask on the device.  Returns the averaged "loss", "reg_loss" (unweighted),
     "rec_loss", "cl_loss" (weighted), "loss_s", and "sparsity" / "n_params" after the epoch."""
     from .embeddings.cf_opt_embed import IOptEmbed
-    from .lightgcn import get_sparsity_and_param
 
     if not isinstance(optimizers, (list, tuple)):
         optimizers = [optimizers]
@@ -498,38 +508,28 @@ def train_epoch_optembed(dataloader, model, optimizers, device="cuda", log_step=
     sums = torch.zeros(5, dtype=torch.float32, device=device)          # loss, reg_loss, rec_loss, cl_loss, loss_s
     one = losses.unit_scalar(device)
     zero = torch.zeros((), device=device)
-    idx = -1
-    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
-        users, pos_items = users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True)
-        neg_items = neg_items.to(device, non_blocking=True)
-        all_user_emb, all_item_emb = model(adj)
-        rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users, pos_items, neg_items)
-        reg_loss = model.get_reg_loss(users, pos_items, neg_items) if weight_decay > 0 else zero
-        cl_loss = zero
-        if info_nce_weight > 0:        # the batch's distinct users and positives (repeats masked out, no unique())
-            view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
-            valid = torch.cat([losses.first_occurrence(users, all_user_emb.shape[0]),
-                               losses.first_occurrence(pos_items, all_item_emb.shape[0])])
-            cl_loss = losses.info_nce(view, view, 0.2, valid=valid) * info_nce_weight
+
+    def log(idx):
+        sparsity, n_params = get_sparsity_and_param(model)
+        avg = _mean_since(sums, None, idx + 1)
+        logger.info("Idx: %d - sparsity=%.4f - n_params=%d - loss: %.4g - loss_s: %.4g", idx, sparsity, n_params,
+                    avg[0], avg[4])
+
+    def batch(users, pos_items, neg_items):
+        loss, rec_loss, reg_loss, cl_loss = cf_step_losses(model, adj, users, pos_items, neg_items, weight_decay,
+                                                            info_nce_weight, fused_reg=False, zero=zero)
         loss_s = zero
         for t in tables:
             loss_s = loss_s + t.get_l_s().to(device)
-        loss = rec_loss + weight_decay * reg_loss + cl_loss + alpha * loss_s
+        loss = loss + alpha * loss_s
         for opt in optimizers:
             opt.zero_grad()
         loss.backward(one)
         for opt in optimizers:
             opt.step()
-        sums += torch.stack([loss.detach(), reg_loss.detach(), rec_loss.detach(), cl_loss.detach(), loss_s.detach()])
-        if log_step and idx % log_step == 0:
-            sparsity, n_params = get_sparsity_and_param(model)
-            avg = (sums / (idx + 1)).tolist()
-            logger.info("Idx: %d - sparsity=%.4f - n_params=%d - loss: %.4g - loss_s: %.4g", idx, sparsity, n_params,
-                        avg[0], avg[4])
-            _lib.check_index_errors()
-        if profiler:
-            profiler.step()
-    avg = (sums / max(idx + 1, 1)).tolist()
+        sums.add_(torch.stack([loss.detach(), reg_loss.detach(), rec_loss.detach(), cl_loss.detach(), loss_s.detach()]))
+
+    avg = _mean_since(sums, None, _run_epoch(dataloader, device, log_step, profiler, batch, log))
     _lib.check_index_errors()
     sparsity, n_params = get_sparsity_and_param(model)
     return {"loss": avg[0], "reg_loss": avg[1], "rec_loss": avg[2], "cl_loss": avg[3], "loss_s": avg[4],
@@ -562,6 +562,22 @@ def ndcg_recall_at_k(y_pred: torch.Tensor, y_true: Sequence[Union[Sequence[int],
     return float(ndcg), float(recall)
 
 
+def _ranking_metrics(val_loader, topk, device, k: int, metrics: Optional[List[str]], profiler) -> Dict[str, float]:
+    """What the ranking validations share: `topk(users)` ([users, k] item ids) for every batch of the loader, then
+    {"ndcg"}, or {"ndcg", "recall"} when `metrics` names both."""
+    preds, truths = [], []
+    for users, pos_items in val_loader:
+        preds.append(topk(torch.as_tensor(users).to(device)))
+        truths.extend(pos_items)
+        if profiler:
+            profiler.step()
+    ndcg, recall = ndcg_recall_at_k(torch.cat(preds), truths, k)
+    _lib.check_index_errors()
+    if metrics is not None and "ndcg" in metrics and "recall" in metrics:
+        return {"ndcg": ndcg, "recall": recall}
+    return {"ndcg": ndcg}
+
+
 @torch.no_grad()
 def validate_epoch_cf(train_dataset, val_loader, model, device="cuda", k=20, filter_item_on_train=True, profiler=None,
                       metrics: Optional[List[str]] = None) -> Dict[str, float]:
@@ -574,17 +590,8 @@ def validate_epoch_cf(train_dataset, val_loader, model, device="cuda", k=20, fil
     model = model.to(device)
     user_embs, item_embs = model(adj)
     csr = train_items_csr(graph, user_embs.shape[0], device) if filter_item_on_train else None
-    preds, truths = [], []
-    for users, pos_items in val_loader:
-        preds.append(score_topk(user_embs, item_embs, torch.as_tensor(users).to(device), k, csr))
-        truths.extend(pos_items)
-        if profiler:
-            profiler.step()
-    ndcg, recall = ndcg_recall_at_k(torch.cat(preds), truths, k)
-    _lib.check_index_errors()
-    if metrics is not None and "ndcg" in metrics and "recall" in metrics:
-        return {"ndcg": ndcg, "recall": recall}
-    return {"ndcg": ndcg}
+    return _ranking_metrics(val_loader, lambda users: score_topk(user_embs, item_embs, users, k, csr), device, k, metrics,
+                            profiler)
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -619,25 +626,18 @@ def train_epoch_nmf(dataloader, model, optimizer, device="cuda", log_step=10, we
     model.to(device)
     sums = torch.zeros(3, dtype=torch.float32, device=device)
     one = losses.unit_scalar(device)
-    idx = -1
-    for idx, (users, pos_items, neg_items) in enumerate(dataloader):
-        users, pos_items = users.to(device, non_blocking=True), pos_items.to(device, non_blocking=True)
-        if isinstance(neg_items, (list, tuple)):
-            neg_items = [n.to(device, non_blocking=True) for n in neg_items]
-        else:
-            neg_items = neg_items.to(device, non_blocking=True)
+
+    def log(idx):
+        logger.info("Idx: %d - loss: %.2g - rec_loss: %.2g - reg_loss: %.2g", idx, *_mean_since(sums, None, idx + 1))
+
+    def batch(users, pos_items, neg_items):
         loss, rec_loss, reg_loss = nmf_step_losses(model, users, pos_items, neg_items, weight_decay)
         optimizer.zero_grad()
         loss.backward(one)
         optimizer.step()
-        sums += torch.stack([loss.detach(), rec_loss.detach(), reg_loss.detach().float()])
-        if log_step and idx % log_step == 0:
-            avg = (sums / (idx + 1)).tolist()
-            logger.info("Idx: %d - loss: %.2g - rec_loss: %.2g - reg_loss: %.2g", idx, *avg)
-            _lib.check_index_errors()
-        if profiler:
-            profiler.step()
-    avg = (sums / max(idx + 1, 1)).tolist()
+        sums.add_(torch.stack([loss.detach(), rec_loss.detach(), reg_loss.detach().float()]))
+
+    avg = _mean_since(sums, None, _run_epoch(dataloader, device, log_step, profiler, batch, log))
     _lib.check_index_errors()
     return {"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2]}
 
@@ -655,20 +655,14 @@ def validate_epoch_nmf(train_dataset, val_loader, model, device="cuda", k=20, fi
     model = model.to(device)
     csr = train_items_csr(graph, model.num_user, device) if filter_item_on_train else None
     crow, col = (None, None) if csr is None else csr
-    preds, truths = [], []
-    for users, pos_items in val_loader:
-        users = torch.as_tensor(users).to(device).to(torch.int64)
+
+    def topk(users):
+        users = users.to(torch.int64)
         scores = score_all_items(model, users)
         out = torch.empty((users.numel(), k), dtype=torch.int64, device=device)
         _lib.check(_lib.load().mi_mask_topk_rows(scores.data_ptr(), scores.stride(0), scores.shape[0], scores.shape[1],
                                                  users.data_ptr(), _lib.ptr(crow), _lib.ptr(col), k, out.data_ptr(), None,
                                                  _lib.stream_ptr(scores.device)), "mi_mask_topk_rows")
-        preds.append(out)
-        truths.extend(pos_items)
-        if profiler:
-            profiler.step()
-    ndcg, recall = ndcg_recall_at_k(torch.cat(preds), truths, k)
-    _lib.check_index_errors()
-    if metrics is not None and "ndcg" in metrics and "recall" in metrics:
-        return {"ndcg": ndcg, "recall": recall}
-    return {"ndcg": ndcg}
+        return out
+
+    return _ranking_metrics(val_loader, topk, device, k, metrics, profiler)

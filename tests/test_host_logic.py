@@ -489,3 +489,100 @@ def test_deterministic_switch_restores_the_fused_tail_setting_and_refuses_crossn
     finally:
         pkg.use_deterministic_algorithms(False)
         mlp.FUSED_TAIL = before
+
+
+def test_replayed_warms_up_captures_once_and_replays_through_static_clones(monkeypatch):
+    """The state machine of trainer._Replayed (the one place the graphed steps and GraphedForward capture and replay), on
+    CPU tensors: the graph, the capture context and the synchronise are stubs; the stub graph's replay() re-runs what
+    the body registered while it was being 'captured', on the static tensors it was captured with."""
+    import warnings
+
+    from recsys_benchmark_amd import trainer
+
+    capturing, syncs, eager, hooked = [], [], [], []
+
+    class Graph:
+        def replay(self):
+            self.rerun()
+
+    class Capture:
+        def __init__(self, graph):
+            self.graph = graph
+
+        def __enter__(self):
+            capturing.append(self.graph)
+
+        def __exit__(self, *exc):
+            capturing.pop()
+
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", Graph)
+    monkeypatch.setattr(trainer, "_capture", Capture)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda: syncs.append(1))
+
+    def body(x, y):
+        out = x * 2 + y
+        if capturing:
+            capturing[-1].rerun = lambda: out.copy_(x * 2 + y)
+        else:
+            eager.append(x)
+        return out
+
+    def pair(n, seed):
+        return torch.arange(n, dtype=torch.float32) + seed, torch.full((n,), 0.5 * seed)
+
+    # (a) exactly `warmup` eager calls, then the capture, which serves that very call
+    step = trainer._Replayed(body, 2, "the thing", before_capture=lambda *static: hooked.append(static))
+    for seed in (1, 2):
+        x, y = pair(3, seed)
+        assert torch.equal(step(x, y), x * 2 + y) and step.graph is None
+    assert len(eager) == 2 and not hooked
+    x, y = pair(3, 3)
+    out = step(x, y)
+    assert isinstance(step.graph, Graph) and len(eager) == 2 and torch.equal(out, x * 2 + y)
+    assert len(hooked) == 1 and all(s is not t and torch.equal(s, t) for s, t in zip(hooked[0], (x, y)))
+    # (c) another shape runs eagerly and leaves the graph alone; the captured shape replays again afterwards, and
+    # (d) the replay sees the new inputs through the static clones and answers in the static output
+    graph = step.graph
+    x5, y5 = pair(5, 4)
+    assert torch.equal(step(x5, y5), x5 * 2 + y5) and len(eager) == 3 and eager[-1] is x5 and step.graph is graph
+    x, y = pair(3, 5)
+    again = step(x, y)
+    assert again is out and torch.equal(again, x * 2 + y) and len(eager) == 3 and step.graph is graph
+    assert torch.equal(hooked[0][0], x) and torch.equal(hooked[0][1], y) and not syncs
+    # a dtype change is another shape too
+    assert step(x.double(), y.double()).dtype == torch.float64 and len(eager) == 4
+
+    # (b) a shape change before the capture restarts the count
+    del eager[:]
+    step = trainer._Replayed(body, 2, "the thing")
+    for n in (3, 3, 4, 4):                      # two calls of [3] do not count towards [4]
+        step(*pair(n, 1))
+        assert step.graph is None
+    assert len(eager) == 4
+    step(*pair(4, 2))
+    assert step.graph is not None and len(eager) == 4
+
+    # (e) a capture that raises: one warning, one synchronise, that call's eager result, and never another attempt
+    attempts = []
+
+    def fragile(x):
+        if capturing:
+            attempts.append(1)
+            raise RuntimeError("not capturable")
+        return x + 1
+
+    step = trainer._Replayed(fragile, 1, "the thing", eager="launches")
+    x = torch.ones(2)
+    assert torch.equal(step(x), x + 1) and step.enabled
+    with pytest.warns(UserWarning, match=r"hipGraph capture of the thing failed \(RuntimeError\('not capturable'\)\); "
+                                         "continuing with eager launches") as caught:
+        assert torch.equal(step(x), x + 1)
+    assert len(caught) == 1 and syncs == [1] and not step.enabled and step.graph is None
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for _ in range(3):
+            assert torch.equal(step(x), x + 1)
+    assert attempts == [1] and syncs == [1]
+    # turned off by the owner: never captures
+    step = trainer._Replayed(fragile, 0, "the thing", enabled=False)
+    assert torch.equal(step(x), x + 1) and torch.equal(step(x), x + 1) and attempts == [1]
