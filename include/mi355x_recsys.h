@@ -188,6 +188,30 @@ MI_API int mi_dual_gather_fwd_off(const int64_t *idx, const int64_t *offsets, in
                                   int64_t n2, int64_t mod1, int64_t div2, int32_t op, int32_t xform, int32_t *err,
                                   void *stream);
 
+/* The same family in TABLE form: out[i] = T1'[i % mod1] (op) T2'[i / div2] for i = 0 .. N-1 — get_weight() of
+ * QRHashingEmbedding / CerpEmbedding / RetrainCerpEmbedding (the module's forward over arange(N)), which a LightGCN or
+ * NeuMF asks for on every step.  No index tensor and no error word: every row is in range by construction (tables that
+ * cannot cover N rows — n1 < min(N, mod1) or n2 < ceil(N / div2) — are MI_ERR_INVALID_ARG).  Same arithmetic per element as
+ * mi_dual_gather_fwd: bit-identical to it over arange(N).  out is [N, De] ([N, 2 De] for cat).
+ * mi_dual_table_bwd: owner computes.  Row r of T1 sums rows r, r + mod1, ... of g_out, row r of T2 rows r div2 ..
+ * (r + 1) div2 - 1 (times the other table's transformed row for mult, its own half for cat), in ascending i, by one
+ * thread per float4; the transform's derivative is applied once per table element after the sum; every element of
+ * gT1 / gT2 (and gS1 / gS2 for xform 1) is WRITTEN exactly once (rows without a contributor get zeros): no atomics, no
+ * zero fill, the same bits on every run.  Rows with more than 16 contributors are cut into chunks of 8 contributors
+ * (constants: the order of additions depends on the shapes only), the chunk sums go to `workspace`
+ * (mi_dual_table_bwd_workspace_elems floats, may be 0 / NULL when no row is cut; no state between launches) and a second
+ * launch joins them in a fixed order.  De % 4 == 0 with 16-byte aligned operands (masks 4-byte aligned), De <= 1024 and
+ * fewer than 2^31 output elements; anything else is MI_ERR_UNSUPPORTED (the caller keeps the lookup over arange(N)). */
+MI_API int mi_dual_table_fwd(const float *T1, const float *T2, const float *S1, const float *S2, const uint8_t *M1,
+                             const uint8_t *M2, float *out, int64_t N, int32_t De, int64_t n1, int64_t n2,
+                             int64_t mod1, int64_t div2, int32_t op, int32_t xform, void *stream);
+MI_API int64_t mi_dual_table_bwd_workspace_elems(int64_t N, int32_t De, int64_t n1, int64_t n2, int64_t mod1,
+                                                 int64_t div2);
+MI_API int mi_dual_table_bwd(const float *g_out, const float *T1, const float *T2, const float *S1, const float *S2,
+                             const uint8_t *M1, const uint8_t *M2, float *gT1, float *gT2, float *gS1, float *gS2,
+                             int64_t N, int32_t De, int64_t n1, int64_t n2, int64_t mod1, int64_t div2, int32_t op,
+                             int32_t xform, float *workspace, void *stream);
+
 /* Dense gradients of the above into caller-zeroed gT1/gT2 (and gS1/gS2 for xform 1),
  * float atomics; tables of <= 4096 elements are pre-summed per workgroup in LDS. */
 MI_API int mi_dual_gather_bwd(const int64_t *idx, const float *g_out, const float *T1,
@@ -731,6 +755,26 @@ MI_API int mi_rowsq_fwd_armed(const float *U, const int64_t *ui, const float *P,
 MI_API int mi_rowsq_bwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi,
                         const float *Nn, const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP,
                         int64_t nN, const float *g, float *dU, float *dP, float *dN, void *stream);
+/* mi_reg_prune_rows_fwd/bwd: the batch-row terms of the CERP step on LightGCN / SingleLightGCN
+ *   (get_prune_and_reg_loss_lightgcn, src/models/embeddings/cerp_embedding_utils.py:15-62) on materialised tables U [nU, D]
+ *   and I [nI, D], from one read of each row: ui, pi int64[B], ni int64[Bn], uvalid uint8[B] (1 = first occurrence of the
+ *   user in the batch: the reference's torch.unique);
+ *     out[0] = (sum_b |U[ui[b]]|^2 + sum_b |I[pi[b]]|^2 + sum_k |I[ni[k]]|^2) / (2 B)
+ *     out[1] = -(sum_{b: uvalid[b]} |tanh(k_tanh U[ui[b]])|^2 + sum_b |tanh(k_tanh I[pi[b]])|^2 + sum_k |tanh(k_tanh I[ni[k]])|^2)
+ *   An id outside its table is skipped and ORs MI_IDX_OUT_OF_RANGE into *err.  The workgroup partials are joined in index
+ *   order by the last workgroup to take a ticket; workspace: mi_reg_prune_rows_workspace_elems(B, Bn) floats, armed != 0:
+ *   the caller promises its last word is zero on entry (the kernel leaves it zero), else it is zeroed by a memset node.
+ *   bwd: g[0], g[1] the upstream gradients of out[0], out[1]; adds both terms' row gradients into the caller-zeroed dense
+ *   dU / dI (float atomics; either may be NULL).                                                                     */
+MI_API int64_t mi_reg_prune_rows_workspace_elems(int64_t B, int64_t Bn);
+MI_API int mi_reg_prune_rows_fwd(const float *U, const float *I, const int64_t *ui, const int64_t *pi,
+                                 const int64_t *ni, const uint8_t *uvalid, int64_t B, int64_t Bn, int32_t D,
+                                 int64_t nU, int64_t nI, float k_tanh, int32_t *err, float *workspace, int32_t armed,
+                                 float *out, void *stream);
+MI_API int mi_reg_prune_rows_bwd(const float *U, const float *I, const int64_t *ui, const int64_t *pi,
+                                 const int64_t *ni, const uint8_t *uvalid, int64_t B, int64_t Bn, int32_t D,
+                                 int64_t nU, int64_t nI, float k_tanh, const float *g, float *dU, float *dI,
+                                 void *stream);
 MI_API int64_t mi_bpr_workspace_elems(int64_t B);
 MI_API int mi_bpr_fwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi,
                       const float *Nn, const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP,

@@ -509,6 +509,75 @@ def dual_gather(idx, T1, T2, mod1, div2, op="add", S1=None, S2=None, M1=None, M2
     return DualGather.apply(idx, T1, T2, S1, S2, M1, M2, int(mod1), int(div2), OPS[op], xform, fields, bool(sparse2), offsets)
 
 
+class DualTable(torch.autograd.Function):
+    """out[i] = T1'[i % mod1] (op) T2'[i // div2] for i = 0 .. N-1 (mi_dual_table_fwd / _bwd): the whole table, no index
+    tensor; the backward writes every gradient element once, in a fixed order, without atomics."""
+
+    @staticmethod
+    def forward(ctx, T1, T2, S1, S2, M1, M2, N: int, mod1: int, div2: int, op: int, xform: int):
+        dev = _lib.require_gpu(T1, T2)
+        T1c, T2c = _f32c(T1), _f32c(T2)
+        S1c = None if S1 is None else _f32c(S1)
+        S2c = None if S2 is None else _f32c(S2)
+        M1c = None if M1 is None else M1.to(torch.uint8).contiguous()
+        M2c = None if M2 is None else M2.to(torch.uint8).contiguous()
+        De = T1c.shape[1]
+        out = torch.empty((N, 2 * De if op == OPS["cat"] else De), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().mi_dual_table_fwd(T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c), _lib.ptr(M1c),
+                                                 _lib.ptr(M2c), out.data_ptr(), N, De, T1c.shape[0], T2c.shape[0], mod1, div2,
+                                                 op, xform, _lib.stream_ptr(dev)), "mi_dual_table_fwd")
+        ctx.save_for_backward(T1c, T2c, S1c, S2c, M1c, M2c)
+        ctx.meta = (N, De, mod1, div2, op, xform)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        T1c, T2c, S1c, S2c, M1c, M2c = ctx.saved_tensors
+        N, De, mod1, div2, op, xform = ctx.meta
+        dev = g.device
+        g = _f32c(g)
+        lib = _lib.load()
+        # every element of the four gradients is written by the kernel: no zero fill
+        gT1, gT2 = torch.empty_like(T1c), torch.empty_like(T2c)
+        gS1 = torch.empty_like(S1c) if xform == XF_SOFT else None
+        gS2 = torch.empty_like(S2c) if xform == XF_SOFT else None
+        ne = int(lib.mi_dual_table_bwd_workspace_elems(N, De, T1c.shape[0], T2c.shape[0], mod1, div2))
+        ws = torch.empty(ne, dtype=torch.float32, device=dev) if ne else None      # chunk sums of the long rows: no state
+        _lib.check(lib.mi_dual_table_bwd(g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
+                                         _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1),
+                                         _lib.ptr(gS2), N, De, T1c.shape[0], T2c.shape[0], mod1, div2, op, xform, _lib.ptr(ws),
+                                         _lib.stream_ptr(dev)), "mi_dual_table_bwd")
+        return gT1, gT2, gS1, gS2, None, None, None, None, None, None, None
+
+
+def dual_table_supported(N: int, mod1: int, div2: int, *tables) -> bool:
+    """Whether mi_dual_table_* takes this shape (csrc/dual_table.hip, fill(): float4 rows of 16-byte aligned fp32 tables
+    on the GPU, 32-bit element counters); otherwise the caller keeps `dual_gather` over an explicit arange(N).
+    tables: T1, T2 and, where the transform has them, the logits or masks."""
+    T1, T2 = tables[0], tables[1]
+    De = T1.shape[1] if T1.dim() == 2 else 0
+    if not (T1.is_cuda and T2.dim() == 2 and De % 4 == 0 and 4 <= De <= 1024 and N >= 0 and mod1 > 0 and div2 > 0):
+        return False
+
+    def chunks(contributors):          # kLongRow / kChunk of the kernel
+        return -(-contributors // 8) if contributors > 16 else 1
+
+    items = T1.shape[0] * chunks(-(-N // mod1)) + T2.shape[0] * chunks(min(div2, N))
+    if max(2 * N * De, items * De, T1.shape[0], T2.shape[0], mod1, div2) >= 2 ** 31:
+        return False
+    if T1.shape[0] < min(N, mod1) or T2.shape[0] < -(-N // div2):
+        return False                   # (tables that cannot cover N rows: the lookup flags those ids)
+    return all(t is None or (t.dim() == 2 and t.shape[1] == De and t.data_ptr() % 16 == 0) for t in tables)
+
+
+def dual_table(T1, T2, N, mod1, div2, op="add", S1=None, S2=None, M1=None, M2=None):
+    """The two-table family's whole table [N, De] ([N, 2 De] for cat): `dual_gather(arange(N), ...)` bit for bit, without
+    the index tensor, and with a backward that has no atomics and no zero fill (gradients differ from dual_gather's in
+    the order of the float additions only).  Check `dual_table_supported` first."""
+    xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
+    return DualTable.apply(T1, T2, S1, S2, M1, M2, int(N), int(mod1), int(div2), OPS[op], xform)
+
+
 def csr_rows(values, crow, col, ids, D: int, N: int) -> torch.Tensor:
     """Dense rows of a CSR-stored table (inference only, like the reference's PrunedEmbedding)."""
     dev = _lib.require_gpu(crow, ids)

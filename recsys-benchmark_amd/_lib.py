@@ -45,6 +45,9 @@ SIGNATURES = {
     "mi_dual_gather_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _p, _p],
     "mi_dual_gather_bwd_fields": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64,
                                   _i64, _i64, _i32, _i32, _p, _i32, _p, _p, _p],
+    "mi_dual_table_fwd": [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _p],
+    "mi_dual_table_bwd_workspace_elems": [_i64, _i32, _i64, _i64, _i64, _i64],
+    "mi_dual_table_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p],
     "mi_xform_gather_fwd": [_p, _p, _p, _p, _i64, _i64, _p, _i64, _i32, _i64, _i32, _p, _p],
     "mi_xform_gather_bwd": [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i32, _i64, _i32, _p],
     "mi_gather_rows_quant": [_p, _p, _i32, _p, _p, _p, _i64, _i32, _i64, _p, _p],
@@ -98,6 +101,9 @@ SIGNATURES = {
     "mi_rowsq_fwd": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p],
     "mi_rowsq_fwd_armed": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p],
     "mi_rowsq_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],
+    "mi_reg_prune_rows_workspace_elems": [_i64, _i64],
+    "mi_reg_prune_rows_fwd": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i64, _i64, ctypes.c_float, _p, _p, _i32, _p, _p],
+    "mi_reg_prune_rows_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i64, _i64, ctypes.c_float, _p, _p, _p, _p],
     "mi_bpr_workspace_elems": [_i64],
     "mi_bpr_fwd": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "mi_bpr_fwd_armed": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],
@@ -187,7 +193,8 @@ SIGNATURES = {
 _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.c_int64,
              "mi_bpr_workspace_elems": ctypes.c_int64, "mi_lse_diag_workspace_elems": ctypes.c_int64,
              "mi_sort_field_rows_workspace_bytes": ctypes.c_int64, "mi_tail_part_elems": ctypes.c_int64,
-             "mi_dual_gather_bwd_rows_workspace_elems": ctypes.c_int64}
+             "mi_dual_gather_bwd_rows_workspace_elems": ctypes.c_int64,
+             "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

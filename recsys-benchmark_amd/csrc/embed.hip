@@ -21,12 +21,10 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "dual_xform.hpp"
 
 namespace {
 using namespace mi;
-
-enum { OP_MULT = 0, OP_ADD = 1, OP_CAT = 2 };
-enum { XF_NONE = 0, XF_SOFT = 1, XF_MASK = 2 };
 
 struct DualTables {
   const float *T1, *T2;      // [n1,De], [n2,De]
@@ -55,26 +53,6 @@ __device__ __forceinline__ void split_id(int64_t id, const DualTables &t, int64_
     i1 = id % t.mod1;
     i2 = id / t.div2;
   }
-}
-
-__device__ __forceinline__ float sigmoidf_(float s) { return 1.f / (1.f + expf(-s)); }
-__device__ __forceinline__ float signf_(float w) { return (w > 0.f) ? 1.f : ((w < 0.f) ? -1.f : 0.f); }
-__device__ __forceinline__ float soft_(float w, float s) {
-  const float u = fabsf(w) - sigmoidf_(s);
-  return signf_(w) * (u > 0.f ? u : 0.f);
-}
-
-template <int XF>
-__device__ __forceinline__ float4 load_row4(const float *T, const float *S, const uint8_t *M, int64_t o) {
-  float4 w = ld4(T + o);
-  if constexpr (XF == XF_SOFT) {
-    const float4 s = ld4(S + o);
-    w.x = soft_(w.x, s.x); w.y = soft_(w.y, s.y); w.z = soft_(w.z, s.z); w.w = soft_(w.w, s.w);
-  } else if constexpr (XF == XF_MASK) {
-    const uchar4 m = *reinterpret_cast<const uchar4 *>(M + o);
-    w.x = m.x ? w.x : 0.f; w.y = m.y ? w.y : 0.f; w.z = m.z ? w.z : 0.f; w.w = m.w ? w.w : 0.f;
-  }
-  return w;
 }
 
 // element offset of lookup i's output row(s); CAT puts table-1 rows at field f and table-2 rows at

@@ -284,6 +284,105 @@ __global__ __launch_bounds__(kBlock) void k_rowsq_bwd(
   }
 }
 
+// ---- CERP's batch-row terms: get_prune_and_reg_loss_lightgcn (src/models/embeddings/cerp_embedding_utils.py:15-62) on the
+// materialised tables, both from one read of each row:
+//   out[0] = reg   = ( sum_b |U[ui[b]]|^2 + sum_b |I[pi[b]]|^2 + sum_k |I[ni[k]]|^2 ) / (2 B)
+//   out[1] = prune = -( sum_{b: uvalid[b]} |tanh(K U[ui[b]])|^2 + sum_b |tanh(K I[pi[b]])|^2 + sum_k |tanh(K I[ni[k]])|^2 )
+// B users and positives, Bn negatives; uvalid flags the first occurrence of each user (the reference's torch.unique).
+// Row x of the B + B + Bn is one wave's; an id outside its table is skipped and flagged.  The workgroup partials (two
+// per workgroup) are joined by the last workgroup to take a ticket, in index order, as in k_rowsq_fwd.
+struct BatchRows {
+  const float *U, *I;
+  const int64_t *ui, *pi, *ni;
+  const uint8_t *uvalid;
+  int64_t B, Bn, nU, nI;
+  int D;
+  // row x of the batch: its table row (NULL = out of range) and whether it counts in the prune term
+  __device__ __forceinline__ const float *row(int64_t x, bool &prune, bool &bad, int64_t &off) const {
+    const bool user = x < B;
+    const int64_t id = user ? ui[x] : (x < 2 * B ? pi[x - B] : ni[x - 2 * B]);
+    prune = !user || uvalid[x] != 0;
+    bad = (uint64_t)id >= (uint64_t)(user ? nU : nI);
+    off = id * D;
+    return bad ? nullptr : (user ? U : I) + off;
+  }
+};
+
+__global__ __launch_bounds__(kBlock) void k_reg_prune_fwd(BatchRows a, float k_tanh, int *err, float *__restrict__ part,
+                                                          unsigned *ticket, float *__restrict__ out) {
+  __shared__ float red[2][kWavesPerBlock];
+  __shared__ bool last;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float sq = 0.f, th = 0.f;
+  bool any_bad = false;
+  const int64_t R = 2 * a.B + a.Bn;
+  for (int64_t x = (int64_t)blockIdx.x * kWavesPerBlock + wv; x < R; x += (int64_t)gridDim.x * kWavesPerBlock) {
+    bool prune, bad;
+    int64_t off;
+    const float *w = a.row(x, prune, bad, off);
+    if (bad) { any_bad = true; continue; }
+    for (int j = lane; j < a.D; j += kWave) {
+      const float v = w[j], t = tanhf(k_tanh * v);
+      sq += v * v;
+      th += prune ? t * t : 0.f;
+    }
+  }
+  if (any_bad && lane == 0 && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
+  sq = wave_sum(sq);
+  th = wave_sum(th);
+  if (lane == 0) { red[0][wv] = sq; red[1][wv] = th; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s0 = 0.f, s1 = 0.f;
+    for (int j = 0; j < kWavesPerBlock; ++j) { s0 += red[0][j]; s1 += red[1][j]; }
+    // (publish_partial with two words per workgroup: both stores acknowledged before the ticket is taken)
+    __hip_atomic_store(part + 2 * blockIdx.x, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(part + 2 * blockIdx.x + 1, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (last) {
+    float s0 = 0.f, s1 = 0.f;
+    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) {
+      s0 += read_partial(part + 2 * j);
+      s1 += read_partial(part + 2 * j + 1);
+    }
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    __syncthreads();
+    if (lane == 0) { red[0][wv] = s0; red[1][wv] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t0 = 0.f, t1 = 0.f;
+      for (int j = 0; j < kWavesPerBlock; ++j) { t0 += red[0][j]; t1 += red[1][j]; }
+      out[0] = t0 / (2.f * (float)a.B);
+      out[1] = -t1;
+      *ticket = 0;
+    }
+  }
+}
+
+// dTable[row] += g[0] w / B + g[1] d(-tanh^2(K w))/dw,   d(-tanh^2(K w))/dw = -2 K tanh(K w) (1 - tanh^2(K w))
+// (float atomics into caller-zeroed dense gradients, as k_rowsq_bwd: a batch's rows repeat)
+__global__ __launch_bounds__(kBlock) void k_reg_prune_bwd(BatchRows a, float k_tanh, const float *__restrict__ g,
+                                                          float *__restrict__ dU, float *__restrict__ dI) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float cr = g[0] / (float)a.B, cp = -2.f * k_tanh * g[1];
+  const int64_t R = 2 * a.B + a.Bn;
+  for (int64_t x = (int64_t)blockIdx.x * kWavesPerBlock + wv; x < R; x += (int64_t)gridDim.x * kWavesPerBlock) {
+    bool prune, bad;
+    int64_t off;
+    const float *w = a.row(x, prune, bad, off);
+    float *d = x < a.B ? dU : dI;
+    if (bad || !d) continue;
+    for (int j = lane; j < a.D; j += kWave) {
+      const float v = w[j], t = tanhf(k_tanh * v);
+      atomicAdd(d + off + j, cr * v + (prune ? cp * t * (1.f - t * t) : 0.f));
+    }
+  }
+}
+
 // ------------------------------------------------------------------ mask + top-k per row ----
 constexpr int kCand = 2048;   // candidate slots in LDS
 constexpr int kSample = 4096; // row prefix that sets the candidate bound
@@ -556,6 +655,40 @@ int mi_rowsq_bwd(const float *U, const int64_t *ui, const float *P, const int64_
   const RowBounds nb{nU, nP, nN, nullptr};
   if (!U || !P || !Nn || !ui || !pi || !ni || !g) return MI_ERR_INVALID_ARG;
   MI_LAUNCH("rowsq_bwd", k_rowsq_bwd, grid_for_waves(B), kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, g, dU, dP, dN);
+  return launch_status();
+}
+
+static bool batch_rows(BatchRows &a, const float *U, const float *I, const int64_t *ui, const int64_t *pi, const int64_t *ni,
+                       const uint8_t *uvalid, int64_t B, int64_t Bn, int32_t D, int64_t nU, int64_t nI) {
+  if (B <= 0 || Bn < 0 || D <= 0 || nU < 0 || nI < 0 || !U || !I || !ui || !pi || (Bn > 0 && !ni) || !uvalid) return false;
+  a = BatchRows{U, I, ui, pi, ni, uvalid, B, Bn, nU, nI, D};
+  return true;
+}
+
+int64_t mi_reg_prune_rows_workspace_elems(int64_t B, int64_t Bn) {
+  if (B < 0 || Bn < 0) return 0;
+  return 2 * (int64_t)grid_for_waves(2 * B + Bn) + 1;   // two partials per workgroup + the ticket word
+}
+
+int mi_reg_prune_rows_fwd(const float *U, const float *I, const int64_t *ui, const int64_t *pi, const int64_t *ni,
+                          const uint8_t *uvalid, int64_t B, int64_t Bn, int32_t D, int64_t nU, int64_t nI, float k_tanh,
+                          int32_t *err, float *workspace, int32_t armed, float *out, void *stream) {
+  BatchRows a;
+  if (!batch_rows(a, U, I, ui, pi, ni, uvalid, B, Bn, D, nU, nI) || !workspace || !out) return MI_ERR_INVALID_ARG;
+  const int grid = grid_for_waves(2 * B + Bn);
+  if (!armed && hipMemsetAsync(workspace + 2 * grid, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess)
+    return MI_ERR_LAUNCH;
+  MI_LAUNCH("reg_prune_rows_fwd", k_reg_prune_fwd, grid, kBlock, stream, a, k_tanh, err, workspace,
+            reinterpret_cast<unsigned *>(workspace + 2 * grid), out);
+  return launch_status();
+}
+
+int mi_reg_prune_rows_bwd(const float *U, const float *I, const int64_t *ui, const int64_t *pi, const int64_t *ni,
+                          const uint8_t *uvalid, int64_t B, int64_t Bn, int32_t D, int64_t nU, int64_t nI, float k_tanh,
+                          const float *g, float *dU, float *dI, void *stream) {
+  BatchRows a;
+  if (!batch_rows(a, U, I, ui, pi, ni, uvalid, B, Bn, D, nU, nI) || !g) return MI_ERR_INVALID_ARG;
+  MI_LAUNCH("reg_prune_rows_bwd", k_reg_prune_bwd, grid_for_waves(2 * B + Bn), kBlock, stream, a, k_tanh, g, dU, dI);
   return launch_status();
 }
 

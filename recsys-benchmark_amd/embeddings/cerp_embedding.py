@@ -113,6 +113,12 @@ class CerpEmbedding(IEmbedding):
         return 1 - n_params / total_params
 
     def get_weight(self):
+        """The whole table [N, D]: forward(arange(N)) bit for bit.  In table form (mi_dual_table_*: no index tensor, a
+        backward without atomics) when the shape allows it and no bag mode reduces the rows."""
+        N, tables = self._num_item, (self.p_weight, self.q_weight, self.p_threshold, self.q_threshold)
+        if self._mode is None and _kernels.dual_table_supported(N, self._bucket_size, self.q_entity_per_row, *tables):
+            return _kernels.dual_table(self.p_weight, self.q_weight, N, self._bucket_size, self.q_entity_per_row, op="add",
+                                       S1=self.p_threshold, S2=self.q_threshold)
         all_idxes = torch.arange(self._num_item, device=self.p_weight.data.device)
         return self(all_idxes)
 
@@ -196,6 +202,13 @@ class RetrainCerpEmbedding(IEmbedding):
         return masks
 
     def get_weight(self):
+        """The whole table [N, D]: forward(arange(N)) bit for bit; the dense form goes through mi_dual_table_* (see
+        CerpEmbedding.get_weight), the row-gradient form (sparse=True) keeps the lookup."""
+        N, tables = self._num_item, (self.p_weight, self.q_weight)
+        if (not self._sparse and self._mode is None and self.p_mask.shape == self.p_weight.shape
+                and _kernels.dual_table_supported(N, self._bucket_size, self.q_entity_per_row, *tables)):
+            return _kernels.dual_table(self.p_weight, self.q_weight, N, self._bucket_size, self.q_entity_per_row, op="add",
+                                       M1=self.p_mask, M2=self.q_mask)
         all_idxes = torch.arange(self._num_item, device=self.p_weight.data.device)
         return self(all_idxes)
 

@@ -6,7 +6,7 @@ Drop-in: same constructor arguments, parameter holders `emb1` / `emb2` (state_di
     and is addressed by the QUOTIENT (names inverted w.r.t. the paper: `divider: 2` = a 2-row emb1);
   * operation "cat" concatenates along dim=1, so [B,F] ids give [B,2F,D/2].
 Index math, both row gathers and the combine are one HIP kernel (mi_dual_gather_fwd);
-get_weight() is that kernel over arange(N) and stays differentiable.
+get_weight() is the same arithmetic in table form (mi_dual_table_fwd: no index tensor) and stays differentiable.
 """
 import functools
 import math
@@ -109,4 +109,10 @@ class QRHashingEmbedding(IEmbedding):
                     and (De // 4) & (De // 4 - 1) == 0)
 
     def get_weight(self):
+        """The whole table: forward(arange(N)) bit for bit.  Without a bag mode and without the row-form gradient it goes
+        through mi_dual_table_* (no index tensor, a backward without atomics) when the shape allows it."""
+        w1, w2 = self._tables()
+        d, N = self._divider, self._num_item
+        if self._mode is None and not self._sparse2 and _kernels.dual_table_supported(N, d, d, w1, w2):
+            return _kernels.dual_table(w1, w2, N, d, d, op=self._operation)
         return self(torch.arange(self._num_item, device=self.emb1.weight.device))

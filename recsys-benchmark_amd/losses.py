@@ -273,6 +273,64 @@ def reg_loss_rows(user_table, item_table, users, pos_items, neg_items):
     return _RowSqFn.apply(user_table, item_table, item_table, users, pos_items, neg_items)
 
 
+class _RegPruneFn(torch.autograd.Function):
+    """(reg, prune) of the CERP step over the batch's rows of materialised tables (mi_reg_prune_rows_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, U, I, ui, pi, ni, uvalid, k_tanh: float):
+        dev = _lib.require_gpu(U, I, ui)
+        lib = _lib.load()
+        U, I = _kernels._f32c(U), _kernels._f32c(I)
+        ui, pi, ni = (_kernels._i64c(t).view(-1) for t in (ui, pi, ni))
+        uvalid = uvalid.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
+        B, Bn, D = ui.numel(), ni.numel(), U.shape[1]
+        if U.dim() != 2 or I.dim() != 2 or I.shape[1] != D or pi.numel() != B or uvalid.numel() != B or B == 0:
+            raise ValueError("reg / prune loss: users, positives and the user mask must be [B], the tables [*, D]")
+        ws, armed = _ticket_workspace("reg_prune", dev, lib.mi_reg_prune_rows_workspace_elems(B, Bn))
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.check(lib.mi_reg_prune_rows_fwd(U.data_ptr(), I.data_ptr(), ui.data_ptr(), pi.data_ptr(), ni.data_ptr(),
+                                             uvalid.data_ptr(), B, Bn, D, U.shape[0], I.shape[0], float(k_tanh),
+                                             _lib.err_word(dev).data_ptr(), ws.data_ptr(), int(armed), out.data_ptr(),
+                                             _lib.stream_ptr(dev)), "mi_reg_prune_rows_fwd")
+        ctx.save_for_backward(U, I, ui, pi, ni, uvalid)
+        ctx.k_tanh = float(k_tanh)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_reg, g_prune):
+        U, I, ui, pi, ni, uvalid = ctx.saved_tensors
+        g = torch.stack([_kernels._f32c(g_reg).view(()), _kernels._f32c(g_prune).view(())])
+        need_u, need_i = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # users and items that are the two row segments of ONE matrix (SingleLightGCN's table): one zero-filled gradient
+        joint = None
+        if (need_u and need_i and U.is_contiguous() and I.is_contiguous() and I.data_ptr() == U.data_ptr() + U.numel() * 4
+                and U.untyped_storage().data_ptr() == I.untyped_storage().data_ptr()):
+            joint = torch.zeros((U.shape[0] + I.shape[0], U.shape[1]), dtype=torch.float32, device=U.device)
+            dU, dI = joint[: U.shape[0]], joint[U.shape[0]:]
+        else:
+            dU = torch.zeros_like(U) if need_u else None
+            dI = torch.zeros_like(I) if need_i else None
+        _lib.check(_lib.load().mi_reg_prune_rows_bwd(U.data_ptr(), I.data_ptr(), ui.data_ptr(), pi.data_ptr(), ni.data_ptr(),
+                                                     uvalid.data_ptr(), ui.numel(), ni.numel(), U.shape[1], U.shape[0],
+                                                     I.shape[0], ctx.k_tanh, g.data_ptr(), _lib.ptr(dU), _lib.ptr(dI),
+                                                     _lib.stream_ptr(g.device)), "mi_reg_prune_rows_bwd")
+        return dU, dI, None, None, None, None, None
+
+
+def reg_prune_loss_rows(user_table, item_table, users, pos_items, neg_items, user_valid=None, k_tanh: float = 100):
+    """(reg_loss, prune_loss) of the CERP step on LightGCN / SingleLightGCN
+    (get_prune_and_reg_loss_lightgcn, src/models/embeddings/cerp_embedding_utils.py:15-62) from the MATERIALISED tables
+    (`get_weight()`, which the step has anyway for the propagation), one launch each way:
+        reg   = (|U[users]|^2 + |I[pos]|^2 + |I[neg]|^2) / (2 len(users))
+        prune = -(|tanh(k U[distinct users])|^2 + |tanh(k I[pos])|^2 + |tanh(k I[neg])|^2)
+    users, pos_items [B]; neg_items any shape (B * K ids).  user_valid ([B] bool, default `first_occurrence(users)`)
+    stands in for the reference's torch.unique: no data-dependent shape.  SingleLightGCN passes the two row segments
+    of its one table.  An id outside its table is skipped and flagged (check_index_errors)."""
+    if user_valid is None:
+        user_valid = first_occurrence(users, user_table.shape[0])
+    return _RegPruneFn.apply(user_table, item_table, users, pos_items, neg_items, user_valid, k_tanh)
+
+
 def bpr_loss_multi(user_embs, pos_embs, neg_embs):
     """src/losses.py:50-68 — K negatives per positive ([N, K, D]): the BPR kernel over the N*K (user, positive, negative)
     triples, summed over the negatives and averaged over the N samples."""

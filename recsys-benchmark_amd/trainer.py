@@ -388,19 +388,128 @@ def cf_step_losses(model, adj, users, pos_items, neg_items, weight_decay: float 
         zero = torch.zeros((), device=rec_loss.device)
     if not fused:
         reg_loss = model.get_reg_loss(users, pos_items, neg_items) if weight_decay > 0 else zero
-    cl_loss = zero
-    if info_nce_weight > 0:           # SGL without augmentation (src/trainer/lightgcn.py:405-417)
-        # view1 = rows of the batch's DISTINCT users and positives; here: all batch rows, repeats masked out (the loss is
-        # a mean over rows of a softmax over columns: the order of the rows is immaterial), so no shape depends on data
-        view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
-        valid = torch.cat([losses.first_occurrence(users, all_user_emb.shape[0]),
-                           losses.first_occurrence(pos_items, all_item_emb.shape[0])])
-        cl_loss = losses.info_nce(view, view, 0.2, valid=valid) * info_nce_weight
+    cl_loss = _cf_info_nce(all_user_emb, all_item_emb, users, pos_items, info_nce_weight) if info_nce_weight > 0 else zero
     if not fused:
         loss = rec_loss + weight_decay * reg_loss + cl_loss
     elif info_nce_weight > 0:
         loss = loss + cl_loss
     return loss, rec_loss, reg_loss, cl_loss
+
+
+def _cf_info_nce(all_user_emb, all_item_emb, users, pos_items, info_nce_weight, user_valid=None):
+    """SGL without augmentation (src/trainer/lightgcn.py:405-417), weighted: view1 = rows of the batch's DISTINCT users and
+    positives; here: all batch rows, repeats masked out (the loss is a mean over rows of a softmax over columns: the
+    order of the rows is immaterial), so no shape depends on data."""
+    view = torch.cat([torch.index_select(all_user_emb, 0, users), torch.index_select(all_item_emb, 0, pos_items)], 0)
+    if user_valid is None:
+        user_valid = losses.first_occurrence(users, all_user_emb.shape[0])
+    valid = torch.cat([user_valid, losses.first_occurrence(pos_items, all_item_emb.shape[0])])
+    return losses.info_nce(view, view, 0.2, valid=valid) * info_nce_weight
+
+
+def _negatives_2d(neg_items, like: torch.Tensor) -> torch.Tensor:
+    """[B, K] from what the CF loaders hand over: [B], [B, K], or a list of K [B] tensors (stacked on dim 1, as
+    src/models/embeddings/cerp_embedding_utils.py:106-110 does)."""
+    if isinstance(neg_items, (list, tuple)):
+        neg_items = torch.stack(list(neg_items), dim=1)
+    elif neg_items.dim() == 1:
+        neg_items = neg_items.unsqueeze(1)
+    return neg_items.to(like.device)
+
+
+def cf_cerp_step_losses(model, adj, users, pos_items, neg_items, weight_decay: float = 0, info_nce_weight: float = 0,
+                        prune_loss_weight: float = 0):
+    """(loss, rec_loss, reg_loss, cl_loss, prune_loss) of one CERP batch on LightGCN / SingleLightGCN as
+    `train_epoch_cerp` forms them (src/models/embeddings/cerp_embedding_utils.py:99-149): K negatives per positive through
+    `bpr_loss_multi`, the regulariser and the tanh prune loss over the batch's rows of the INPUT tables (users
+    de-duplicated for the prune term), optional InfoNCE (`cl_loss` comes weighted, `prune_loss` unweighted).
+
+    Each table's `get_weight()` is taken ONCE and shared by the propagation and the batch-row terms
+    (`losses.reg_prune_loss_rows`: no second lookup, no torch.unique); the BPR term reads the B * K triples straight
+    from the propagated tables (no [B, K, D] gather).  No host sync, no shape that depends on data."""
+    from . import _kernels
+    from .lightgcn import LightGCN, SingleLightGCN
+
+    neg = _negatives_2d(neg_items, users)
+    B, K = neg.shape
+    matrix = model.sparse_dropout(adj)
+    if isinstance(model, LightGCN):
+        user_table, item_table = model.user_emb_table.get_weight(), model.item_emb_table.get_weight()
+        all_user_emb, all_item_emb = _kernels.lightgcn_propagate(matrix, user_table, item_table, model.num_layers)
+    elif isinstance(model, SingleLightGCN):
+        table = model.emb_table.get_weight()
+        sizes = (model._num_user, model._num_item)
+        all_user_emb, all_item_emb = torch.split(_kernels.lightgcn_propagate(matrix, table, None, model.num_layers), sizes)
+        user_table, item_table = torch.split(table, sizes)
+    else:
+        raise ValueError(f"Not supported model for prune loss {model}")
+    neg_flat = neg.reshape(-1)
+    users_k, pos_k = (users, pos_items) if K == 1 else (users.repeat_interleave(K), pos_items.repeat_interleave(K))
+    # bpr_loss_multi: the sum over the K negatives, averaged over the B samples = K times the mean over the B * K triples
+    rec_loss = losses.bpr_loss_rows(all_user_emb, all_item_emb, users_k, pos_k, neg_flat)
+    if K != 1:
+        rec_loss = rec_loss * K
+    user_valid = losses.first_occurrence(users, user_table.shape[0])
+    reg_loss, prune_loss = losses.reg_prune_loss_rows(user_table, item_table, users, pos_items, neg_flat, user_valid)
+    loss = rec_loss + weight_decay * reg_loss + prune_loss * prune_loss_weight
+    cl_loss = torch.zeros((), device=rec_loss.device)
+    if info_nce_weight > 0:
+        cl_loss = _cf_info_nce(all_user_emb, all_item_emb, users, pos_items, info_nce_weight, user_valid)
+        loss = loss + cl_loss
+    return loss, rec_loss, reg_loss, cl_loss, prune_loss
+
+
+CERP_CLIP_GRAD_NORM = 100      # cerp_embedding_utils.py:98
+
+
+def train_epoch_cerp_cf(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None,
+                        info_nce_weight=0, prune_loss_weight=0, target_sparsity=0.8, step=None) -> Dict[str, float]:
+    """src/models/embeddings/cerp_embedding_utils.py:65-218 (`train_epoch_cerp`): a LightGCN / SingleLightGCN epoch on CERP
+    tables — several negatives per positive, the tanh prune loss, gradients clipped at norm 100, and the tables'
+    sparsity read at the logging steps.  Once it reaches `target_sparsity` the epoch returns AT ONCE with the running
+    SUMS (what the reference returns there); otherwise the averages over the batches.  Keys: "loss", "reg_loss",
+    "rec_loss", "cl_loss" (weighted), "prune_loss" (unweighted), "sparsity", "num_params".  Eager; the sums stay on
+    the device and are read at the logging steps only.
+    step (optional, for tests): a callable (users, pos_items, neg_items) -> the five losses of a batch it has already
+    stepped the optimizer for, in place of the built-in step."""
+    model.train()
+    model.to(device)
+    keys = ("loss", "reg_loss", "rec_loss", "cl_loss", "prune_loss")
+    sums = torch.zeros(len(keys), dtype=torch.float32, device=device)
+    if step is None:
+        adj = dataloader.dataset.get_norm_adj().to(device)
+        one = losses.unit_scalar(device)
+
+        def step(users, pos_items, neg_items):
+            loss, rec_loss, reg_loss, cl_loss, prune_loss = cf_cerp_step_losses(
+                model, adj, users, pos_items, neg_items, weight_decay, info_nce_weight, prune_loss_weight)
+            optimizer.zero_grad()
+            loss.backward(one)
+            torch.nn.utils.clip_grad_norm_(model.parameters(), CERP_CLIP_GRAD_NORM)
+            optimizer.step()
+            return loss, rec_loss, reg_loss, cl_loss, prune_loss
+
+    def batch(users, pos_items, neg_items):
+        loss, rec_loss, reg_loss, cl_loss, prune_loss = step(users, pos_items, neg_items)
+        sums.add_(torch.stack([t.detach().float() for t in (loss, reg_loss, rec_loss, cl_loss, prune_loss)]))
+
+    early = {}
+
+    def log(idx):
+        sparsity, num_params = get_sparsity_and_param(model)
+        running = dict(zip(keys, sums.tolist()))
+        logger.info("Idx: %d - sparsity: %.2g - num_params: %d - loss: %.2g - prune_loss: %.2g", idx, sparsity, num_params,
+                    running["loss"] / (idx + 1), running["prune_loss"] / (idx + 1))
+        if sparsity >= target_sparsity:
+            early.update(running, sparsity=sparsity, num_params=num_params)
+        return bool(early)
+
+    n = _run_epoch(dataloader, device, log_step, profiler, batch, log)
+    if early:
+        return early
+    _lib.check_index_errors()
+    sparsity, num_params = get_sparsity_and_param(model)
+    return dict(zip(keys, _mean_since(sums, None, n)), sparsity=sparsity, num_params=num_params)
 
 
 class GraphedCFTrainStep:
@@ -640,6 +749,79 @@ def train_epoch_nmf(dataloader, model, optimizer, device="cuda", log_step=10, we
     avg = _mean_since(sums, None, _run_epoch(dataloader, device, log_step, profiler, batch, log))
     _lib.check_index_errors()
     return {"loss": avg[0], "rec_loss": avg[1], "reg_loss": avg[2]}
+
+
+def nmf_prune_step_losses(model, users, pos_items, neg_items, weight_decay: float = 0, prune_loss_weight: float = 0):
+    """(loss, rec_loss, reg_loss, prune_loss): `nmf_step_losses` plus `prune_loss_weight * model.get_prune_loss_tanh(...)`
+    over the batch's rows, as `_train_step` adds it (src/trainer/nmf.py:483-487); `prune_loss` comes unweighted, a zero
+    without a weight."""
+    loss, rec_loss, reg_loss = nmf_step_losses(model, users, pos_items, neg_items, weight_decay)
+    if prune_loss_weight > 0:
+        neg = torch.cat(list(neg_items)) if isinstance(neg_items, (list, tuple)) else neg_items
+        prune_loss = model.get_prune_loss_tanh(users, pos_items, neg)
+        loss = loss + prune_loss * prune_loss_weight
+    else:
+        prune_loss = torch.zeros((), device=rec_loss.device)
+    return loss, rec_loss, reg_loss, prune_loss
+
+
+def _nmf_pruning_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, target_sparsity,
+                       prune_loss_weight, clip_grad_norm, keys, step=None) -> Dict[str, float]:
+    """What `train_epoch_pep` and `train_epoch_cerp` of src/trainer/nmf.py:284-443 share: the NeuMF step (with the prune
+    term and the clipping when asked for), the tables' sparsity read at the logging steps, a `break` once it EXCEEDS
+    `target_sparsity`, and the averages over the batches stepped."""
+    from .neumf import get_sparsity_and_param as nmf_sparsity_and_param
+
+    model.train()
+    model.to(device)
+    sums = torch.zeros(4, dtype=torch.float32, device=device)          # loss, rec_loss, reg_loss, prune_loss
+    extra = {}
+    if step is None:
+        one = losses.unit_scalar(device)
+
+        def step(users, pos_items, neg_items):
+            parts = nmf_prune_step_losses(model, users, pos_items, neg_items, weight_decay, prune_loss_weight)
+            optimizer.zero_grad()
+            parts[0].backward(one)
+            if clip_grad_norm > 0:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad_norm)
+            optimizer.step()
+            return parts
+
+    def batch(users, pos_items, neg_items):
+        sums.add_(torch.stack([t.detach().float() for t in step(users, pos_items, neg_items)]))
+
+    def log(idx):
+        sparsity, num_params = nmf_sparsity_and_param(model)
+        extra.update(sparsity=sparsity, num_params=num_params)
+        logger.info("Idx: %d - sparsity: %.2f - num_params: %d - loss: %.2g", idx, sparsity, num_params,
+                    _mean_since(sums, None, idx + 1)[0])
+        if sparsity > target_sparsity:
+            logger.info("Found target sparsity")
+            return True
+
+    avg = dict(zip(("loss", "rec_loss", "reg_loss", "prune_loss"),
+                   _mean_since(sums, None, _run_epoch(dataloader, device, log_step, profiler, batch, log))))
+    _lib.check_index_errors()
+    return dict({k: avg[k] for k in keys}, **extra)
+
+
+def train_epoch_pep_nmf(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None,
+                        target_sparsity=0, step=None) -> Dict[str, float]:
+    """src/trainer/nmf.py:284-357 (`train_epoch_pep`): a NeuMF epoch on PEP tables — {"loss", "reg_loss", "rec_loss"}
+    averaged over the batches stepped, plus "sparsity" / "num_params" of the last logging step; the epoch ends once the
+    sparsity exceeds `target_sparsity`.  step: see train_epoch_cerp_cf (four losses, the last a zero)."""
+    return _nmf_pruning_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, target_sparsity, 0, 0,
+                              ("loss", "reg_loss", "rec_loss"), step)
+
+
+def train_epoch_cerp_nmf(dataloader, model, optimizer, device="cuda", log_step=10, weight_decay=0, profiler=None,
+                         target_sparsity=0, prune_loss_weight=0, clip_grad_norm=100, step=None) -> Dict[str, float]:
+    """src/trainer/nmf.py:360-443 (`train_epoch_cerp`): `train_epoch_pep_nmf` with `prune_loss_weight *
+    model.get_prune_loss_tanh(...)` in the loss and the gradients clipped at `clip_grad_norm`; adds "prune_loss"
+    (unweighted) to the returned averages."""
+    return _nmf_pruning_epoch(dataloader, model, optimizer, device, log_step, weight_decay, profiler, target_sparsity,
+                              prune_loss_weight, clip_grad_norm, ("loss", "reg_loss", "rec_loss", "prune_loss"), step)
 
 
 @torch.no_grad()
