@@ -1167,6 +1167,40 @@ MI_API int mi_comm_abort(void *comm);
 MI_API int mi_comm_all_to_all(void *comm, const void *send, void *recv, int64_t bytes_per_peer, void *stream);
 MI_API int mi_comm_all_reduce_sum_f32(void *comm, float *buf, int64_t count, void *stream);
 
+/* ---- global magnitude pruning (src/utils.py:8-34 `prune`; scripts/lightgcn/run_mag_prune.py:55-81 and
+ * scripts/cf_train/run_mag_prune.py:55-97 `get_v` call it once per table and per search candidate) ------------------
+ * One table W fp32[N, D] (row stride ldw), k elements to prune, floor m kept per row.  key(w) = bits(|w|) (+0.0 and -0.0
+ * share key 0; inf is the largest ordinary key; NaN is outside the contract: its key sorts above inf and nothing else is
+ * promised for it).  The m largest keys of a row are protected (equal keys: lower column first); the k smallest
+ * unprotected keys of the table become +0.0 (equal keys at the cut: lower flat index i * D + j first); every other
+ * element is copied bit for bit.  The reference's topk / argsort / two index writes are a k-th element selection here: a
+ * row cut (m > 0 only; 8 bytes per row), three histogram passes of a most-significant-first radix select (integer
+ * adds only: the result does not depend on the order of arrival), one apply pass — and, when the cut falls inside a run
+ * of equal keys (to be expected at hundreds of millions of fp32 values), one more read of the table that counts the
+ * equals per chunk, so that the apply pass can take the first ones in flat order: five table passes (six with a floor)
+ * in the plain case, one more in that case.  Nothing is read back to the host.
+ *   mi_mag_prune: out == NULL selects only (the workspace then feeds mi_mag_csr_*); out may alias W (the reference
+ *     prunes in place).  workspace: mi_mag_prune_workspace_bytes(N) bytes, no state between calls (zeroed by a memset
+ *     node).  N * D <= 2^32 - 1, m <= D and N * m + k <= N * D, else MI_ERR_INVALID_ARG (beyond that bound the reference
+ *     prunes its own `inf` markers in sort order); D <= 1024, else MI_ERR_UNSUPPORTED.
+ *   mi_mag_prune_result: copies {T, elements with key < T, elements with key == T, equals of T that are pruned}
+ *     (unprotected elements only) from the workspace of a finished mi_mag_prune to result4 (device uint32[4]).
+ * CSR of the pruned table (what PrunedEmbedding serves, scripts/lightgcn/infer_lightgcn.py:224-247) without the dense
+ * pruned table being written; exact zeros of either sign are dropped, as Tensor.to_sparse_csr() drops them:
+ *   mi_mag_csr_count: crow int64[N + 1] (crow[N] = number of stored elements; the caller sizes col / values from it);
+ *   mi_mag_csr_fill:  col int64 (ascending inside a row) and values fp32, by ballot / popcount compaction.
+ *   prune_ws: the workspace of a finished mi_mag_prune with the same W, N, D, m — or NULL (then m == 0): W is taken as
+ *   it is, a dense-to-CSR conversion.  csr_ws: mi_mag_csr_workspace_bytes(N) bytes, shared by count and fill.        */
+MI_API int64_t mi_mag_prune_workspace_bytes(int64_t N);
+MI_API int mi_mag_prune(const float *W, int64_t ldw, float *out, int64_t ldo, int64_t N, int32_t D, int64_t k,
+                        int32_t m, void *workspace, void *stream);
+MI_API int mi_mag_prune_result(const void *workspace, uint32_t *result4, void *stream);
+MI_API int64_t mi_mag_csr_workspace_bytes(int64_t N);
+MI_API int mi_mag_csr_count(const float *W, int64_t ldw, int64_t N, int32_t D, const void *prune_ws, int32_t m,
+                            void *csr_ws, int64_t *crow, void *stream);
+MI_API int mi_mag_csr_fill(const float *W, int64_t ldw, int64_t N, int32_t D, const void *prune_ws, int32_t m,
+                           const void *csr_ws, const int64_t *crow, int64_t *col, float *values, void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.

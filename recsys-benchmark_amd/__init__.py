@@ -12,6 +12,7 @@ from .factory import (get_ctr_model, get_graph_model, load_ctr_model, load_graph
 from .lightgcn import LightGCN, SingleLightGCN
 from .losses import BCEWithLogitsLoss
 from .neumf import ModelFlag, NeuMF
+from .pruning import evaluate_pruned, prune, prune_table, search_min_item, to_pruned_tables
 
 
 
@@ -47,5 +48,5 @@ __all__ = [
     "DeepFM", "IEmbedding", "VanillaEmbedding", "NAME_TO_CLS", "get_embedding",
     "LightGCN", "SingleLightGCN", "get_ctr_model", "get_graph_model", "load_ctr_model", "load_graph_model",
     "save_cf_emb_checkpoint", "save_ctr_checkpoint", "MI355XLibraryError", "check_index_errors", "use_deterministic_algorithms",
-    "BCEWithLogitsLoss", "NeuMF", "ModelFlag",
+    "BCEWithLogitsLoss", "NeuMF", "ModelFlag", "prune", "prune_table", "to_pruned_tables", "evaluate_pruned", "search_min_item",
 ]

@@ -179,6 +179,12 @@ SIGNATURES = {
     "mi_neumf_score_supported": [_i32, _p, _i32, _i32],
     "mi_neumf_score_all": [_p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _i32, _p, _i64, _p,
                            _p],
+    "mi_mag_prune_workspace_bytes": [_i64],
+    "mi_mag_prune": [_p, _i64, _p, _i64, _i64, _i32, _i64, _i32, _p, _p],
+    "mi_mag_prune_result": [_p, _p, _p],
+    "mi_mag_csr_workspace_bytes": [_i64],
+    "mi_mag_csr_count": [_p, _i64, _i64, _i32, _p, _i32, _p, _p, _p],
+    "mi_mag_csr_fill": [_p, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p],
     "mi_comm_available": [],
     "mi_comm_unique_id": [ctypes.c_char_p],
     "mi_comm_init": [ctypes.c_char_p, _i32, _i32, ctypes.POINTER(ctypes.c_void_p)],
@@ -194,7 +200,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_bpr_workspace_elems": ctypes.c_int64, "mi_lse_diag_workspace_elems": ctypes.c_int64,
              "mi_sort_field_rows_workspace_bytes": ctypes.c_int64, "mi_tail_part_elems": ctypes.c_int64,
              "mi_dual_gather_bwd_rows_workspace_elems": ctypes.c_int64,
-             "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64}
+             "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64,
+             "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

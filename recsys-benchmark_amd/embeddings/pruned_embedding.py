@@ -43,6 +43,22 @@ class PrunedEmbedding(IEmbedding):
         result.is_cuda = result.values.is_cuda
         return result
 
+    @classmethod
+    @torch.no_grad()
+    def from_pruned(cls, source: Union[torch.Tensor, IEmbedding], p: float, min_item: int = 0,
+                    mode=None) -> "PrunedEmbedding":
+        """The table (a tensor, or an IEmbedding's get_weight()) magnitude-pruned by (p, min_item) — src/utils.py:8-34 —
+        and stored as CSR, the triple written by the fused build of csrc/mag_prune.hip: equal, array for array, to
+        from_weight(pruning.prune_table(weight.clone(), p, min_item)), without the dense pruned table."""
+        from ..pruning import _pruned_csr
+
+        weight = source.get_weight() if isinstance(source, IEmbedding) else source
+        crow, col, values = _pruned_csr(weight, p, min_item)
+        result = cls(weight.shape[0], weight.shape[1], mode)
+        result.values, result.crow_indices, result.col_indices = values, crow, col
+        result.is_cuda = values.is_cuda
+        return result
+
     def to_cuda(self):
         """Move the CSR triple to the GPU (reference API, pruned_embedding.py:51-65)."""
         self.to("cuda")
