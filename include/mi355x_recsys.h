@@ -1201,6 +1201,46 @@ MI_API int mi_mag_csr_count(const float *W, int64_t ldw, int64_t N, int32_t D, c
 MI_API int mi_mag_csr_fill(const float *W, int64_t ldw, int64_t N, int32_t D, const void *prune_ws, int32_t m,
                            const void *csr_ws, const int64_t *crow, int64_t *col, float *values, void *stream);
 
+/* ---- device-resident CF data (src/dataset/cf_graph_dataset.py:50-168 `CFGraphDataset`; src/metrics.py:70-108
+ * `get_ndcg_recall`) ------------------------------------------------------------------------------------------------
+ * mi_cf_sample_triples: samples [first, first + n) of an epoch in one launch, one thread per sample.
+ *   pair_user / pair_item int64[P]: the stored interactions, duplicates kept; pair_crow int64[U + 1]: user u's stored
+ *     list is pair_item[pair_crow[u] .. pair_crow[u + 1]) (read in uniform mode only; pair_user in popularity mode only).
+ *   pos_crow int64[U + 1] / pos_col int32[pos_nnz]: the membership CSR, every row DISTINCT and ASCENDING.
+ *   mode MI_CF_SAMPLE_POPULARITY: sample i is pair order[i - first] (order int64[n]; NULL: pair i).
+ *   mode MI_CF_SAMPLE_UNIFORM: sample i belongs to user i / per_user_num; its positive is a uniformly drawn entry of the
+ *     user's STORED list (a duplicated interaction is twice as likely, as random.choice over the reference's list).
+ *   The K negatives of a sample are uniform over the items outside the user's pos_col row and pairwise distinct — the
+ *     law of the reference's rejection loop, drawn without a loop: rank among the remaining non-positives, bumped past
+ *     the earlier picks, mapped to the item by one binary search (<= K * ceil(log2(deg + 1)) reads of pos_col).
+ *   Draws (all arithmetic modulo 2^64; mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ *     0x94D049BB133111EB; z ^ z >> 31):  base = mix64(seed + G * (epoch + 1));  key(i) = mix64(base + S * (i + 1));
+ *     bits(i, d) = mix64(key(i) + G * (d + 1)) with G = 0x9E3779B97F4A7C15, S = 0xD1B54A32D192ED03, i the index in the
+ *     epoch, d = 0 for the positive and 1 + t for negative t;  value = (bits * range) >> 64, range = the stored list's
+ *     length resp. num_items - deg - t.  That reduction is biased by at most range / 2^64 per value; accepted.
+ *     Stateless: any sub-range of an epoch gives the bits the whole epoch gives there.
+ *   Outputs: users int64[n], pos int64[n], neg int64[K, n] (K-major: each of the K negative vectors is contiguous).
+ *   A sample whose pair index or user is out of range, whose user has no stored item, or whose user has
+ *     deg + K > num_items writes -1 to users, pos and its K negatives, ORs MI_IDX_OUT_OF_RANGE into *err and reads
+ *     nothing else.  K > MI_CF_MAX_NEG or num_items >= 2^31: MI_ERR_UNSUPPORTED.
+ * mi_ndcg_recall_rows: row i of pred int64[n, ld] (its first k columns; k <= ld) against the truth row of users[i] in
+ *   crow int64[U + 1] / col int64[nnz] (rows distinct and ascending): relevant_j = pred[i, j] in the row, dcg = sum over
+ *   ascending j of relevant_j * weight[j], length = min(row length, k), ndcg[i] = dcg / ideal[length - 1],
+ *   recall[i] = hits / length, all float64.  weight double[k] = 1 / log2(j + 2) and ideal double[k] = its running sum
+ *   come from the caller, so that host and device use the same constants to the last bit.  An empty truth row gives
+ *   NaN for both (the reference's 0 / 0); users[i] outside [0, U) gives NaN and ORs MI_IDX_OUT_OF_RANGE into *err.   */
+#define MI_CF_SAMPLE_UNIFORM 0
+#define MI_CF_SAMPLE_POPULARITY 1
+#define MI_CF_MAX_NEG 32
+MI_API int mi_cf_sample_triples(const int64_t *pair_user, const int64_t *pair_item, const int64_t *pair_crow, int64_t P,
+                                const int64_t *pos_crow, const int32_t *pos_col, int64_t pos_nnz, int64_t U,
+                                int64_t num_items, int32_t mode, int64_t per_user_num, int32_t K, const int64_t *order,
+                                int64_t seed, int64_t epoch, int64_t first, int64_t n, int64_t *users, int64_t *pos,
+                                int64_t *neg, int *err, void *stream);
+MI_API int mi_ndcg_recall_rows(const int64_t *pred, int64_t ld, const int64_t *users, int64_t n, int32_t k,
+                               const int64_t *crow, const int64_t *col, int64_t U, int64_t nnz, const double *weight,
+                               const double *ideal, double *ndcg, double *recall, int *err, void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.

@@ -1903,3 +1903,60 @@ def optembed_cf_draw(n: int, D: int, law: int, hi: int, cdf, salt: int, device) 
                                               optembed_cf_seed(device).data_ptr(), salt, 1, None, n, D, None,
                                               _lib.stream_ptr(device)), "mi_optembed_cf_fwd")
     return k
+
+
+# ---- device-resident CF data (csrc/cf_data.hip) ------------------------------------------------------------------------
+CF_SAMPLE_MODES = {"uniform": 0, "popularity": 1}
+
+
+def cf_sample_triples(pair_user, pair_item, pair_crow, pos_crow, pos_col, num_items: int, mode: str, per_user_num: int,
+                      K: int, first: int, n: int, seed: int, epoch: int, order=None):
+    """(users [n], pos [n], neg [K, n]) int64: samples [first, first + n) of epoch `epoch` by mi_cf_sample_triples (see
+    include/mi355x_recsys.h for the draw function).  pos_col is int32; `order` (popularity mode) is int64 [n]."""
+    dev = _lib.require_gpu(pair_user, pair_item, pair_crow, pos_crow, pos_col, order)
+    if pos_col.dtype != torch.int32 or not pos_col.is_contiguous():
+        raise TypeError("pos_col must be a contiguous int32 tensor")
+    for t in (pair_user, pair_item, pair_crow, pos_crow, order):
+        if t is not None and (t.dtype != torch.int64 or not t.is_contiguous()):
+            raise TypeError("the pair arrays, the row offsets and `order` must be contiguous int64 tensors")
+    if order is not None and order.numel() != n:
+        raise ValueError(f"order must name one pair per sample: {order.numel()} for {n} samples")
+    U = pos_crow.numel() - 1
+    if pair_crow.numel() != U + 1 or pair_user.numel() != pair_item.numel():
+        raise ValueError("pair_crow / pos_crow must both be [U + 1] and pair_user / pair_item equally long")
+    users = torch.empty(n, dtype=torch.int64, device=dev)
+    pos = torch.empty(n, dtype=torch.int64, device=dev)
+    neg = torch.empty((K, n), dtype=torch.int64, device=dev)
+    s64 = lambda v: ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)          # noqa: E731  (the seed as a two's-complement word)
+    _lib.check(_lib.load().mi_cf_sample_triples(
+        pair_user.data_ptr(), pair_item.data_ptr(), pair_crow.data_ptr(), pair_item.numel(), pos_crow.data_ptr(),
+        pos_col.data_ptr(), pos_col.numel(), U, num_items, CF_SAMPLE_MODES[mode], per_user_num, K, _lib.ptr(order), s64(seed),
+        s64(epoch), first, n, users.data_ptr(), pos.data_ptr(), neg.data_ptr(), _lib.err_word(dev).data_ptr(),
+        _lib.stream_ptr(dev)), "mi_cf_sample_triples")
+    return users, pos, neg
+
+
+def ndcg_weights(k: int):
+    """(weight, ideal) float64 [k] on the host: 1 / log2(j + 2) and its running sum, as ndcg_recall_at_k forms them."""
+    weight = 1.0 / torch.log2(torch.arange(2, k + 2, dtype=torch.float64))
+    return weight, torch.cumsum(weight, 0)
+
+
+def ndcg_recall_rows(pred: torch.Tensor, users: torch.Tensor, crow: torch.Tensor, col: torch.Tensor, k: int):
+    """(ndcg [n], recall [n]) float64 of the first k columns of pred int64 [n, >= k] against the truth rows of `users` in
+    the CSR (crow int64 [U + 1], col int64, rows distinct and ascending) by mi_ndcg_recall_rows."""
+    dev = _lib.require_gpu(pred, users, crow, col)
+    if pred.dim() != 2 or pred.shape[1] < k or k < 1:
+        raise ValueError(f"pred must be [n, >= k]; got {tuple(pred.shape)} for k = {k}")
+    pred, users, crow, col = _i64c(pred), _i64c(users).view(-1), _i64c(crow), _i64c(col)
+    n = pred.shape[0]
+    if users.numel() != n:
+        raise ValueError("one user per row of pred")
+    weight, ideal = (t.to(dev) for t in ndcg_weights(k))
+    ndcg = torch.empty(n, dtype=torch.float64, device=dev)
+    recall = torch.empty(n, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().mi_ndcg_recall_rows(pred.data_ptr(), pred.stride(0), users.data_ptr(), n, k, crow.data_ptr(),
+                                               col.data_ptr(), crow.numel() - 1, col.numel(), weight.data_ptr(),
+                                               ideal.data_ptr(), ndcg.data_ptr(), recall.data_ptr(),
+                                               _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)), "mi_ndcg_recall_rows")
+    return ndcg, recall

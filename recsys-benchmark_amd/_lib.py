@@ -185,6 +185,9 @@ SIGNATURES = {
     "mi_mag_csr_workspace_bytes": [_i64],
     "mi_mag_csr_count": [_p, _i64, _i64, _i32, _p, _i32, _p, _p, _p],
     "mi_mag_csr_fill": [_p, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _p, _p],
+    "mi_cf_sample_triples": [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p,
+                             _p, _p, _p],
+    "mi_ndcg_recall_rows": [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p],
     "mi_comm_available": [],
     "mi_comm_unique_id": [ctypes.c_char_p],
     "mi_comm_init": [ctypes.c_char_p, _i32, _i32, ctypes.POINTER(ctypes.c_void_p)],

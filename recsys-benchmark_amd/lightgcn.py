@@ -157,7 +157,11 @@ def get_sparsity_and_param(model: Union[LightGCN, SingleLightGCN]):
 
 def train_items_csr(graph, num_users: int, device=None):
     """CSR (crow, col) of the train interactions, from the reference dataset's `graph`
-    (user -> iterable of item ids, CFGraphDataset.get_graph()).  Built once per dataset on the host."""
+    (user -> iterable of item ids, CFGraphDataset.get_graph()).  Built once per dataset on the host — except for a
+    DeviceCFGraphDataset (or its `get_graph()`), whose stored lists already lie on the device as this CSR."""
+    resident = getattr(graph.get_graph() if hasattr(graph, "get_graph") else graph, "resident_csr", None)
+    if resident is not None and resident[0].numel() == num_users + 1:
+        return resident[0].to(device), resident[1].to(device)
     lens = [len(graph[u]) if u in graph else 0 for u in range(num_users)] if isinstance(graph, dict) else \
         [len(graph[u]) for u in range(num_users)]
     crow = torch.zeros(num_users + 1, dtype=torch.int64)
