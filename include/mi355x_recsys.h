@@ -853,7 +853,29 @@ MI_API int mi_neumf_score_all(const float *P, const float *Q, int64_t B, int64_t
  * mi_slot_fm_bwd: zero gbuf[nslot, D+4], then the row gradients of mi_gather_fm_bwd_rows written to
  *   gbuf[slot[b,f]] (first-order gradient in column D); slots >= nslot are skipped.
  * mi_unpack_rows: vals[i, 0:D] = packed[i, 0:D], lin[i] = packed[i, D] for m rows of D + 4 floats: the gradient rows
- *   received by the owner as the two contiguous value arrays of its shards' row-form gradients.  */
+ *   received by the owner as the two contiguous value arrays of its shards' row-form gradients.
+ *
+ * De-duplicated routing (one slot per DISTINCT row; a hot id costs its owner one slot however often a batch holds it):
+ * mi_route_buckets_unique: input is the batch's n rows in STABLE sorted order — rows_sorted[j] ascending over the rows
+ *   in [0, N), perm[j] the flat lookup position of the j-th (a permutation of 0..n-1; equal rows in ascending position).
+ *   mi_sort_field_rows' output qualifies (its value N for an id outside its own field counts as out of range), and so
+ *   does any generic stable sort.  With owner = row % world, local = row / world as above:
+ *     - an owner's bucket holds its distinct rows in ascending local order: the p-th has send_rows[owner*cap + p] = local,
+ *       and EVERY lookup of that row gets slot[perm[j]] = owner*cap + p; unused slots carry the owner's sink row;
+ *     - distinct rows beyond cap: their lookups get the dump slot world*cap and 1 is OR-ed into *overflow;
+ *     - rows outside [0, N) get the dump slot and MI_IDX_OUT_OF_RANGE — unless `rows` (nullable: the n rows BEFORE the
+ *       sort) shows the id inside [0, N): then the sort dropped it and has raised MI_IDX_OUT_OF_FIELD itself.
+ *   Positions are prefix counts over the sorted order, so the outputs do not depend on scheduling.
+ *   segments (int32 [2*world*cap + n], the description the backward pulls through):
+ *     segments[2*s], segments[2*s + 1] = [begin, end) of slot s's lookups in the sorted order ((0, 0) for an unused slot),
+ *     segments[2*world*cap + j]        = perm[j]: within [begin, end) the flat lookup positions ascend.
+ *   workspace: mi_route_unique_workspace_elems(n, world) int32.  n < 2^31, world <= 64.
+ * mi_slot_fm_bwd_segments: mi_slot_fm_bwd for shared slots.  gbuf[s, :] (s < nslot) = the SUM, in ascending flat lookup
+ *   position, of its lookups' gradient rows (g_emb[b,f] + g_y[b] * (S_b - e) in columns 0..D-1, g_y[b] in column D, zeros
+ *   behind); slots without lookups and row nslot (the dump row: gbuf has nslot + 1 rows) are written as zeros.  Two
+ *   launches, no float atomics, no memset: the per-lookup rows of mi_gather_fm_bwd_rows go to `workspace`
+ *   (mi_slot_fm_bwd_segments_workspace_elems(B, F, D) floats, 16-byte aligned), then every slot pulls its own.
+ *   `segments` as written by mi_route_buckets_unique with world*cap = nslot.  D = 4 * 2^k only.  */
 MI_API int64_t mi_route_workspace_elems(int64_t n, int32_t world);
 MI_API int mi_route_buckets(const int64_t *idx, const int64_t *offsets, int64_t n, int32_t F,
                             int32_t world, int64_t N, int64_t cap, int32_t *workspace,
@@ -868,6 +890,14 @@ MI_API int mi_slot_fm_fwd(const int64_t *slot, const float *buf, int64_t nrows, 
 MI_API int mi_slot_fm_bwd(const int64_t *slot, const float *emb, const float *g_y,
                           const float *g_emb, float *gbuf, float *gbias, int64_t nslot, int64_t B,
                           int32_t F, int32_t D, void *stream);
+MI_API int64_t mi_route_unique_workspace_elems(int64_t n, int32_t world);
+MI_API int mi_route_buckets_unique(const int64_t *rows_sorted, const int64_t *perm, const int64_t *rows, int64_t n,
+                                   int32_t world, int64_t N, int64_t cap, int32_t *workspace, int64_t *send_rows,
+                                   int64_t *slot, int32_t *segments, int32_t *overflow, int32_t *err, void *stream);
+MI_API int64_t mi_slot_fm_bwd_segments_workspace_elems(int64_t B, int32_t F, int32_t D);
+MI_API int mi_slot_fm_bwd_segments(const int32_t *segments, const float *emb, const float *g_y, const float *g_emb,
+                                   float *workspace, float *gbuf, float *gbias, int64_t nslot, int64_t B, int32_t F,
+                                   int32_t D, void *stream);
 
 /* ---- §8 a5 / f.2: the MLP tail as fused MFMA kernels (recsys-benchmark_amd/csrc/tail.hip) ---------------------------
  * Replaces, for (Linear, BatchNorm1d(training), ReLU, Dropout) x k + Linear(., 1) — src/models/deepfm.py:53-66,100-102

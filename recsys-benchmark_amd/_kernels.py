@@ -1825,6 +1825,124 @@ def slot_fm(buf, slot, bias):
     return SlotFM.apply(buf, slot, bias)
 
 
+
+# ---- row-sharded lookup, de-duplicated: one slot per distinct row (csrc/route.hip, csrc/gather_fm.hip) ----------------
+def route_buckets_unique(idx: torch.Tensor, offsets: Optional[torch.Tensor], world: int, num_rows: int, cap: int,
+                         overflow: torch.Tensor, slot_out: Optional[torch.Tensor] = None,
+                         segments_out: Optional[torch.Tensor] = None, send_out: Optional[torch.Tensor] = None,
+                         field_sort: bool = True):
+    """Bucketing of the DISTINCT rows = idx + offsets by owner = row % world (mi_route_buckets_unique): an owner's bucket
+    holds its distinct rows in ascending local order, every lookup of a row shares the row's slot.
+
+    Returns (send_rows int64[world*cap], slot int64[idx.shape], segments int32[2*world*cap + n]); `segments` is what
+    slot_fm_unique's backward pulls through (layout: include/mi355x_recsys.h).  The rows are sorted first: field by field
+    (mi_sort_field_rows) when `offsets` are given — they must then be the ascending field offsets, and an id outside
+    its own field goes to the dump slot and raises the out-of-field bit, as that sort has it —, generically
+    (torch.sort, stable) without offsets, beyond that sort's limits, or with field_sort=False."""
+    dev = _lib.require_gpu(idx, offsets, overflow)
+    lib = _lib.load()
+    idxc = _i64c(idx)
+    if overflow.dtype != torch.int32:
+        raise TypeError("overflow must be an int32 device word")
+    F = idxc.shape[-1] if idxc.dim() > 1 else 1
+    off = None if offsets is None else _i64c(offsets.reshape(-1))
+    if off is not None and off.numel() != F:
+        raise ValueError(f"offsets must have {F} entries")
+    n = idxc.numel()
+    S = world * cap
+    rows = idxc if off is None else idxc + off
+    err = _lib.err_word(dev).data_ptr()
+    stream = _lib.stream_ptr(dev)
+    flat = rows.reshape(-1)
+    B = n // F
+    if field_sort and off is not None and idxc.dim() == 2 and 0 < B <= 65536 and num_rows < 2**32 - 2:
+        rs, perm = torch.empty_like(flat), torch.empty_like(flat)
+        nbytes = int(lib.mi_sort_field_rows_workspace_bytes(B, F))
+        sws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        _lib.check(lib.mi_sort_field_rows(rows.data_ptr(), off.data_ptr(), num_rows, B, F, rs.data_ptr(), perm.data_ptr(),
+                                          _lib.ptr(sws), err, stream), "mi_sort_field_rows")
+    else:
+        rs, perm = torch.sort(flat, stable=True)
+    ws = torch.empty(int(lib.mi_route_unique_workspace_elems(n, world)), dtype=torch.int32, device=dev)
+
+    def _out(given, shape, dtype, what):
+        if given is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if given.numel() != int(torch.Size(shape).numel()) or given.dtype != dtype or not given.is_contiguous() or given.device != dev:
+            raise ValueError(f"{what} must be a contiguous {dtype} device tensor with {int(torch.Size(shape).numel())} entries")
+        return given
+
+    send_rows = _out(send_out, (S,), torch.int64, "send_out")
+    slot = _out(slot_out, tuple(idxc.shape), torch.int64, "slot_out")
+    segments = _out(segments_out, (2 * S + n,), torch.int32, "segments_out")
+    _lib.check(
+        lib.mi_route_buckets_unique(rs.data_ptr(), perm.data_ptr(), flat.data_ptr(), n, world, num_rows, cap, ws.data_ptr(),
+                                    send_rows.data_ptr(), slot.data_ptr(), segments.data_ptr(), overflow.data_ptr(), err,
+                                    stream),
+        "mi_route_buckets_unique",
+    )
+    return send_rows, slot, segments
+
+
+class SlotFMUnique(torch.autograd.Function):
+    """SlotFM where lookups may SHARE slots (route_buckets_unique): the forward is the same kernel (repeated slots are
+    repeated reads); the backward writes to every slot the sum of its lookups' gradient rows, in ascending lookup order
+    and without float atomics (mi_slot_fm_bwd_segments).  `segments` must be the description routing made for `slot`."""
+
+    @staticmethod
+    def forward(ctx, buf, slot, bias, segments):
+        dev = _lib.require_gpu(buf, slot, bias, segments)
+        lib = _lib.load()
+        buf = _f32c(buf)
+        slot = _i64c(slot)
+        B, F = slot.shape
+        D = buf.shape[1] - 4
+        nslot = buf.shape[0] - 1
+        if segments.dtype != torch.int32 or not segments.is_contiguous() or segments.numel() != 2 * nslot + B * F:
+            raise ValueError(f"segments must be a contiguous int32 tensor of 2 * {nslot} + {B * F} entries")
+        emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
+        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
+        _lib.check(
+            lib.mi_slot_fm_fwd(slot.data_ptr(), buf.data_ptr(), buf.shape[0], _lib.ptr(bias), emb.data_ptr(),
+                               yfm.data_ptr(), B, F, D, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
+            "mi_slot_fm_fwd",
+        )
+        ctx.save_for_backward(emb, segments)
+        ctx.meta = (B, F, D, buf.shape[0], bias is not None)
+        ctx.set_materialize_grads(False)
+        return emb, yfm
+
+    @staticmethod
+    def backward(ctx, g_emb, g_y):
+        emb, segments = ctx.saved_tensors
+        B, F, D, rows, has_bias = ctx.meta
+        dev = emb.device
+        lib = _lib.load()
+        if g_y is None:
+            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
+        g_y = _f32c(g_y)
+        g_emb = None if g_emb is None else _f32c(g_emb)
+        gbuf = None
+        want_gb = has_bias and ctx.needs_input_grad[2]
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if want_gb else None
+        if ctx.needs_input_grad[0]:
+            gbuf = torch.empty((rows, D + 4), dtype=torch.float32, device=dev)      # every row is written by the kernel
+            ws = torch.empty(int(lib.mi_slot_fm_bwd_segments_workspace_elems(B, F, D)), dtype=torch.float32, device=dev)
+            _lib.check(
+                lib.mi_slot_fm_bwd_segments(segments.data_ptr(), emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb),
+                                            ws.data_ptr(), gbuf.data_ptr(), _lib.ptr(gb), rows - 1, B, F, D,
+                                            _lib.stream_ptr(dev)),
+                "mi_slot_fm_bwd_segments",
+            )
+        elif want_gb:
+            gb = g_y.sum().view(1)
+        return gbuf, None, gb, None
+
+
+def slot_fm_unique(buf, slot, bias, segments):
+    return SlotFMUnique.apply(buf, slot, bias, segments)
+
+
 # ---- OptEmbed supernet for the CF tables (csrc/optembed_cf.hip) -------------------------------------------------------
 _cf_seeds: Dict[int, list] = {}
 

@@ -127,6 +127,10 @@ SIGNATURES = {
     "mi_gather_pack_rows": [_p, _p, _p, _p, _i64, _i32, _i64, _p, _p],
     "mi_slot_fm_fwd": [_p, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _p, _p],
     "mi_slot_fm_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p],
+    "mi_route_unique_workspace_elems": [_i64, _i32],
+    "mi_route_buckets_unique": [_p, _p, _p, _i64, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p],
+    "mi_slot_fm_bwd_segments_workspace_elems": [_i64, _i32, _i32],
+    "mi_slot_fm_bwd_segments": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p],
     "mi_prof_enable": [_i32],
     "mi_col_act_fwd": [_p, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, _p],
     "mi_col_act_bwd": [_p, _p, _i32, _p, _p, _p, _i32, _p, _p, _i32, _i32, _p],
@@ -204,7 +208,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_sort_field_rows_workspace_bytes": ctypes.c_int64, "mi_tail_part_elems": ctypes.c_int64,
              "mi_dual_gather_bwd_rows_workspace_elems": ctypes.c_int64,
              "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64,
-             "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64}
+             "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64,
+             "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

@@ -358,6 +358,138 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD(
   }
 }
 
+// ------------------------------------------- backward, summed per slot ----
+// The de-duplicated sharded lookup (route.hip, mi_route_buckets_unique) lets many lookups share one slot, so the slot
+// backward cannot store: every slot needs the SUM of its lookups' gradient rows.  Store pass + per-destination sum pass
+// (no float atomics): k_gather_fm_bwd_rows<SLOT=false> writes the per-lookup rows, then this kernel PULLS — slot s adds
+// rows order[begin_s .. end_s) in that order, which routing made the ascending flat lookup index.
+//   phase 1: LPR lanes per slot, for the slots of up to kLongSeg lookups (nearly all of them);
+//   phase 2: a whole wave per LONG slot (a field with fewer values than B / kLongSeg has only long ones; so has a hot
+//            value).  Wave w takes the slots = w modulo the number of waves, so the neighbouring long slots of a small
+//            field go to different waves.  Per round the wave fetches RS*U rows at once into its LDS slab and one lane
+//            per column adds them in order: the chain of adds stays serial, the loads do not.  Rows past the end are
+//            staged as zeros (x + 0 = x), which keeps the adding loop's trip count fixed.
+constexpr int kLongSeg = 32;
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restrict__ seg,
+                                                        const float *__restrict__ gvals,
+                                                        const float *__restrict__ g1vals,
+                                                        float *__restrict__ gbuf, int64_t nslot, int64_t n) {
+  constexpr int RS = kWave / LPR;
+  constexpr int D = LPR * 4;
+  constexpr int LD = D + 4;
+  constexpr int U = LPR >= 4 ? 8 : 4;            // row fetches in flight per lane in phase 2
+  constexpr int ROWS = RS * U;                   // rows per round
+  constexpr int NC = (LD + kWave - 1) / kWave;   // columns per lane when one lane adds one column
+  __shared__ float slab[kWavesPerBlock][ROWS * LD];
+  const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+  const int q = lane % LPR, r = lane / LPR;
+  const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + wib;
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  const int32_t *__restrict__ order = seg + 2 * nslot;
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  float *my = slab[wib];
+  // ---- phase 1 (+1: the dump row nslot is written as zeros, nobody's gradient)
+  for (int64_t tile = wave0; tile * RS < nslot + 1; tile += nwaves) {
+    const int64_t s = tile * RS + r;
+    int beg = 0, end = 0;
+    if (s < nslot) {
+      beg = seg[2 * s];
+      end = seg[2 * s + 1];
+      if (beg < 0 || end > n || end < beg) beg = end = 0;
+    }
+    if (s > nslot || end - beg > kLongSeg) continue;
+    float4 acc = z;
+    float a1 = 0.f;
+    for (int t = beg; t < end; t += 4) {
+      int i[4];
+      float4 v[4];
+      float l[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) i[u] = t + u < end ? order[t + u] : -1;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool ok = (uint64_t)(uint32_t)i[u] < (uint64_t)n;
+        v[u] = ok ? ld4(gvals + (int64_t)i[u] * D + q * 4) : z;
+        l[u] = (ok && q == 0) ? g1vals[i[u]] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (t + u < end) {
+          acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+          a1 += l[u];
+        }
+      }
+    }
+    st4(gbuf + s * LD + q * 4, acc);
+    if (q == 0) st4(gbuf + s * LD + D, make_float4(a1, 0.f, 0.f, 0.f));
+  }
+  // ---- phase 2: lane k looks at slot base + k * nwaves + wave0, the wave then takes its long ones in turn
+  for (int64_t base = 0; base < nslot; base += (int64_t)kWave * nwaves) {
+    const int64_t sl = base + (int64_t)lane * nwaves + wave0;
+    int lb = 0, le = 0;
+    if (sl < nslot) {
+      lb = seg[2 * sl];
+      le = seg[2 * sl + 1];
+      if (lb < 0 || le > n || le < lb) lb = le = 0;
+    }
+    unsigned long long m = __ballot(le - lb > kLongSeg);
+    while (m) {
+      const int src = __ffsll((long long)m) - 1;
+      m &= m - 1;
+      const int b0 = __shfl(lb, src), e0 = __shfl(le, src);
+      const int64_t s0 = base + (int64_t)src * nwaves + wave0;
+      float c[NC];
+#pragma unroll
+      for (int k = 0; k < NC; ++k) c[k] = 0.f;
+      int inext[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int t = b0 + u * RS + r;
+        inext[u] = t < e0 ? order[t] : -1;
+      }
+      for (int t0 = b0; t0 < e0; t0 += ROWS) {
+        float4 v[U];
+        float l[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const bool ok = (uint64_t)(uint32_t)inext[u] < (uint64_t)n;
+          v[u] = ok ? ld4(gvals + (int64_t)inext[u] * D + q * 4) : z;
+          l[u] = (ok && q == 0) ? g1vals[inext[u]] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {             // the next round's indices travel while this round is added up
+          const int t = t0 + ROWS + u * RS + r;
+          inext[u] = t < e0 ? order[t] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          st4(my + (u * RS + r) * LD + q * 4, v[u]);
+          if (q == 0) st4(my + (u * RS + r) * LD + D, make_float4(l[u], 0.f, 0.f, 0.f));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          const int col = lane + k * kWave;
+          if (col < LD) {
+#pragma unroll 16
+            for (int j = 0; j < ROWS; ++j) c[k] += my[j * LD + col];
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        const int col = lane + k * kWave;
+        if (col < LD) gbuf[s0 * LD + col] = c[k];
+      }
+    }
+  }
+}
+
 // --------------------------------------------------- backward, dense form ----
 // Same gradient rows, scatter-added into gW / gw1.  The wave's RS x D tile of a
 // step (256 floats = the lanes' float4 fragments back to back) goes through a
@@ -847,6 +979,38 @@ int mi_slot_fm_bwd(const int64_t *slot, const float *emb, const float *g_y, cons
   MI_LAUNCH("slot_fm_bwd", (k_gather_fm_bwd_rows<LPR, NIT, true>), grid, kBlock, stream, emb,  \
             g_y, g_emb, gbuf, (float *)nullptr, B, F, slot, nslot, gbias)
   MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+  return launch_status();
+}
+
+int64_t mi_slot_fm_bwd_segments_workspace_elems(int64_t B, int32_t F, int32_t D) {
+  if (B < 0 || F < 0 || D <= 0) return 0;
+  return B * F * ((int64_t)D + 1) + 3;           // per-lookup rows [n, D], first-order values [n], (+3: 16-byte slack)
+}
+
+int mi_slot_fm_bwd_segments(const int32_t *segments, const float *emb, const float *g_y, const float *g_emb,
+                            float *workspace, float *gbuf, float *gbias, int64_t nslot, int64_t B, int32_t F,
+                            int32_t D, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || nslot < 0) return MI_ERR_INVALID_ARG;
+  if (!gbuf || (nslot > 0 && !segments)) return MI_ERR_INVALID_ARG;
+  const int64_t n = B * F;
+  if (n >= (1ll << 31)) return MI_ERR_UNSUPPORTED;
+  if (n > 0 && (!emb || !g_y || !workspace || !segments)) return MI_ERR_INVALID_ARG;
+  if (!vec_ok(D) || !aligned16(gbuf) || !aligned16(workspace) || (emb && !aligned16(emb)) || (g_emb && !aligned16(g_emb)))
+    return MI_ERR_UNSUPPORTED;
+  float *gvals = workspace, *g1vals = workspace + n * D;
+  if (n > 0) {
+    const int rc = mi_gather_fm_bwd_rows(emb, g_y, g_emb, gvals, g1vals, gbias, B, F, D, stream);
+    if (rc != MI_OK) return rc;
+  } else if (gbias && hipMemsetAsync(gbias, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) {
+    return MI_ERR_LAUNCH;
+  }
+  const int lpr = D / 4;
+  const int64_t rs = kWave / lpr;
+  const int grid = grid_for_waves((nslot + 1 + rs - 1) / rs);
+#define CALL(LPR) \
+  MI_LAUNCH("slot_fm_bwd_segments", (k_segment_sum<LPR>), grid, kBlock, stream, segments, gvals, g1vals, gbuf, nslot, n)
+  MI_DISPATCH_LPR(lpr, CALL)
 #undef CALL
   return launch_status();
 }

@@ -16,6 +16,9 @@
 // unused slots carry the owner's SINK row (one extra all-zero-gradient row at the end of every
 // shard), lookups that do not fit or are out of range go to the DUMP slot world*cap (a zero row
 // of the received buffer) and raise the overflow / index-error words.
+// De-duplicated form (mi_route_buckets_unique, ShardedDeepFM(dedup=True)): step 1 buckets the batch's DISTINCT rows and
+// every lookup of a row shares its slot, so hot ids cannot overflow a bucket; the backward then SUMS per slot
+// (mi_slot_fm_bwd_segments in gather_fm.hip) through the segment description step 1 leaves behind.
 #include "common.hpp"
 
 namespace {
@@ -182,6 +185,142 @@ __global__ __launch_bounds__(kBlock) void k_route_assign(
   if (bad && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
 }
 
+// ---- de-duplicated routing (mi_route_buckets_unique) ----------------------------------------------------------------
+// One slot per DISTINCT row instead of one per lookup: a hot id costs its owner one slot however often the batch holds
+// it.  The input is the batch's rows in stable sorted order (rows_sorted[j], perm[j] = flat lookup position), so equal
+// rows are neighbours, a row's first lookup (its run HEAD) marks a new distinct row, and the heads of one owner come in
+// ascending local order.  The count / scan / assign structure above then ranks HEADS per owner; every lookup of the run
+// takes "heads of my owner up to and including me, minus one", which is its head's position, because no other head lies
+// inside a run.  Nothing depends on scheduling: positions are prefix counts over the sorted order.
+__device__ __forceinline__ void classify_sorted(const int64_t *__restrict__ rs, int64_t j, int64_t n, int world,
+                                                int64_t N, int &own, int64_t &loc, bool &head, bool &valid) {
+  valid = j < n;
+  own = -1;
+  loc = 0;
+  head = false;
+  if (valid) {
+    const int64_t row = rs[j];
+    if ((uint64_t)row < (uint64_t)N) {
+      loc = row / world;
+      own = (int)(row - loc * world);
+      head = j == 0 || rs[j - 1] != row;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_uniq_count(const int64_t *__restrict__ rs, int64_t n, int world, int64_t N,
+                                                       int32_t *__restrict__ counts) {
+  __shared__ int c[kMaxWorld];
+  if (threadIdx.x < kMaxWorld) c[threadIdx.x] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < kIt; ++k) {
+    const int64_t j = (int64_t)blockIdx.x * kChunk + k * kBlock + threadIdx.x;
+    int own;
+    int64_t loc;
+    bool head, valid;
+    classify_sorted(rs, j, n, world, N, own, loc, head, valid);
+    for (int w = 0; w < world; ++w) {
+      const unsigned long long m = __ballot(head && own == w);
+      if (lane == 0 && m) atomicAdd(&c[w], __popcll(m));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < world) counts[(int64_t)blockIdx.x * world + threadIdx.x] = c[threadIdx.x];
+}
+
+// segments: int32 [2 * world*cap + n] — (begin, end) of every slot's run in the sorted order, then the sorted order's
+// flat lookup positions (the header documents the layout)
+template <bool SELF_SCAN>
+__global__ __launch_bounds__(kBlock) void k_uniq_assign(
+    const int64_t *__restrict__ rs, const int64_t *__restrict__ perm, const int64_t *__restrict__ rows, int64_t n,
+    int world, int64_t N, int64_t cap, const int32_t *__restrict__ base, const int32_t *__restrict__ total,
+    int64_t *__restrict__ send_rows, int64_t *__restrict__ slot, int32_t *__restrict__ segments, int32_t *overflow,
+    int32_t *err, const int32_t *__restrict__ counts) {
+  __shared__ int cnt[kIt][kWavesPerBlock][kMaxWorld];
+  __shared__ int sbase[kMaxWorld], stotal[kMaxWorld];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if constexpr (SELF_SCAN) {
+    const int G = gridDim.x;
+    for (int w = wv; w < world; w += kWavesPerBlock) {
+      int b = 0, t = 0;
+      for (int g = lane; g < G; g += kWave) {
+        const int v = counts[(int64_t)g * world + w];
+        t += v;
+        b += g < (int)blockIdx.x ? v : 0;
+      }
+#pragma unroll
+      for (int off = 32; off; off >>= 1) {
+        b += __shfl_xor(b, off);
+        t += __shfl_xor(t, off);
+      }
+      if (lane == 0) { sbase[w] = b; stotal[w] = t; }
+    }
+  }
+  const unsigned long long upto = ~0ull >> (63 - lane);      // this lane and the ones below it
+  int own[kIt], rank[kIt];
+  int64_t loc[kIt];
+  bool head[kIt], valid[kIt];
+#pragma unroll
+  for (int k = 0; k < kIt; ++k) {
+    const int64_t j = (int64_t)blockIdx.x * kChunk + k * kBlock + threadIdx.x;
+    classify_sorted(rs, j, n, world, N, own[k], loc[k], head[k], valid[k]);
+    rank[k] = 0;
+    for (int w = 0; w < world; ++w) {
+      const unsigned long long m = __ballot(head[k] && own[k] == w);
+      if (own[k] == w) rank[k] = __popcll(m & upto);          // heads of my owner in this wave step, me included
+      if (lane == 0) cnt[k][wv][w] = __popcll(m);
+    }
+  }
+  __syncthreads();
+  const int64_t S = (int64_t)world * cap;
+  int32_t *__restrict__ order = segments + 2 * S;
+  int over = 0, bad = 0;
+#pragma unroll
+  for (int k = 0; k < kIt; ++k) {
+    if (!valid[k]) continue;
+    const int64_t j = (int64_t)blockIdx.x * kChunk + k * kBlock + threadIdx.x;
+    const int64_t i = perm[j];
+    const bool placed = (uint64_t)i < (uint64_t)n;             // (a permutation by contract; never write outside slot[n])
+    order[j] = placed ? (int32_t)i : 0;
+    int64_t s = S;
+    if (own[k] >= 0) {
+      int64_t pos = (SELF_SCAN ? sbase[own[k]] : base[(int64_t)blockIdx.x * world + own[k]]) + rank[k] - 1;
+      for (int kk = 0; kk <= k; ++kk) {
+        const int wend = kk < k ? kWavesPerBlock : wv;
+        for (int w2 = 0; w2 < wend; ++w2) pos += cnt[kk][w2][own[k]];
+      }
+      if (pos >= 0 && pos < cap) {
+        s = own[k] * cap + pos;
+        if (head[k]) {
+          send_rows[s] = loc[k];
+          segments[2 * s] = (int32_t)j;
+        }
+        if (j + 1 == n || rs[j + 1] != rs[j]) segments[2 * s + 1] = (int32_t)(j + 1);
+      } else if (head[k]) {
+        over = 1;
+      }
+    } else if (!rows || !placed || (uint64_t)rows[i] >= (uint64_t)N) {
+      bad = 1;       // (in [0, N) before the sort: the field sort dropped it and raised MI_IDX_OUT_OF_FIELD itself)
+    }
+    if (placed) slot[i] = s; else bad = 1;
+  }
+  // unused slots of every bucket point at the owner's sink row and own no lookups
+  for (int w = 0; w < world; ++w) {
+    const int64_t tw = SELF_SCAN ? stotal[w] : total[w];
+    const int64_t used = tw < cap ? tw : cap;
+    const int64_t sink = (N - w + world - 1) / world;
+    for (int64_t p = used + (int64_t)blockIdx.x * kBlock + threadIdx.x; p < cap; p += (int64_t)gridDim.x * kBlock) {
+      send_rows[w * cap + p] = sink;
+      segments[2 * (w * cap + p)] = 0;
+      segments[2 * (w * cap + p) + 1] = 0;
+    }
+  }
+  if (over && overflow) atomicOr(overflow, 1);
+  if (bad && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
+}
+
 // out[i, 0:D] = W[rows[i], :], out[i, D:D+4] = (w1[rows[i]], 0, 0, 0); rows of ldo = D + 4 floats
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void k_gather_pack(
@@ -284,6 +423,30 @@ int mi_route_buckets(const int64_t *idx, const int64_t *offsets, int64_t n, int3
   MI_LAUNCH("route_scan", k_route_scan, 1, kBlock, stream, counts, G, world, base, total);
   MI_LAUNCH("route_assign", k_route_assign<false>, G, kBlock, stream, idx, offsets, F, n, world, N, cap,
             base, total, send_rows, slot, overflow, err, counts);
+  return launch_status();
+}
+
+int64_t mi_route_unique_workspace_elems(int64_t n, int32_t world) { return mi_route_workspace_elems(n, world); }
+
+int mi_route_buckets_unique(const int64_t *rows_sorted, const int64_t *perm, const int64_t *rows, int64_t n,
+                            int32_t world, int64_t N, int64_t cap, int32_t *workspace, int64_t *send_rows,
+                            int64_t *slot, int32_t *segments, int32_t *overflow, int32_t *err, void *stream) {
+  if (n < 0 || world < 1 || N < 0 || cap < 0) return MI_ERR_INVALID_ARG;
+  if (world > kMaxWorld || n >= (1ll << 31) || world * cap >= (1ll << 40)) return MI_ERR_UNSUPPORTED;
+  if (!workspace || (world * cap > 0 && (!send_rows || !segments)) || (n > 0 && (!rows_sorted || !perm || !slot || !segments)))
+    return MI_ERR_INVALID_ARG;
+  const int64_t G64 = route_groups(n) > 0 ? route_groups(n) : 1;
+  const int G = (int)G64;
+  int32_t *counts = workspace, *base = workspace + G64 * world, *total = base + G64 * world;
+  MI_LAUNCH("route_unique_count", k_uniq_count, G, kBlock, stream, rows_sorted, n, world, N, counts);
+  if (G <= kSelfScanGroups) {
+    MI_LAUNCH("route_unique_assign", k_uniq_assign<true>, G, kBlock, stream, rows_sorted, perm, rows, n, world, N, cap, base,
+              total, send_rows, slot, segments, overflow, err, counts);
+    return launch_status();
+  }
+  MI_LAUNCH("route_scan", k_route_scan, 1, kBlock, stream, counts, G, world, base, total);
+  MI_LAUNCH("route_unique_assign", k_uniq_assign<false>, G, kBlock, stream, rows_sorted, perm, rows, n, world, N, cap, base,
+            total, send_rows, slot, segments, overflow, err, counts);
   return launch_status();
 }
 

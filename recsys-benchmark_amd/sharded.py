@@ -26,6 +26,9 @@ and has no distributed code; this is the MI355X-native extension of the same Dee
     and the compute between the collectives replays as hipGraphs (`enable_graphs`).  A bucket that
     overflows (pathological skew) drops the excess lookups to zeros and raises the sticky flag
     `check_overflow()` reports; `bucket_slack=world` makes overflow impossible (cap = n).
+  * `dedup=True` (opt-in): one slot per DISTINCT row instead of one per lookup — hot ids cannot overflow a bucket, the
+    buckets shrink (`dedup_bucket_capacity`), and the FM/gather backward SUMS the gradient rows of the lookups that share
+    a slot before they are shipped.
 
 The three device steps come from `ops` (default: the HIP library).  The world-size-2 gloo tests
 run on CPU, where the library cannot, and inject torch restatements of the same three steps so
@@ -48,6 +51,8 @@ class HipOps:
     gather_pack_rows = staticmethod(_kernels.gather_pack_rows)
     unpack_rows = staticmethod(_kernels.unpack_rows)
     slot_fm = staticmethod(_kernels.slot_fm)
+    route_buckets_unique = staticmethod(_kernels.route_buckets_unique)
+    slot_fm_unique = staticmethod(_kernels.slot_fm_unique)
 
     @staticmethod
     def tail(deep_branch: nn.Sequential, x: torch.Tensor, y_fm: torch.Tensor, labels=None, loss_seed=None) -> torch.Tensor:
@@ -310,8 +315,33 @@ def field_bucket_capacity(field_dims: List[int], batch: int, world: int, slack: 
     return min(n, int(peak * slack + 6.0 * (peak ** 0.5)) + 64)
 
 
+def expected_peak_distinct(field_dims: List[int], batch: int, world: int) -> float:
+    """Largest expected number of DISTINCT rows one owner is asked for by a batch of `batch` samples with ids uniform within
+    every field: a row of a field with c values is drawn at least once with probability 1 - (1 - 1/c)^batch, summed over the
+    rows the owner holds of every field.  Uniform ids are the worst case for distinct rows (skew only repeats rows), which
+    is why this bound, unlike expected_peak_load, survives hot values."""
+    load = [0.0] * world
+    off = 0
+    for c in field_dims:
+        base, extra = divmod(c, world)
+        hit = 1.0 - (1.0 - 1.0 / c) ** batch
+        for o in range(world):
+            rows = base + (1 if ((o - off) % world) < extra else 0)
+            load[o] += rows * hit
+        off += c
+    return max(load)
+
+
+def dedup_bucket_capacity(field_dims: List[int], batch: int, world: int, slack: float) -> int:
+    """Slots per peer bucket when every distinct row travels once (ShardedDeepFM(dedup=True)): expected_peak_distinct with
+    `slack` headroom + six standard deviations, never above field_bucket_capacity."""
+    peak = expected_peak_distinct(field_dims, batch, world)
+    return min(field_bucket_capacity(field_dims, batch, world, slack), int(peak * slack + 6.0 * (peak ** 0.5)) + 64)
+
+
 class _Exchange(torch.autograd.Function):
-    """x[B,F] raw ids -> (packed rows received [world*cap + 1, D+4], slot[B,F]).
+    """x[B,F] raw ids -> (packed rows received [world*cap + 1, D+4], slot[B,F], segments or None).
+    (segments: the de-duplicated routing's description of which lookups share a slot, model.dedup only.)
 
     Backward ships the gradient of the received buffer to the owners and returns it as
     uncoalesced COO gradients of the LOCAL shards (what nn.Embedding(sparse=True) gives a local
@@ -326,8 +356,13 @@ class _Exchange(torch.autograd.Function):
         S = world * cap
         static = model.__dict__.get("_static_io")
         use_static = static is not None and static[0].shape[0] == S + 1 and tuple(static[1].shape) == tuple(x.shape)
-        send_rows, slot = ops.route_buckets(x, model.offsets, world, model.num_rows, cap, model.bucket_overflow,
-                                            slot_out=static[1] if use_static else None)
+        segments = None
+        if model.dedup:
+            send_rows, slot, segments = ops.route_buckets_unique(x, model.offsets, world, model.num_rows, cap,
+                                                                 model.bucket_overflow)
+        else:
+            send_rows, slot = ops.route_buckets(x, model.offsets, world, model.num_rows, cap, model.bucket_overflow,
+                                                slot_out=static[1] if use_static else None)
         local_rows = torch.empty_like(send_rows)
         _all_to_all(model, local_rows, send_rows)
         packed = ops.gather_pack_rows(local_rows, W_local, w1_local)              # [S, D+4]
@@ -340,10 +375,12 @@ class _Exchange(torch.autograd.Function):
         ctx.model = model
         ctx.local_rows, ctx.meta = local_rows, (S, D, world, group, tuple(W_local.shape), tuple(w1_local.shape))
         ctx.mark_non_differentiable(slot)
-        return recv, slot
+        if segments is not None:
+            ctx.mark_non_differentiable(segments)
+        return recv, slot, segments
 
     @staticmethod
-    def backward(ctx, g_recv, _g_slot):
+    def backward(ctx, g_recv, _g_slot, _g_segments=None):
         S, D, world, group, Wshape, w1shape = ctx.meta
         g_owner = g_recv.new_empty((S, D + 4))
         _all_to_all(ctx.model, g_owner, g_recv[:S].contiguous())
@@ -377,9 +414,14 @@ class ShardedDeepFM(nn.Module):
     """
 
     def __init__(self, field_dims: List[int], num_factor: int, hidden_sizes: List[int], p_dropout: float = 0.1,
-                 use_batchnorm=False, device=None, process_group=None, ops=None, bucket_slack: float = 1.25):
+                 use_batchnorm=False, device=None, process_group=None, ops=None, bucket_slack: float = 1.25,
+                 dedup: bool = False):
+        """dedup=True: every DISTINCT row travels once per rank and step (mi_route_buckets_unique): hot ids cost one slot,
+        the buckets — and with them all three all-to-alls — shrink to dedup_bucket_capacity, and the slot backward sums
+        the gradient rows of the lookups that share a slot, in a fixed order and without atomics."""
         super().__init__()
         self.ops = ops or HipOps
+        self.dedup = bool(dedup)
         self.bucket_slack = bucket_slack
         self.field_dims = list(field_dims)
         self.group = process_group
@@ -461,6 +503,8 @@ class ShardedDeepFM(nn.Module):
 
     def capacity(self, batch: int) -> int:
         """Slots per peer bucket for a batch of `batch` samples (every rank computes the same number)."""
+        if self.dedup:
+            return dedup_bucket_capacity(self.field_dims, batch, self.world, self.bucket_slack)
         return field_bucket_capacity(self.field_dims, batch, self.world, self.bucket_slack)
 
     def _collective_flags(self) -> List[int]:
@@ -481,6 +525,11 @@ class ShardedDeepFM(nn.Module):
         """Synchronise; raise ON EVERY RANK if a fixed-capacity bucket overflowed on any rank since the last check."""
         if self._collective_flags()[0]:
             self.bucket_overflow.zero_()
+            if self.dedup:
+                raise RuntimeError("sharded lookup: a peer bucket overflowed its fixed capacity on some rank although every "
+                                   "distinct row is sent once (dedup=True): the batch asks one owner for more distinct rows "
+                                   "than uniform ids would, e.g. ids concentrated on rows congruent modulo the world size; "
+                                   "raise bucket_slack (bucket_slack=world can never overflow)")
             raise RuntimeError("sharded lookup: a peer bucket overflowed its fixed capacity on some rank (extreme id skew); "
                                "raise bucket_slack (bucket_slack=world can never overflow)")
 
@@ -505,14 +554,21 @@ class ShardedDeepFM(nn.Module):
         self.fc_shard[n].zero_()
 
     # ---- the compute between the collectives ------------------------------------------------
-    def _local_compute(self, recv, slot, labels=None, loss_seed=None):
+    def _local_compute(self, recv, slot, labels=None, loss_seed=None, segments=None):
         """received packed rows + slots -> logits [B]: slot gather, FM, first-order term, MLP tail.
         labels / loss_seed (the graphed step): the targets and the scalar its backward is seeded with (1 / world) — the
-        tail's head launch then evaluates the BCE criterion and the head's backward as well (mlp.run_tail)."""
-        fused = self._fused_local(recv, slot, labels, loss_seed)
-        if fused is not None:
-            return fused
-        emb, y_fm = self.ops.slot_fm(recv, slot, self._bias)
+        tail's head launch then evaluates the BCE criterion and the head's backward as well (mlp.run_tail).
+        segments (dedup): lookups share slots, so the two-node path with the summing slot backward runs — the fused tail's
+        FM epilogue STORES gradient rows, one lookup per slot."""
+        if self.dedup:
+            if segments is None:
+                raise ValueError("dedup=True: the local compute needs the routing's segment description")
+            emb, y_fm = self.ops.slot_fm_unique(recv, slot, self._bias, segments)
+        else:
+            fused = self._fused_local(recv, slot, labels, loss_seed)
+            if fused is not None:
+                return fused
+            emb, y_fm = self.ops.slot_fm(recv, slot, self._bias)
         if labels is None:
             return self.ops.tail(self._deep_branch, emb.reshape(slot.shape[0], -1), y_fm)
         return self.ops.tail(self._deep_branch, emb.reshape(slot.shape[0], -1), y_fm, labels, loss_seed)
@@ -540,6 +596,10 @@ class ShardedDeepFM(nn.Module):
         recording them hung on this stack — so a step is: routing + two all-to-alls, ONE graph replay
         for gather+FM+MLP forward, one for their backward, the gradient all-to-all + all-reduce.
         The exchange writes straight into the graphs' static inputs (no staging copy)."""
+        if self.dedup:
+            raise NotImplementedError("enable_graphs() is not available with dedup=True (its graphed callable takes the slot "
+                                      "array alone, not the segment description the summing backward needs); use "
+                                      "make_graphed_step(), which keeps both in static buffers")
         F, D = self.offsets.shape[1], self.embedding_shard.shape[1]
         dev = self.embedding_shard.device
         S = self.world * self.capacity(batch_size)
@@ -589,6 +649,14 @@ class ShardedDeepFM(nn.Module):
         dense = self.dense_parameters()
         recv = torch.zeros(S + 1, D + 4, device=dev).requires_grad_(True)
         slot = (torch.arange(batch_size * F, device=dev) % max(S, 1)).view(batch_size, F)
+        segments = None
+        if self.dedup:
+            # static (slot, segments) pair that routing refreshes every step; warm-up and capture run on a CONSISTENT pair:
+            # a dummy batch (id 0 of every field) routed into the two buffers, its overflow word thrown away
+            segments = torch.zeros(2 * S + batch_size * F, dtype=torch.int32, device=dev)
+            self.ops.route_buckets_unique(torch.zeros(batch_size, F, dtype=torch.int64, device=dev), self.offsets, world,
+                                          self.num_rows, cap, torch.zeros(1, dtype=torch.int32, device=dev),
+                                          slot_out=slot, segments_out=segments)
         ys = static_labels if static_labels is not None else torch.zeros(batch_size, device=dev)
         # d(global-batch mean loss)/d(this rank's mean loss) = 1/world: seeded into the backward so that the table
         # gradients arrive already averaged and the dense ones only need a SUM all-reduce
@@ -598,7 +666,8 @@ class ShardedDeepFM(nn.Module):
         in_head = isinstance(criterion, _losses.BCEWithLogitsLoss) and self.ops is HipOps      # (the gloo tests' CPU ops take no labels)
 
         def local():
-            logits = self._local_compute(recv, slot, ys, seed_grad) if in_head else self._local_compute(recv, slot)
+            logits = (self._local_compute(recv, slot, ys, seed_grad, segments=segments) if in_head
+                      else self._local_compute(recv, slot, segments=segments))
             loss = criterion(logits, ys)
             grads = torch.autograd.grad(loss, [recv] + dense, grad_outputs=seed_grad)
             return loss, grads[0], torch.cat([g.reshape(-1) for g in grads[1:]])
@@ -633,10 +702,14 @@ class ShardedDeepFM(nn.Module):
                 raise ValueError(f"this step was captured for x of shape {(batch_size, F)}, got {tuple(x.shape)}")
             if y is not None and y.data_ptr() != ys.data_ptr():
                 ys.copy_(y)
-            send_rows, _ = self.ops.route_buckets(x, self.offsets, world, self.num_rows, cap, self.bucket_overflow,
-                                                  slot_out=slot)
+            if self.dedup:
+                send_rows = self.ops.route_buckets_unique(x, self.offsets, world, self.num_rows, cap, self.bucket_overflow,
+                                                          slot_out=slot, segments_out=segments)[0]
+            else:
+                send_rows, _ = self.ops.route_buckets(x, self.offsets, world, self.num_rows, cap, self.bucket_overflow,
+                                                      slot_out=slot)
             local_rows = torch.empty_like(send_rows)
-            if mark: mark("route (2 launches)")
+            if mark: mark("route (row add, sort, 2 launches)" if self.dedup else "route (2 launches)")
             _all_to_all(self, local_rows, send_rows)
             if mark: mark("all-to-all #1: row ids")
             packed = self.ops.gather_pack_rows(local_rows, self.embedding_shard, self.fc_shard)
@@ -671,8 +744,8 @@ class ShardedDeepFM(nn.Module):
 
     def forward(self, x):
         """x: int [B_local, F] raw per-field ids -> logits [B_local]."""
-        recv, slot = _Exchange.apply(x, self.embedding_shard, self.fc_shard, self)
+        recv, slot, segments = _Exchange.apply(x, self.embedding_shard, self.fc_shard, self)
         graphed = self.__dict__.get("_graphed_local")
         if graphed is not None and x.shape[0] == self._graphed_batch and self.training:
             return graphed(recv, slot)
-        return self._local_compute(recv, slot)
+        return self._local_compute(recv, slot, segments=segments)

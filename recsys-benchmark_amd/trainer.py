@@ -13,6 +13,7 @@ kernels.
 and read back at the logging steps only (the reference calls `.item()` every batch).
 """
 import datetime
+import gc
 import logging
 import inspect
 import warnings
@@ -46,19 +47,30 @@ class _capture(torch.cuda.graph):
         from . import sharded
 
         sharded.note_capture(+1)
+        # torch.cuda.graph no longer collects garbage before a capture.  A dead reference cycle that owns a graph, a stream
+        # or an event, collected by a pass that happens to run INSIDE the capture, destroys it there — not allowed while a
+        # global-mode capture is open (the runtime aborted the process).  Collect now; no pass until the capture has ended.
+        self._gc_was_enabled = gc.isenabled()
+        gc.collect()
+        gc.disable()
         try:
             return super().__enter__()
         except BaseException:
-            sharded.note_capture(-1)
+            self._leave()
             raise
 
-    def __exit__(self, *exc):
+    def _leave(self):
         from . import sharded
 
+        if self._gc_was_enabled:
+            gc.enable()
+        sharded.note_capture(-1)
+
+    def __exit__(self, *exc):
         try:
             return super().__exit__(*exc)
         finally:
-            sharded.note_capture(-1)
+            self._leave()
 
 
 def _capturable(optimizers) -> bool:

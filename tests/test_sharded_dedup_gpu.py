@@ -1,0 +1,265 @@
+"""GPU: the de-duplicated routing (mi_route_buckets_unique) bit for bit against its torch restatement
+(tests/sharded_dedup_helpers.py), the summing slot backward (mi_slot_fm_bwd_segments) against autograd through
+TorchOps.slot_fm, all ranks emulated on one GPU against the unsharded kernel, and ShardedDeepFM(dedup=True) on a 1-rank
+RCCL group (child process)."""
+import os
+import socket
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from conftest import ROOT, assert_close
+from sharded_dedup_helpers import (DedupTorchOps, congruent_hot_values, field_offsets, hot_value_ids, segments_from_slots,
+                                   slots_from_segments, zipf_ids)
+
+import recsys_benchmark_amd as pkg
+from oracle.sharded_ops import TorchOps
+from recsys_benchmark_amd import _kernels, _lib
+from recsys_benchmark_amd.sharded import (bucket_capacity, dedup_bucket_capacity, field_bucket_capacity, local_num_rows,
+                                          shard_rows)
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda", 0)
+
+
+def _flag():
+    return torch.zeros(1, dtype=torch.int32, device=DEV)
+
+
+def _check_route(x, offsets, world, N, cap, **kw):
+    """Kernel against restatement: send_rows, slot and the overflow word bit for bit; the segment description must list
+    every slot's lookups in ascending flat position."""
+    of_ref = torch.zeros(1, dtype=torch.int32)
+    send_ref, slot_ref, _ = DedupTorchOps.route_buckets_unique(x, offsets, world, N, cap, of_ref)
+    of = _flag()
+    send, slot, seg = _kernels.route_buckets_unique(x.to(DEV), None if offsets is None else offsets.to(DEV), world, N, cap,
+                                                    of, **kw)
+    assert torch.equal(slot.cpu(), slot_ref)
+    assert torch.equal(send.cpu(), send_ref)
+    assert int(of.item()) == int(of_ref.item())
+    rebuilt, ascending = slots_from_segments(seg, world * cap, x.numel())
+    assert ascending and torch.equal(rebuilt, slot_ref.reshape(-1))
+    return send, slot, seg, int(of.item())
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 8])
+@pytest.mark.parametrize("B,F", [(1, 1), (5, 3), (39, 26), (40, 26), (4096, 26), (1000, 39)])
+def test_route_unique_matches_restatement_bit_exact(world, B, F):
+    g = torch.Generator().manual_seed(B * 131 + F + world)
+    dims = torch.randint(1, 5000, (F,), generator=g)
+    N = int(dims.sum())
+    offsets = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.long), dims[:-1]]), 0)
+    x = torch.stack([torch.randint(0, int(d), (B,), generator=g) for d in dims], 1)
+    cap = bucket_capacity(B * F, world, 1.25)
+    _check_route(x, offsets, world, N, cap)
+    _check_route(x, offsets, world, N, cap, field_sort=False)          # the generic stable sort gives the same answer
+    pkg.check_index_errors()
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 8])
+@pytest.mark.parametrize("kind", ["hot", "zipf"])
+def test_route_unique_skewed_ids(kind, world):
+    dims, B = [50, 7, 1000, 3, 211, 4000], 1500                        # B > 1024: the field sort merges runs
+    g = torch.Generator().manual_seed(world)
+    x = hot_value_ids(dims, B, 0.5, g) if kind == "hot" else zipf_ids(dims, B, 2.0, world)
+    cap = dedup_bucket_capacity(dims, B, world, 1.25)
+    *_, over = _check_route(x, field_offsets(dims), world, sum(dims), cap)
+    assert over == 0
+    pkg.check_index_errors()
+
+
+def test_route_unique_overflow_goes_to_the_dump_slot_and_raises_the_flag():
+    x = (torch.arange(300, dtype=torch.int64) % 100 * 4).view(300, 1)   # 100 distinct rows, all at owner 0 of 4
+    cap, world = 64, 4
+    _, slot, _, over = _check_route(x, None, world, 1000, cap)
+    assert over == 1
+    assert int((slot == world * cap).sum()) == 3 * (100 - cap)          # the 36 surplus rows, three lookups each
+
+
+def test_route_unique_out_of_range_ids_hit_the_dump_slot_and_the_error_word():
+    x = torch.tensor([[3, 10], [-1, 2], [7, 0], [3, 2]], dtype=torch.int64)
+    offsets = torch.tensor([0, 8])
+    N = 12                                                              # 8 + 10 >= N, -1 < 0
+    _, slot, _, _ = _check_route(x, offsets, 2, N, 6)
+    assert int(slot[0, 1]) == 12 and int(slot[1, 0]) == 12
+    assert int(slot[0, 0]) == int(slot[3, 0]) and int(slot[1, 1]) == int(slot[3, 1])
+    with pytest.raises(IndexError):
+        pkg.check_index_errors()
+
+
+def test_route_unique_int32_ids_no_offsets_and_noncontiguous():
+    g = torch.Generator().manual_seed(4)
+    x = torch.randint(0, 977, (64, 7), generator=g, dtype=torch.int32)
+    for inp in (x, x.t()):
+        _check_route(inp, None, 4, 977, 200)
+    pkg.check_index_errors()
+
+
+def test_route_unique_empty_batch():
+    send, slot, seg = _kernels.route_buckets_unique(torch.zeros(0, 5, dtype=torch.int64, device=DEV), None, 2, 100, 0, _flag())
+    assert send.numel() == 0 and slot.numel() == 0 and seg.numel() == 0
+    send, slot, seg = _kernels.route_buckets_unique(torch.zeros(0, 5, dtype=torch.int64, device=DEV), None, 2, 101, 3, _flag())
+    assert send.tolist() == [51, 51, 51, 50, 50, 50] and not seg.any()  # only sink rows, no segments
+
+
+@pytest.mark.parametrize("B,F,world", [(66000, 2, 3), (700000, 1, 4)])
+def test_route_unique_beyond_the_field_sorts_limits(B, F, world):
+    """B > 65 536 samples: mi_sort_field_rows declines and the wrapper sorts generically; 700 000 lookups also take the
+    three-launch form (a scan launch between count and assign)."""
+    g = torch.Generator().manual_seed(B + world)
+    dims = [3000, 70000][:F]
+    x = torch.stack([torch.randint(0, d, (B,), generator=g) for d in dims], 1)
+    _check_route(x, field_offsets(dims), world, sum(dims), (B * F) // world + 512)
+    pkg.check_index_errors()
+
+
+def test_route_unique_writes_into_static_buffers():
+    dims, B, world = [50, 7, 1000, 3], 64, 2
+    g = torch.Generator().manual_seed(9)
+    off = field_offsets(dims).to(DEV)
+    cap = dedup_bucket_capacity(dims, B, world, 1.25)
+    slot_out = torch.zeros(B, len(dims), dtype=torch.int64, device=DEV)
+    seg_out = torch.zeros(2 * world * cap + B * len(dims), dtype=torch.int32, device=DEV)
+    send_out = torch.zeros(world * cap, dtype=torch.int64, device=DEV)
+    for _ in range(2):                                                  # the second batch overwrites the first completely
+        x = hot_value_ids(dims, B, 0.5, g).to(DEV)
+        fresh = _kernels.route_buckets_unique(x, off, world, sum(dims), cap, _flag())
+        got = _kernels.route_buckets_unique(x, off, world, sum(dims), cap, _flag(), slot_out=slot_out, segments_out=seg_out,
+                                            send_out=send_out)
+        assert got[0] is send_out and got[1] is slot_out and got[2] is seg_out
+        assert all(torch.equal(a, b) for a, b in zip(got, fresh))
+
+
+@pytest.mark.parametrize("B,F,D", [(1, 1, 16), (33, 26, 16), (64, 39, 16), (17, 100, 8), (9, 5, 64), (300, 3, 4), (40, 2, 256)])
+def test_segment_backward_sums_shared_slots(B, F, D):
+    """Repeated slots (one of them shared by more than kLongSeg = 32 lookups where the batch allows: the whole-wave
+    path), unused slots and a dump-slot lookup, against autograd through the torch restatement."""
+    g = torch.Generator().manual_seed(B + F + D)
+    n = B * F
+    S = n // 2 + 11
+    buf = torch.randn(S + 1, D + 4, generator=g) * 0.1
+    buf[:, D + 1:] = 0
+    buf[S] = 0
+    slot = torch.randint(0, max(S - 5, 1), (n,), generator=g)          # the last slots stay unused
+    slot[torch.rand(n, generator=g) < 0.4] = 2                          # a hot slot
+    slot[0] = S                                                         # one dropped lookup -> the dump row
+    slot = slot.view(B, F)
+    bias = torch.tensor([0.3])
+    g_emb, g_y = torch.randn(B, F, D, generator=g), torch.randn(B, generator=g)
+
+    rb, rbias = buf.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    e_ref, y_ref = TorchOps.slot_fm(rb, slot, rbias)
+    ((e_ref * g_emb).sum() + (y_ref * g_y).sum()).backward()
+
+    seg = segments_from_slots(slot, S).to(DEV)
+    grads = []
+    for _ in range(2):
+        hb, hbias = buf.to(DEV).requires_grad_(True), bias.to(DEV).requires_grad_(True)
+        e, y = _kernels.slot_fm_unique(hb, slot.to(DEV), hbias, seg)
+        ((e * g_emb.to(DEV)).sum() + (y * g_y.to(DEV)).sum()).backward()
+        grads.append((hb.grad.clone(), hbias.grad.clone()))
+    assert torch.equal(e.detach().cpu(), e_ref.detach())
+    assert_close(y, y_ref, 1e-5, 1e-5, "y_fm")
+    hg = grads[0][0]
+    assert_close(hg[:S, :D + 1], rb.grad[:S, :D + 1], 1e-5, 1e-5, "grad rows")
+    assert not hg[:, D + 1:].any()
+    unused = torch.ones(S, dtype=torch.bool)
+    unused[slot.view(-1)[slot.view(-1) < S]] = False
+    assert unused.any() and not hg[:S][unused.to(DEV)].any()           # exactly zero
+    assert_close(grads[0][1], rbias.grad, 1e-5, 1e-6, "bias grad")
+    assert torch.equal(grads[0][0], grads[1][0]) and torch.equal(grads[0][1], grads[1][1])     # two runs: same bits
+    pkg.check_index_errors()
+
+
+def test_segment_backward_adds_in_ascending_lookup_order():
+    """The sum of a slot is taken in ascending flat lookup index, on both paths (5 and 70 lookups in a slot): terms
+    chosen so that any other order rounds differently."""
+    for L in (5, 70):
+        D, F = 4, 1
+        B = L
+        slot = torch.zeros(B, F, dtype=torch.int64)
+        g_emb = torch.zeros(B, F, D)
+        g_emb[:, 0, 0] = torch.tensor([1e8, 1.0, -1e8] + [3.0 ** -k for k in range(L - 3)])
+        want = torch.zeros((), dtype=torch.float32)
+        for v in g_emb[:, 0, 0]:
+            want = want + v
+        buf = torch.zeros(3, D + 4, device=DEV).requires_grad_(True)
+        e, y = _kernels.slot_fm_unique(buf, slot.to(DEV), None, segments_from_slots(slot, 2).to(DEV))
+        (e * g_emb.to(DEV)).sum().backward()
+        assert float(buf.grad[0, 0]) == float(want)
+
+
+@pytest.mark.parametrize("world", [2, 4, 8])
+def test_emulated_ranks_deduplicated_reproduce_the_unsharded_lookup(world):
+    """All `world` ranks emulated on one GPU (the all-to-alls done by slicing), skewed ids, buckets of the de-duplicated
+    capacity: embeddings exactly the unsharded fused kernel's, y and the gradients summed at the owners within fp32."""
+    g = torch.Generator().manual_seed(world)
+    dims, D, B = [50, 7, 1000, 3, 211], 16, 48
+    F, N = len(dims), sum(dims)
+    offsets = field_offsets(dims).to(DEV)
+    W, w1 = torch.randn(N, D, generator=g).to(DEV), torch.randn(N, 1, generator=g).to(DEV)
+    bias = torch.tensor([0.1], device=DEV)
+    hot = [min(h, d - 1) for h, d in zip([(-int(o)) % world for o in field_offsets(dims)], dims)]
+    xs = [hot_value_ids(dims, B, 0.6, g, hot=hot).to(DEV) for _ in range(world)]
+    cap = dedup_bucket_capacity(dims, B, world, 1.25)
+    S = world * cap
+    shards = []
+    for r in range(world):
+        n = local_num_rows(N, r, world)
+        Wl, wl = torch.zeros(n + 1, D, device=DEV), torch.zeros(n + 1, 1, device=DEV)
+        Wl[:n], wl[:n] = shard_rows(W, r, world), shard_rows(w1, r, world)
+        shards.append((Wl, wl))
+    over = _flag()
+    routed = [_kernels.route_buckets_unique(x, offsets, world, N, cap, over) for x in xs]
+    assert int(over.item()) == 0
+    local_rows = [torch.cat([routed[r][0][o * cap:(o + 1) * cap] for r in range(world)]) for o in range(world)]
+    packed = [_kernels.gather_pack_rows(local_rows[o], *shards[o]) for o in range(world)]
+    g_total, g1_total = torch.zeros(N, D, device=DEV), torch.zeros(N, device=DEV)
+    ref_total, ref1_total = torch.zeros(N, D, device=DEV), torch.zeros(N, device=DEV)
+    g_send = []
+    for r in range(world):
+        recv = torch.zeros(S + 1, D + 4, device=DEV)
+        recv[:S] = torch.cat([packed[o][r * cap:(r + 1) * cap] for o in range(world)])
+        recv.requires_grad_(True)
+        emb, y = _kernels.slot_fm_unique(recv, routed[r][1], bias, routed[r][2])
+        Wf, w1f = W.clone().requires_grad_(True), w1.clone().requires_grad_(True)
+        emb_ref, y_ref = _kernels.gather_fm(xs[r], offsets, Wf, w1f, bias, True, True)
+        assert torch.equal(emb, emb_ref)
+        assert_close(y, y_ref, 1e-6, 1e-6, "y_fm")
+        ge, gy = torch.randn(B, F, D, generator=g).to(DEV), torch.randn(B, generator=g).to(DEV)
+        ((emb * ge).sum() + (y * gy).sum()).backward()
+        ((emb_ref * ge).sum() + (y_ref * gy).sum()).backward()
+        ref_total += Wf.grad.to_dense()
+        ref1_total += w1f.grad.to_dense().view(-1)
+        g_send.append(recv.grad[:S])
+    for o in range(world):
+        g_owner = torch.cat([g_send[r][o * cap:(o + 1) * cap] for r in range(world)])
+        n = local_num_rows(N, o, world)
+        acc = torch.zeros(n + 1, D + 4, device=DEV).index_add_(0, local_rows[o], g_owner)
+        assert not acc[n].any()                                               # the sink only sees zeros
+        g_total[o::world] += acc[:n, :D]
+        g1_total[o::world] += acc[:n, D]
+    assert_close(g_total, ref_total, 1e-5, 1e-5, "table grad")
+    assert_close(g1_total, ref1_total, 1e-5, 1e-5, "first-order grad")
+    pkg.check_index_errors()
+
+
+def test_wrapper_rejects_mismatched_buffers_loudly():
+    x = torch.zeros(4, 2, dtype=torch.int64, device=DEV)
+    with pytest.raises(ValueError):
+        _kernels.route_buckets_unique(x, None, 2, 10, 4, _flag(), segments_out=torch.zeros(3, dtype=torch.int32, device=DEV))
+    with pytest.raises(ValueError):
+        _kernels.slot_fm_unique(torch.zeros(9, 8, device=DEV), x, None, torch.zeros(5, dtype=torch.int32, device=DEV))
+
+
+def test_sharded_deepfm_dedup_on_one_rank_matches_the_plain_lookup():
+    """Eager and make_graphed_step, three consecutive skewed batches, against dedup=False with the same weights; in a
+    child process of its own (tests/_sharded_dedup_check.py) so that it shares no process group with another module."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_sharded_dedup_check.py"), str(port)],
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and "SHARDED_DEDUP_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -37,7 +37,7 @@ def main():
         t = time.perf_counter()
         model.zero_grad(set_to_none=True)
         t = tick("zero_grad", t) if record else t
-        recv, slot = _Exchange.apply(x, model.embedding_shard, model.fc_shard, model)
+        recv, slot, _ = _Exchange.apply(x, model.embedding_shard, model.fc_shard, model)
         t = tick("exchange_fwd", t) if record else t
         out = model._graphed_local(recv, slot)
         t = tick("graph_fwd", t) if record else t
