@@ -418,6 +418,31 @@ MI_API int mi_spmm_sliced(const int32_t *crow, const int32_t *col, const float *
                           float scale, int32_t D, const int32_t *long_rows, int32_t n_long, const uint32_t *xmask,
                           void *stream);
 
+/* ---- a14b: HCCF layer (src/models/hccf.py:53-63), the product above with a leaky-residual epilogue ----
+ * With S = [user_emb_step; item_emb_step] (n_rows = users + items) and the square block adjacency
+ * A = [[0, M], [M^T, 0]] in CSR (M = sparse_dropout(matrix): one draw serves both blocks, so A is symmetric):
+ *   pre          = A[row,:] . S                       S as two row segments (Sa rows [0,s_split), Sb the rest; Sb null = one)
+ *   S_out[row]   = S[row] + LeakyReLU_slope(pre)      (S_out nullable: the last layer; it must not alias S)
+ *   R_out[row]   = (R[row] + S_out[row]) * scale      R as two row segments likewise; R_out may alias R (in place)
+ *   bits[row]    = ceil(D/32) words, bit d%32 of word d/32 set iff pre[d] > 0   (nullable: no backward, or slope == 1)
+ * short_rows / long_rows as in mi_spmm_csr.  D = 4 * 2^k <= 256 with 16-byte aligned operands takes the float4 kernel, any
+ * other D one wave per row.  One launch; no atomics, so the sum order is the CSR's and reruns give the same bits.
+ *
+ * mi_hccf_bwd is one step of the backward recurrence  G_{k-1} = c g + G_k + A (G_k . f_k),  f_k = 1 where the bit of
+ * layer k is set, else slope (torch's convention: pre == 0 takes the slope):
+ *   out[row] = xscale * (sum_j A[row,j] * (G[j,:] . f[j,:]) + G[row]) + cg * g[row]
+ * G and g as two row segments each; the first step (k = L) passes G = g and xscale = c (G_L = c g is never stored), later
+ * steps xscale = 1.  bits null: f = 1.  xmask (nullable) as in mi_spmm_csr_masked: rows of G promised to be all zeros.
+ * out must alias neither G nor g. */
+MI_API int mi_hccf_fwd(const int32_t *crow, const int32_t *col, const float *val, const float *Sa, const float *Sb,
+                       int32_t s_split, float *S_out, const float *Ra, const float *Rb, int32_t r_split, float *R_out,
+                       float scale, float slope, uint32_t *bits, int32_t n_rows, int32_t D, const int32_t *short_rows,
+                       int32_t n_short, const int32_t *long_rows, int32_t n_long, void *stream);
+MI_API int mi_hccf_bwd(const int32_t *crow, const int32_t *col, const float *val, const float *Ga, const float *Gb,
+                       int32_t G_split, float xscale, const uint32_t *bits, float slope, const float *ga, const float *gb,
+                       int32_t g_split, float cg, float *out, int32_t n_rows, int32_t D, const int32_t *short_rows,
+                       int32_t n_short, const int32_t *long_rows, int32_t n_long, const uint32_t *xmask, void *stream);
+
 /* ---- a10: TT-Rec lookup (TTRecTorch semantics) --------------------------------
  * src/models/embeddings/tensortrain_embeddings.py:100-150: mixed-radix split of idx over
  * p_shapes, one slice per core (core c: fp32[1, p_c, r_c*q_c*r_{c+1}] viewed (p_c,r_c,q_c,r_{c+1})),

@@ -1156,6 +1156,178 @@ class SpMM(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------
+# HCCF propagation (src/models/hccf.py:36-68): the LightGCN-shaped product with a leaky-residual epilogue
+class HccfPlan:
+    """The square block CSR of A = [[0, M], [M^T, 0]] for a U x I pattern of M, built once per pattern: a CsrPlan of A
+    and `vidx`, which takes M's nnz stored values (CSR order) to A's 2 nnz (`[arange(nnz), perm]` of the rectangular
+    plan: A's upper rows are M's rows, its lower rows M^T's)."""
+
+    def __init__(self, crow: torch.Tensor, col: torch.Tensor, shape, keep):
+        U, I = shape
+        rect = CsrPlan(crow, col, (U, I))
+        nnz = rect.nnz
+        self.shape, self.nnz = (U, I), nnz
+        self.keep = keep                      # the caller's index tensors: the cache key is their addresses (see CsrPlan)
+        self.keep_versions = tuple(t._version for t in keep)
+        self.vidx = torch.cat([torch.arange(nnz, device=crow.device), rect.perm])
+        crow64, col64 = crow.to(torch.int64), col.to(torch.int64)
+        self.square = CsrPlan(torch.cat([crow64, rect.crow_t[1:].to(torch.int64) + nnz]),
+                              torch.cat([col64 + U, rect.col_t.to(torch.int64)]), (U + I, U + I))
+
+    def values(self, vals: torch.Tensor) -> torch.Tensor:
+        return _f32c(vals).index_select(0, self.vidx)
+
+
+_hccf_plans = {}
+hccf_plan_stats = {"built": 0, "hit": 0}
+
+
+def _hccf_pattern(matrix: torch.Tensor):
+    """(key tensors, stored values) of a U x I sparse matrix.  A COO matrix is read as it is stored when its indices are
+    already in canonical (sorted, distinct) order — what `coalesce()` and SparseDropout leave, whatever the matrix's
+    coalesced flag says: that is checked once per index tensor, by hccf_plan — and coalesced otherwise."""
+    if matrix.layout == torch.sparse_csr:
+        return (matrix.crow_indices(), matrix.col_indices()), matrix.values()
+    if matrix.layout == torch.sparse_coo:
+        return (matrix._indices(),), matrix._values()
+    raise ValueError(f"Not supported matrix layout: {matrix.layout}")
+
+
+def hccf_plan(matrix: torch.Tensor):
+    """(HccfPlan, stored values in the plan's order) of a U x I sparse matrix, the plan cached the way csr_plan caches: on
+    the addresses and versions of the index tensors, which the entry keeps alive."""
+    keep, vals = _hccf_pattern(matrix)
+    key = tuple(t.data_ptr() for t in keep) + (vals.numel(), tuple(matrix.shape), str(vals.device))
+    plan = _hccf_plans.get(key)
+    if plan is not None and plan.keep_versions != tuple(t._version for t in keep):
+        plan = None
+    if plan is not None:
+        hccf_plan_stats["hit"] += 1
+        return plan, vals
+    U, I = matrix.shape
+    if matrix.layout == torch.sparse_coo:
+        idx = keep[0]
+        flat = idx[0] * I + idx[1]
+        if idx.shape[1] > 1 and not bool((flat[1:] > flat[:-1]).all()):      # (one sync, once per index tensor)
+            matrix = matrix.coalesce()
+            keep, vals = (matrix.indices(),), matrix.values()
+            idx = keep[0]
+            key = (idx.data_ptr(), vals.numel(), tuple(matrix.shape), str(vals.device))
+        crow = torch.zeros(U + 1, dtype=torch.int64, device=idx.device)
+        crow[1:] = torch.cumsum(torch.bincount(idx[0], minlength=U), 0)
+        col = idx[1]
+    else:
+        crow, col = keep
+    if len(_hccf_plans) > 16:
+        _hccf_plans.clear()
+    plan = HccfPlan(crow, col, (U, I), keep)
+    _hccf_plans[key] = plan
+    hccf_plan_stats["built"] += 1
+    return plan, vals
+
+
+def _hccf_layer_fwd(sq: CsrPlan, val, S, S_out, R, R_out, scale, slope, bits, D):
+    sr, lr = sq.short_rows, sq.long_rows
+    _lib.check(
+        _lib.load().mi_hccf_fwd(sq.crow.data_ptr(), sq.col.data_ptr(), val.data_ptr(), S[0].data_ptr(), _lib.ptr(S[1]), S[2],
+                                _lib.ptr(S_out), R[0].data_ptr(), _lib.ptr(R[1]), R[2], R_out.data_ptr(), float(scale),
+                                float(slope), _lib.ptr(bits), sq.shape[0], D, sr.data_ptr() if sr.numel() else None, sr.numel(),
+                                lr.data_ptr() if lr.numel() else None, lr.numel(), _lib.stream_ptr(val.device)),
+        "mi_hccf_fwd")
+
+
+def _hccf_layer_bwd(sq: CsrPlan, val, G, xscale, bits, slope, g, cg, out, D, xmask=None):
+    sr, lr = sq.short_rows, sq.long_rows
+    _lib.check(
+        _lib.load().mi_hccf_bwd(sq.crow.data_ptr(), sq.col.data_ptr(), val.data_ptr(), G[0].data_ptr(), _lib.ptr(G[1]), G[2],
+                                float(xscale), _lib.ptr(bits), float(slope), g[0].data_ptr(), _lib.ptr(g[1]), g[2], float(cg),
+                                out.data_ptr(), sq.shape[0], D, sr.data_ptr() if sr.numel() else None, sr.numel(),
+                                lr.data_ptr() if lr.numel() else None, lr.numel(), _lib.ptr(xmask),
+                                _lib.stream_ptr(val.device)),
+        "mi_hccf_bwd")
+
+
+class HCCFPropagate(torch.autograd.Function):
+    """S_k = S_{k-1} + LeakyReLU(A_k S_{k-1}),  out = (S_0 + ... + S_L) / (L + 1)  with S_0 = [Xu; Xi] and A_k the block
+    adjacency of the k-th value tensor — one launch per layer each way.  Kept for the backward: per layer the value
+    tensor and ONE BIT per element of the pre-activation (none when slope == 1), no [N, D] float."""
+
+    @staticmethod
+    def forward(ctx, Xu, Xi, plan: HccfPlan, num_layers: int, slope: float, *vals):
+        dev = _lib.require_gpu(Xu, Xi, *vals)
+        Xuc, Xic = _f32c(Xu), _f32c(Xi)
+        U, I = plan.shape
+        if Xuc.shape[0] != U or Xic.shape[0] != I or Xuc.shape[1] != Xic.shape[1]:
+            raise ValueError(f"the matrix is {plan.shape} but the tables are {tuple(Xuc.shape)} and {tuple(Xic.shape)}")
+        N, D, L, sq = U + I, Xuc.shape[1], num_layers, plan.square
+        need_bits = slope != 1 and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        R = torch.empty((N, D), dtype=torch.float32, device=dev)
+        bufs = [torch.empty((N, D), dtype=torch.float32, device=dev) for _ in range(min(2, L - 1))]
+        S, bits = (Xuc, Xic, U), []
+        for k in range(1, L + 1):
+            last = k == L
+            S_out = None if last else bufs[(k - 1) % len(bufs)]          # ping-pong: other rows still gather S
+            b = torch.empty((N, (D + 31) // 32), dtype=torch.int32, device=dev) if need_bits else None
+            _hccf_layer_fwd(sq, vals[k - 1], S, S_out, (Xuc, Xic, U) if k == 1 else (R, None, 0), R,
+                            1.0 / (L + 1) if last else 1.0, slope, b, D)
+            if need_bits:
+                bits.append(b)
+            S = (S_out, None, 0)
+        ctx.plan, ctx.num_layers, ctx.slope, ctx.n_bits = plan, L, slope, len(bits)
+        ctx.save_for_backward(*bits, *vals)
+        return R[:U], R[U:]
+
+    @staticmethod
+    def backward(ctx, gu, gi):
+        saved = ctx.saved_tensors
+        bits, vals = saved[:ctx.n_bits], saved[ctx.n_bits:]
+        plan, L, slope = ctx.plan, ctx.num_layers, ctx.slope
+        U, I = plan.shape
+        dev = vals[0].device
+        D = (gu if gu is not None else gi).shape[1]
+        gu = _f32c(gu) if gu is not None else torch.zeros((U, D), dtype=torch.float32, device=dev)
+        gi = _f32c(gi) if gi is not None else torch.zeros((I, D), dtype=torch.float32, device=dev)
+        c = 1.0 / (L + 1)
+        g = (gu, gi, U)
+        # the incoming gradient is non-zero on the batch's rows only: the first step does not fetch the others
+        xmask = _row_mask(gu, gi, D) if MASK_FIRST_BACKWARD_LAYER else None
+        bufs = [torch.empty((U + I, D), dtype=torch.float32, device=dev) for _ in range(min(2, L))]
+        G, xscale, out = g, c, None
+        for k in range(L, 0, -1):            # G_{k-1} = c g + G_k + A_k (G_k . f_k); G_L = c g is never stored
+            out = bufs[(L - k) % len(bufs)]
+            _hccf_layer_bwd(plan.square, vals[k - 1], G, xscale, bits[k - 1] if bits else None, slope, g, c, out, D,
+                            xmask=xmask if k == L else None)
+            G, xscale = (out, None, 0), 1.0
+        return (out[:U], out[U:], None, None, None) + (None,) * L
+
+
+def hccf_propagate(matrix, Xu: torch.Tensor, Xi: torch.Tensor, num_layers: int, slope: float):
+    """(user_emb, item_emb) of the HCCF backbone (src/models/hccf.py:36-68).  matrix: the U x I sparse matrix (COO as
+    graph_utils.get_adj returns it, or CSR), or a list of `num_layers` such matrices over ONE sparsity pattern, layer k
+    using the k-th (SparseDropout draws).  The block adjacency is planned once per pattern (hccf_plan); per layer the
+    values cost one index_select.  No host sync and no data-dependent shape once the pattern has been seen."""
+    if num_layers == 0:
+        return Xu, Xi
+    mats = list(matrix) if isinstance(matrix, (list, tuple)) else [matrix] * num_layers
+    if len(mats) != num_layers:
+        raise ValueError(f"{len(mats)} matrices for {num_layers} layers")
+    plan, vals, seen = None, [], {}
+    for m in mats:
+        if id(m) in seen:
+            vals.append(seen[id(m)])
+            continue
+        p, v = hccf_plan(m)
+        if plan is not None and p is not plan:
+            raise ValueError("the per-layer matrices must share one sparsity pattern (the same index tensors)")
+        if v.requires_grad:
+            raise NotImplementedError("gradients w.r.t. the adjacency values are not provided")
+        plan = p
+        seen[id(m)] = plan.values(v)
+        vals.append(seen[id(m)])
+    return HCCFPropagate.apply(Xu, Xi, plan, num_layers, float(slope), *vals)
+
+
+# --------------------------------------------------------------------------------------
 # fp32 MFMA GEMM with fused epilogues (building block of the CrossNet heads)
 EPI = {"none": 0, "bias": 1, "tanh": 2, "cross": 3, "add": 4, "mul_dtanh": 5, "tanh_gate": 6, "accum": 7}
 

@@ -62,6 +62,10 @@ SIGNATURES = {
     "mi_row_mask": [_p, _p, _i32, _i32, _i32, _p, _p],
     "mi_spmm_sliced": [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p, ctypes.c_float, _i32, _p, _i32,
                        _p, _p],
+    "mi_hccf_fwd": [_p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _p, ctypes.c_float, ctypes.c_float, _p, _i32, _i32, _p, _i32, _p,
+                    _i32, _p],
+    "mi_hccf_bwd": [_p, _p, _p, _p, _p, _i32, ctypes.c_float, _p, ctypes.c_float, _p, _p, _i32, ctypes.c_float, _p, _i32, _i32,
+                    _p, _i32, _p, _i32, _p, _p],
     "mi_spmm_tiled": [_p, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _p, ctypes.c_float, _i32, _p],
     "mi_gemm_f32": [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _i64,
                     _i64, _i32, _p, _p, _i32, _i64, _p, _i32, _i64, _p, _i32, _p, _i32, _i64, _i32, _p],

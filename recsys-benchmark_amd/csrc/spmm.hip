@@ -398,6 +398,235 @@ __global__ __launch_bounds__(kBlock) void k_spmm_anyD(
 
 inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
 
+// ------------------------------------------------------------------------------------- HCCF layer (src/models/hccf.py:53-63) ----
+// With S = [U; I] and A = [[0, M], [M^T, 0]] (one dropout draw serves both blocks, so A is symmetric, values included) a layer is
+//   pre = A S;  S' = S + leaky(pre);  R' = (R + S') * scale
+// i.e. the LightGCN product above with another epilogue: the mapping of k_spmm_planned (one wave per short row, a 16-wave
+// workgroup per hub) is kept, the epilogue reads the row's own S and R and, when a backward will follow, keeps ONE BIT per
+// element of `pre` (set iff pre > 0: torch's LeakyReLU sends pre == 0 to the slope side) instead of the [N, D] pre-activation.
+//   bits: uint32[n_rows][ceil(D / 32)], bit d % 32 of word d / 32.  In the float4 kernels lane q of a row holds elements
+//   4 q .. 4 q + 3 = nibble q % 8 of word q / 8.
+// The backward of a layer, G' = c g + G + A (G . f) with f = 1 or slope by the bit of the GATHERED row, is the same product with
+// the factor applied to every gathered row.  No atomics: the sum order is the CSR's.
+__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
+
+// all lanes of the wave call this (the sign words are combined by shuffles); `writer` lanes hold the row's `pre` and store
+template <int LPR>
+__device__ __forceinline__ void hccf_fwd_epilogue(float4 pre, int row, int q, bool writer, const Seg2 &S, float *S_out,
+                                                  const Seg2 &R, float *R_out, float scale, float slope, uint32_t *bits) {
+  constexpr int D = LPR * 4;
+  constexpr int W = (D + 31) / 32;
+  if (bits) {
+    const uint32_t nib = (pre.x > 0.f ? 1u : 0u) | (pre.y > 0.f ? 2u : 0u) | (pre.z > 0.f ? 4u : 0u) | (pre.w > 0.f ? 8u : 0u);
+    int w = (int)(nib << ((q & 7) * 4));
+#pragma unroll
+    for (int m = 1; m < 8 && m < LPR; m <<= 1) w |= __shfl_xor(w, m);
+    if (writer && (q & 7) == 0) bits[(int64_t)row * W + (q >> 3)] = (uint32_t)w;
+  }
+  if (writer) {
+    float4 s = ld4(seg_row(S, row, D) + q * 4);
+    s.x += leaky(pre.x, slope); s.y += leaky(pre.y, slope); s.z += leaky(pre.z, slope); s.w += leaky(pre.w, slope);
+    if (S_out) st4(S_out + (int64_t)row * D + q * 4, s);
+    float4 r = ld4(seg_row(R, row, D) + q * 4);
+    r.x = (r.x + s.x) * scale; r.y = (r.y + s.y) * scale; r.z = (r.z + s.z) * scale; r.w = (r.w + s.w) * scale;
+    st4(R_out + (int64_t)row * D + q * 4, r);
+  }
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kHubWaves * kWave) void k_hccf_fwd(
+    const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 S,
+    float *__restrict__ S_out, Seg2 R, float *__restrict__ R_out, float scale, float slope, uint32_t *__restrict__ bits,
+    const int *__restrict__ short_rows, int n_short, const int *__restrict__ long_rows, int n_long) {
+  constexpr int NPW = kWave / LPR;
+  __shared__ float4 part[kHubWaves][LPR];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int q = lane % LPR, k = lane / LPR;
+  if ((int)blockIdx.x < n_long) {
+    const int row = long_rows[blockIdx.x];
+    const int lo = crow[row], hi = crow[row + 1];
+    float4 a = row_dot<LPR>(col, val, S, lo, hi, w * NPW + k, NPW * kHubWaves, q);
+    a = slot_sum<LPR>(a);
+    if (k == 0) part[w][q] = a;
+    __syncthreads();
+    if (w == 0) {
+      float4 s = part[0][q];
+#pragma unroll
+      for (int i = 1; i < kHubWaves; ++i) {
+        const float4 p = part[i][q];
+        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+      }
+      hccf_fwd_epilogue<LPR>(s, row, q, k == 0, S, S_out, R, R_out, scale, slope, bits);
+    }
+    return;
+  }
+  const int nblk = gridDim.x - n_long;
+  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
+    const int row = short_rows ? short_rows[it] : it;
+    const int lo = crow[row], hi = crow[row + 1];
+    float4 a = row_dot<LPR>(col, val, S, lo, hi, k, NPW, q);
+    a = slot_sum<LPR>(a);
+    hccf_fwd_epilogue<LPR>(a, row, q, k == 0, S, S_out, R, R_out, scale, slope, bits);
+  }
+}
+
+// row_dot with every gathered row scaled, element by element, by 1 or `slope` from the row's sign word
+template <int LPR, bool MASKED, bool SIGNED>
+__device__ __forceinline__ float4 row_dot_signed(const int *__restrict__ col, const float *__restrict__ val, const Seg2 &X,
+                                                 const uint32_t *__restrict__ bits, float slope, int lo, int hi, int slot,
+                                                 int nslots, int q, const uint32_t *__restrict__ xmask) {
+  constexpr int D = LPR * 4;
+  constexpr int W = (D + 31) / 32;
+  constexpr int U = 4;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 a = z4;
+  for (int j0 = lo + slot; j0 < hi; j0 += nslots * U) {
+    int c[U];
+    float v[U];
+    float4 x[U];
+    uint32_t sw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * nslots;
+      const bool ok = j < hi;
+      c[u] = ok ? col[j] : 0;
+      v[u] = ok ? val[j] : 0.f;
+    }
+    if (MASKED) {
+      uint32_t mw[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) mw[u] = xmask[c[u] >> 5];
+#pragma unroll
+      for (int u = 0; u < U; ++u) x[u] = ((mw[u] >> (c[u] & 31)) & 1u) ? ld4(seg_row(X, c[u], D) + q * 4) : z4;
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) x[u] = ld4(seg_row(X, c[u], D) + q * 4);
+    }
+    if (SIGNED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) sw[u] = bits[(int64_t)c[u] * W + (q >> 3)] >> ((q & 7) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (SIGNED) {
+        // one gathered row at a time: the empty statement ties x[u] to the sum so far.  Left to the scheduler, the 16
+        // products x * slope are all formed before the first select (30 more VGPRs, occupancy 6 instead of 8)
+        asm volatile("" : "+v"(x[u].x), "+v"(x[u].y), "+v"(x[u].z), "+v"(x[u].w), "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+        x[u].x = (sw[u] & 1u) ? x[u].x : x[u].x * slope; x[u].y = (sw[u] & 2u) ? x[u].y : x[u].y * slope;
+        x[u].z = (sw[u] & 4u) ? x[u].z : x[u].z * slope; x[u].w = (sw[u] & 8u) ? x[u].w : x[u].w * slope;
+      }
+      a.x += v[u] * x[u].x; a.y += v[u] * x[u].y; a.z += v[u] * x[u].z; a.w += v[u] * x[u].w;
+    }
+  }
+  return a;
+}
+
+// out[row] = xscale (A[row, :] (G . f) + G[row]) + cg g[row]
+__device__ __forceinline__ void hccf_bwd_epilogue(float4 p, int row, int q, int D, const Seg2 &G, float xscale, const Seg2 &g,
+                                                  float cg, float *out) {
+  const float4 s = ld4(seg_row(G, row, D) + q * 4);
+  const float4 t = ld4(seg_row(g, row, D) + q * 4);
+  p.x = (p.x + s.x) * xscale + cg * t.x; p.y = (p.y + s.y) * xscale + cg * t.y;
+  p.z = (p.z + s.z) * xscale + cg * t.z; p.w = (p.w + s.w) * xscale + cg * t.w;
+  st4(out + (int64_t)row * D + q * 4, p);
+}
+
+template <int LPR, bool MASKED, bool SIGNED>
+__global__ __launch_bounds__(kHubWaves * kWave) void k_hccf_bwd(
+    const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 G, float xscale,
+    const uint32_t *__restrict__ bits, float slope, Seg2 g, float cg, float *__restrict__ out,
+    const int *__restrict__ short_rows, int n_short, const int *__restrict__ long_rows, int n_long,
+    const uint32_t *__restrict__ xmask) {
+  constexpr int NPW = kWave / LPR;
+  constexpr int D = LPR * 4;
+  __shared__ float4 part[kHubWaves][LPR];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int q = lane % LPR, k = lane / LPR;
+  if ((int)blockIdx.x < n_long) {
+    const int row = long_rows[blockIdx.x];
+    const int lo = crow[row], hi = crow[row + 1];
+    float4 a = row_dot_signed<LPR, MASKED, SIGNED>(col, val, G, bits, slope, lo, hi, w * NPW + k, NPW * kHubWaves, q, xmask);
+    a = slot_sum<LPR>(a);
+    if (k == 0) part[w][q] = a;
+    __syncthreads();
+    if (w == 0 && k == 0) {
+      float4 s = part[0][q];
+#pragma unroll 4          // (fully unrolled, the 15 LDS reads and the epilogue's loads are all in flight at once: 70 VGPRs)
+      for (int i = 1; i < kHubWaves; ++i) {
+        const float4 p = part[i][q];
+        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+      }
+      hccf_bwd_epilogue(s, row, q, D, G, xscale, g, cg, out);
+    }
+    return;
+  }
+  const int nblk = gridDim.x - n_long;
+  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
+    const int row = short_rows ? short_rows[it] : it;
+    const int lo = crow[row], hi = crow[row + 1];
+    float4 a = row_dot_signed<LPR, MASKED, SIGNED>(col, val, G, bits, slope, lo, hi, k, NPW, q, xmask);
+    a = slot_sum<LPR>(a);
+    if (k == 0) hccf_bwd_epilogue(a, row, q, D, G, xscale, g, cg, out);
+  }
+}
+
+// any D: one wave per row, lane l takes columns l, l + 64, ...; a ballot of a 64-column trip is two sign words
+__global__ __launch_bounds__(kBlock) void k_hccf_fwd_anyD(
+    const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 S,
+    float *__restrict__ S_out, Seg2 R, float *__restrict__ R_out, float scale, float slope, uint32_t *__restrict__ bits,
+    int n_rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int W = (D + 31) / 32;
+  const int wave0 = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * kWavesPerBlock;
+  for (int row = wave0; row < n_rows; row += nwaves) {
+    const int lo = crow[row], hi = crow[row + 1];
+    for (int d0 = 0; d0 < D; d0 += kWave) {
+      const int d = d0 + lane;
+      const bool ok = d < D;
+      float pre = 0.f;
+      if (ok)
+        for (int j = lo; j < hi; ++j) pre += val[j] * seg_row(S, col[j], D)[d];
+      if (bits) {
+        const unsigned long long b = __ballot(ok && pre > 0.f);
+        if (lane == 0) {
+          bits[(int64_t)row * W + (d0 >> 5)] = (uint32_t)b;
+          if (d0 + 32 < D) bits[(int64_t)row * W + (d0 >> 5) + 1] = (uint32_t)(b >> 32);
+        }
+      }
+      if (ok) {
+        const float s = seg_row(S, row, D)[d] + leaky(pre, slope);
+        if (S_out) S_out[(int64_t)row * D + d] = s;
+        R_out[(int64_t)row * D + d] = (seg_row(R, row, D)[d] + s) * scale;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_hccf_bwd_anyD(
+    const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 G, float xscale,
+    const uint32_t *__restrict__ bits, float slope, Seg2 g, float cg, float *__restrict__ out, int n_rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int W = (D + 31) / 32;
+  const int wave0 = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * kWavesPerBlock;
+  for (int row = wave0; row < n_rows; row += nwaves) {
+    const int lo = crow[row], hi = crow[row + 1];
+    for (int d = lane; d < D; d += kWave) {
+      float a = 0.f;
+      for (int j = lo; j < hi; ++j) {
+        const int c = col[j];
+        float x = seg_row(G, c, D)[d];
+        if (bits) x *= ((bits[(int64_t)c * W + (d >> 5)] >> (d & 31)) & 1u) ? 1.f : slope;
+        a += val[j] * x;
+      }
+      out[(int64_t)row * D + d] = (a + seg_row(G, row, D)[d]) * xscale + cg * seg_row(g, row, D)[d];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -513,6 +742,94 @@ int mi_spmm_csr_sel(const int32_t *crow, const int32_t *col, const float *val, c
   } else {
     MI_LAUNCH("spmm_csr_rows", k_spmm_anyD, grid_for_waves(n_rows), kBlock, stream, crow, col, val, X, Y, A,
               has_acc, acc_out, scale, n_rows, D);
+  }
+  return launch_status();
+}
+
+// HCCF layer, forward (k_hccf_fwd above): one launch for all n_rows rows of the square block adjacency.
+int mi_hccf_fwd(const int32_t *crow, const int32_t *col, const float *val, const float *Sa, const float *Sb, int32_t s_split,
+                float *S_out, const float *Ra, const float *Rb, int32_t r_split, float *R_out, float scale, float slope,
+                uint32_t *bits, int32_t n_rows, int32_t D, const int32_t *short_rows, int32_t n_short,
+                const int32_t *long_rows, int32_t n_long, void *stream) {
+  if (n_rows < 0 || D <= 0 || n_short < 0 || n_long < 0 || s_split < 0 || r_split < 0) return MI_ERR_INVALID_ARG;
+  if (n_rows == 0) return MI_OK;
+  if (!crow || !Sa || !Ra || !R_out || S_out == Sa || (Sb && S_out == Sb)) return MI_ERR_INVALID_ARG;
+  if ((n_short > 0 && !short_rows) || (n_long > 0 && !long_rows)) return MI_ERR_INVALID_ARG;
+  if (n_long > 60000) return MI_ERR_UNSUPPORTED;
+  Seg2 S{Sa, Sb ? Sb : Sa + (int64_t)s_split * D, Sb ? s_split : 0x7fffffff};
+  Seg2 R{Ra, Rb ? Rb : Ra, Rb ? r_split : 0x7fffffff};
+  const bool planned = short_rows || long_rows;
+  if (!planned) n_short = n_rows;
+  const bool al = aligned16(Sa) && (!Sb || aligned16(Sb)) && (!S_out || aligned16(S_out)) && aligned16(Ra) &&
+                  (!Rb || aligned16(Rb)) && aligned16(R_out);
+  if (vec_ok(D) && al) {
+    int sb = (n_short + kHubWaves - 1) / kHubWaves;
+    if (sb > 1024) sb = 1024;
+#define CALL(LPR)                                                                                                         \
+  MI_LAUNCH("hccf_fwd", (k_hccf_fwd<LPR>), n_long + sb, kHubWaves * kWave, stream, crow, col, val, S, S_out, R, R_out, scale, \
+            slope, bits, short_rows, n_short, long_rows, n_long)
+    switch (D / 4) {
+      case 1: CALL(1); break;
+      case 2: CALL(2); break;
+      case 4: CALL(4); break;
+      case 8: CALL(8); break;
+      case 16: CALL(16); break;
+      case 32: CALL(32); break;
+      case 64: CALL(64); break;
+      default: return MI_ERR_UNSUPPORTED;
+    }
+#undef CALL
+  } else {
+    MI_LAUNCH("hccf_fwd_rows", k_hccf_fwd_anyD, grid_for_waves(n_rows), kBlock, stream, crow, col, val, S, S_out, R, R_out,
+              scale, slope, bits, n_rows, D);
+  }
+  return launch_status();
+}
+
+// HCCF layer, backward (k_hccf_bwd above).  `out` must alias neither G nor g (other rows gather them).
+int mi_hccf_bwd(const int32_t *crow, const int32_t *col, const float *val, const float *Ga, const float *Gb, int32_t G_split,
+                float xscale, const uint32_t *bits, float slope, const float *ga, const float *gb, int32_t g_split, float cg,
+                float *out, int32_t n_rows, int32_t D, const int32_t *short_rows, int32_t n_short,
+                const int32_t *long_rows, int32_t n_long, const uint32_t *xmask, void *stream) {
+  if (n_rows < 0 || D <= 0 || n_short < 0 || n_long < 0 || G_split < 0 || g_split < 0) return MI_ERR_INVALID_ARG;
+  if (n_rows == 0) return MI_OK;
+  if (!crow || !Ga || !ga || !out || out == Ga || out == ga || (Gb && out == Gb) || (gb && out == gb)) return MI_ERR_INVALID_ARG;
+  if ((n_short > 0 && !short_rows) || (n_long > 0 && !long_rows)) return MI_ERR_INVALID_ARG;
+  if (n_long > 60000) return MI_ERR_UNSUPPORTED;
+  Seg2 G{Ga, Gb ? Gb : Ga + (int64_t)G_split * D, Gb ? G_split : 0x7fffffff};
+  Seg2 g{ga, gb ? gb : ga + (int64_t)g_split * D, gb ? g_split : 0x7fffffff};
+  const bool planned = short_rows || long_rows;
+  if (!planned) n_short = n_rows;
+  // (xmask only lets the float4 kernel skip fetches of all-zero rows; the generic path ignores it — same result)
+  const bool al = aligned16(Ga) && (!Gb || aligned16(Gb)) && aligned16(ga) && (!gb || aligned16(gb)) && aligned16(out);
+  if (vec_ok(D) && al) {
+    int sb = (n_short + kHubWaves - 1) / kHubWaves;
+    if (sb > 1024) sb = 1024;
+#define CALL2(LPR, M, S)                                                                                                 \
+  MI_LAUNCH("hccf_bwd", (k_hccf_bwd<LPR, M, S>), n_long + sb, kHubWaves * kWave, stream, crow, col, val, G, xscale, bits, slope, \
+            g, cg, out, short_rows, n_short, long_rows, n_long, xmask)
+#define CALL(LPR)                                                                                                        \
+  do {                                                                                                                   \
+    if (xmask && bits) CALL2(LPR, true, true);                                                                           \
+    else if (xmask) CALL2(LPR, true, false);                                                                             \
+    else if (bits) CALL2(LPR, false, true);                                                                              \
+    else CALL2(LPR, false, false);                                                                                       \
+  } while (0)
+    switch (D / 4) {
+      case 1: CALL(1); break;
+      case 2: CALL(2); break;
+      case 4: CALL(4); break;
+      case 8: CALL(8); break;
+      case 16: CALL(16); break;
+      case 32: CALL(32); break;
+      case 64: CALL(64); break;
+      default: return MI_ERR_UNSUPPORTED;
+    }
+#undef CALL
+#undef CALL2
+  } else {
+    MI_LAUNCH("hccf_bwd_rows", k_hccf_bwd_anyD, grid_for_waves(n_rows), kBlock, stream, crow, col, val, G, xscale, bits, slope,
+              g, cg, out, n_rows, D);
   }
   return launch_status();
 }

@@ -31,7 +31,8 @@ _GRAPH: Dict[str, _Entry] = {
     "lightgcn": _Entry(".lightgcn", "LightGCN", None, (), True),
     "single-lightgcn": _Entry(".lightgcn", "SingleLightGCN", None, (), True),
 }
-_OUT_OF_SCOPE = {"hccf": "hccf is outside this build's scope (SURVEY.md §2.1 #14)"}
+_OUT_OF_SCOPE = {"hccf": "the factory key 'hccf' is held back: construct recsys_benchmark_amd.HCCFModelCore(num_user, num_item, ...) "
+                         "directly (DESIGN.md §7)"}
 _LOADABLE = ("deepfm", "dcn_mix")    # the model kinds load_ctr_model knows (the reference's `load` classmethods)
 
 

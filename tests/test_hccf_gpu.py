@@ -1,0 +1,308 @@
+"""GPU: HCCFModelCore and _kernels.hccf_propagate (csrc/spmm.hip: hccf_fwd / hccf_bwd) against the reference's goldens and
+the float64 block form of tests/hccf_helpers.py."""
+import copy
+import functools
+import math
+
+import pytest
+import torch
+
+import hccf_helpers as hh
+from conftest import assert_close, load_golden
+
+import recsys_benchmark_amd as pkg
+from oracle import reference_ops as ro
+from recsys_benchmark_amd import _kernels, trainer
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _coo(idx, vals, U, I, csr=False):
+    m = torch.sparse_coo_tensor(idx, vals, (U, I)).coalesce().to(DEV)
+    return m.to_sparse_csr() if csr else m
+
+
+# ---- 1. the reference's goldens through the model ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["hccf_L1", "hccf_L2", "hccf_L3"])
+@pytest.mark.parametrize("train", [False, True])
+def test_model_matches_reference_golden(name, train):
+    g = load_golden(name)
+    nu, ni, L, slope = int(g["num_user"]), int(g["num_item"]), int(g["num_layers"]), float(g["slope"])
+    model = pkg.HCCFModelCore(nu, ni, num_layers=L, hidden_size=8, slope=slope, p_dropout=0)
+    model.load_state_dict(g.group("param/"), strict=True)
+    model.to(DEV).train(train)
+    adj = _coo(g.t("adj_indices"), g.t("adj_values"), nu, ni)
+    ue, ie = model(adj)
+    assert_close(ue, g.t("user_emb"), 1e-5, 1e-6, "user_emb")
+    assert_close(ie, g.t("item_emb"), 1e-5, 1e-6, "item_emb")
+    users, pos, neg = g.t("users").to(DEV), g.t("pos").to(DEV), g.t("neg").to(DEV)
+    loss = ro.bpr_loss(ue[users], ie[pos], ie[neg])
+    reg = model.get_reg_loss(users, pos, neg)
+    assert_close(loss, g.t("bpr"), 1e-5, 1e-6, "bpr")
+    assert_close(reg, g.t("reg"), 1e-5, 1e-5, "reg")
+    (loss + 1e-4 * reg).backward()
+    named = dict(model.named_parameters())
+    for k, ref in g.group("grad/").items():
+        assert_close(named[k].grad, ref, 1e-4, 1e-7, k)
+    pkg.check_index_errors()
+
+
+# ---- 2. the dyadic fixture through the op -------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _dyadic(D, L, slope):
+    """(fixture, float64 reference) computed once per case and shared, never modified."""
+    fx = hh.dyadic_fixture(D, L)
+    if L:
+        hh.assert_dyadic_exact(fx, slope if slope not in (0, 1) else 0.5)
+    return fx, hh.dyadic_reference(fx, slope)
+
+
+def _run(fx, slope, L, csr=False, gu="fx", gi="fx", single=False):
+    base = _coo(fx["idx"], fx["vals"][0], fx["U"], fx["I"], csr)
+    # per-layer matrices over ONE pattern, the way SparseDropout hands them out: new values on the same index tensors
+    if csr:
+        mats = [torch.sparse_csr_tensor(base.crow_indices(), base.col_indices(), v.to(DEV), base.shape) for v in fx["vals"]]
+    else:
+        mats = [torch.sparse_coo_tensor(base.indices(), v.to(DEV), base.shape) for v in fx["vals"]]
+    Xu = fx["Xu"].to(DEV).requires_grad_(True)
+    Xi = fx["Xi"].to(DEV).requires_grad_(True)
+    ue, ie = _kernels.hccf_propagate(mats[0] if single else mats, Xu, Xi, L, slope)
+    gu = fx["gu"] if isinstance(gu, str) else gu
+    gi = fx["gi"] if isinstance(gi, str) else gi
+    outs, grads = zip(*[(o, g.to(DEV)) for o, g in ((ue, gu), (ie, gi)) if g is not None])
+    torch.autograd.backward(outs, grads)
+    return ue.detach().cpu(), ie.detach().cpu(), Xu.grad.cpu(), Xi.grad.cpu()
+
+
+def _check(got, want, L, what):
+    ue, ie, du, di = got
+    rue, rie, rdu, rdi = want
+    if L in (1, 3):          # 1 / (L + 1) is a power of two: every value is exact, in any summation order
+        for a, b, n in ((ue, rue, "user_emb"), (ie, rie, "item_emb"), (du, rdu, "dXu"), (di, rdi, "dXi")):
+            assert torch.equal(a.double(), b), f"{what} {n}: max diff {float((a.double() - b).abs().max()):.3e}"
+    else:                    # one rounding of 1/3 and one of the product, against one of the quotient
+        assert_close(ue.double(), rue, 4 * 2.0 ** -24, 0.0, what + " user_emb")
+        assert_close(ie.double(), rie, 4 * 2.0 ** -24, 0.0, what + " item_emb")
+        assert_close(du.double(), rdu, 1e-4, 1e-5, what + " dXu")
+        assert_close(di.double(), rdi, 1e-4, 1e-5, what + " dXi")
+
+
+@pytest.mark.parametrize("D", [4, 6, 40, 64, 256])      # 6 and 40: no float4 kernel takes them (the one-wave-per-row path)
+@pytest.mark.parametrize("L", [1, 2, 3])
+@pytest.mark.parametrize("slope", [0.5, 0.25])
+def test_dyadic_fixture(D, L, slope):
+    assert _kernels._float4_rows(D) == (D in (4, 64, 256))
+    fx, want = _dyadic(D, L, slope)
+    _check(_run(fx, slope, L), want, L, f"D={D} L={L} slope={slope}")
+
+
+# ---- 3. variants ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [64, 40])
+def test_csr_input_equals_coo_input(D):
+    fx, want = _dyadic(D, 3, 0.5)
+    coo, csr = _run(fx, 0.5, 3), _run(fx, 0.5, 3, csr=True)
+    assert all(torch.equal(a, b) for a, b in zip(coo, csr))
+    _check(csr, want, 3, "csr")
+
+
+@pytest.mark.parametrize("D", [64, 6])
+@pytest.mark.parametrize("side", ["user", "item"])
+def test_gradient_on_one_output_only(D, side):
+    fx, _ = _dyadic(D, 3, 0.25)
+    gu, gi = (fx["gu"], None) if side == "user" else (None, fx["gi"])
+    want = hh.dyadic_reference(fx, 0.25, gu=gu, gi=gi)
+    _check(_run(fx, 0.25, 3, gu=gu, gi=gi), want, 3, side + " gradient only")
+
+
+@pytest.mark.parametrize("D", [64, 40])
+@pytest.mark.parametrize("slope", [1.0, 0.0])
+def test_slope_one_is_the_identity_and_slope_zero_is_relu(D, slope):
+    fx, want = _dyadic(D, 3, slope)
+    if slope == 1.0:         # the helper with phi = identity: plain linear propagation
+        ue, ie, pres = hh.hccf_forward(fx["idx"], fx["vals"], fx["Xu"], fx["Xi"], 1.0)
+        S = torch.cat([fx["Xu"], fx["Xi"]]).double()
+        R = S.clone()
+        for v in fx["vals"]:
+            S = S + hh.block_adjacency(fx["idx"], v, fx["U"], fx["I"]) @ S
+            R = R + S
+        assert torch.equal(torch.cat([ue, ie]), R / 4)
+    _check(_run(fx, slope, 3), want, 3, f"slope={slope}")
+
+
+def test_zero_layers_returns_the_tables():
+    fx, _ = _dyadic(64, 0, 0.5)
+    Xu, Xi = fx["Xu"].to(DEV).requires_grad_(True), fx["Xi"].to(DEV).requires_grad_(True)
+    ue, ie = _kernels.hccf_propagate(_coo(fx["idx"], torch.ones(fx["idx"].shape[1]), fx["U"], fx["I"]), Xu, Xi, 0, 0.5)
+    assert torch.equal(ue, Xu) and torch.equal(ie, Xi)
+    (ue.sum() + 2 * ie.sum()).backward()
+    assert torch.equal(Xu.grad, torch.ones_like(Xu)) and torch.equal(Xi.grad, torch.full_like(Xi, 2.0))
+
+
+def test_two_runs_give_identical_bits_on_rounded_inputs():
+    """Inputs that DO round (normal tables, normalised values): the sum order is the CSR's, so reruns agree bit for bit."""
+    gen = torch.Generator().manual_seed(5)
+    fx = dict(hh.dyadic_fixture(64, 2))
+    nnz = fx["idx"].shape[1]
+    fx["vals"] = [torch.rand(nnz, generator=gen) for _ in range(2)]
+    fx["Xu"], fx["Xi"] = torch.randn(fx["U"], 64, generator=gen), torch.randn(fx["I"], 64, generator=gen)
+    fx["gu"], fx["gi"] = torch.randn(fx["U"], 64, generator=gen), torch.randn(fx["I"], 64, generator=gen)
+    a, b = _run(fx, 0.5, 2), _run(fx, 0.5, 2)
+    assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+    # and the forward (continuous in the pre-activations, so nothing hinges on the kink here) is the float64 value to float32
+    # accuracy: hub rows sum 270 terms, values reach ~50
+    ue, ie, _ = hh.hccf_forward(fx["idx"], fx["vals"], fx["Xu"], fx["Xi"], 0.5)
+    assert_close(a[0].double(), ue, 1e-4, 1e-4, "user_emb")
+    assert_close(a[1].double(), ie, 1e-4, 1e-4, "item_emb")
+
+
+def test_one_matrix_serves_every_layer_and_mismatched_patterns_are_refused():
+    fx = dict(hh.dyadic_fixture(64, 3))
+    fx["vals"] = [fx["vals"][0]] * 3
+    want = hh.dyadic_reference(fx, 0.5)
+    _check(_run(fx, 0.5, 3, single=True), want, 3, "one matrix")
+    a = _coo(fx["idx"], fx["vals"][0], fx["U"], fx["I"])
+    b = _coo(fx["idx"][:, :-1], fx["vals"][0][:-1], fx["U"], fx["I"])
+    with pytest.raises(ValueError):
+        _kernels.hccf_propagate([a, b], fx["Xu"].to(DEV), fx["Xi"].to(DEV), 2, 0.5)
+    with pytest.raises(ValueError):
+        _kernels.hccf_propagate([a], fx["Xu"].to(DEV), fx["Xi"].to(DEV), 2, 0.5)
+
+
+# ---- 4. the model with dropout ------------------------------------------------------------------------------------------------
+class _Recording(torch.nn.Module):
+    """Wraps model.sparse_dropout: keeps what it hands out."""
+
+    def __init__(self, inner):
+        super().__init__()
+        self.inner, self.seen = inner, []
+
+    def forward(self, matrix):
+        out = self.inner(matrix)
+        self.seen.append(out)
+        return out
+
+
+@pytest.mark.parametrize("layout", ["coo", "csr"])
+def test_model_with_dropout_equals_the_helper_on_the_recorded_draws(layout):
+    g = load_golden("hccf_L3")          # the small graph of the goldens (37 x 53, one user of degree 40), normal tables
+    nu, ni, L, slope, D = int(g["num_user"]), int(g["num_item"]), 3, 0.5, 8
+    idx, vals = g.t("adj_indices"), g.t("adj_values")
+    torch.manual_seed(11)
+    model = pkg.HCCFModelCore(nu, ni, num_layers=L, hidden_size=D, slope=slope, p_dropout=0.5)
+    with torch.no_grad():               # |pre| well away from the kink: entries of order 1 instead of xavier's 0.3
+        model.user_emb_table.weight.normal_()
+        model.item_emb_table.weight.normal_()
+    model.to(DEV).train()
+    rec = _Recording(model.sparse_dropout)
+    model.sparse_dropout = rec
+    adj = _coo(idx, vals, nu, ni, csr=layout == "csr")
+    users, pos, neg = g.t("users").to(DEV), g.t("pos").to(DEV), g.t("neg").to(DEV)
+
+    def step(seed):
+        torch.manual_seed(seed)
+        rec.seen.clear()
+        model.zero_grad()
+        ue, ie = model(adj)
+        loss = ro.bpr_loss(ue[users], ie[pos], ie[neg])
+        reg = model.get_reg_loss(users, pos, neg)
+        (loss + 1e-4 * reg).backward()
+        draws = [(m.values() if layout == "csr" else m._values()).detach().cpu().clone() for m in rec.seen]
+        return (ue.detach().cpu(), ie.detach().cpu(), model.user_emb_table.weight.grad.cpu().clone(),
+                model.item_emb_table.weight.grad.cpu().clone(), draws)
+
+    _kernels.hccf_plan_stats.update(built=0, hit=0)
+    first = step(3)
+    draws = first[4]
+    assert len(draws) == L and not torch.equal(draws[0], draws[1])             # one draw per layer
+    for d in draws:
+        assert set((d / vals).round().unique().tolist()) == {0.0, 2.0}          # dropped, or scaled by 1 / (1 - p)
+    Xu, Xi = model.user_emb_table.weight.detach().cpu(), model.item_emb_table.weight.detach().cpu()
+    rue, rie, _, _, rdu, rdi, pres = hh.reference_loss_and_grads(idx, draws, Xu, Xi, slope, users.cpu(), pos.cpu(), neg.cpu(),
+                                                                  1e-4)
+    print("smallest non-zero |pre-activation| under the recorded draws:", hh.min_nonzero_abs(pres))
+    assert hh.min_nonzero_abs(pres) >= 1e-5, "fixture precondition: a pre-activation sits on the LeakyReLU kink"
+    assert_close(first[0].double(), rue, 1e-5, 1e-5, "user_emb")
+    assert_close(first[1].double(), rie, 1e-5, 1e-5, "item_emb")
+    assert_close(first[2].double(), rdu, 1e-4, 1e-5, "grad user table")
+    assert_close(first[3].double(), rdi, 1e-4, 1e-5, "grad item table")
+    again = step(3)                      # the same torch seed: the same draws, the same bits
+    assert all(torch.equal(a, b) for a, b in zip(first[:4], again[:4]))
+    assert all(torch.equal(a, b) for a, b in zip(first[4], again[4]))
+    other = step(4)                      # a new forward draws anew
+    assert not torch.equal(other[4][0], first[4][0]) and not torch.equal(other[0], first[0])
+    # 3 forwards x 3 draws over one sparsity pattern: planned once
+    assert _kernels.hccf_plan_stats["built"] <= 1 and _kernels.hccf_plan_stats["hit"] >= 3 * L - 1, _kernels.hccf_plan_stats
+    model.eval()                         # no draw in eval: the matrix as it is
+    rec.seen.clear()
+    ue, ie = model(adj)
+    eue, eie, _ = hh.hccf_forward(idx, [vals] * L, Xu, Xi, slope)
+    assert_close(ue.double(), eue, 1e-5, 1e-5, "eval user_emb")
+    assert len(rec.seen) == 1
+    pkg.check_index_errors()
+
+
+# ---- 5. the trainers ---------------------------------------------------------------------------------------------------------
+def _toy_graph(num_user=60, num_item=90, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    graph = {u: sorted(set(torch.randint(0, num_item, (int(torch.randint(2, 12, (1,), generator=gen)),),
+                                         generator=gen).tolist())) for u in range(num_user)}
+    graph[0] = sorted(set(graph[0]) | {num_item - 1})                 # every item id is in range of the dataset
+    return graph
+
+
+def test_graphed_step_equals_eager_steps():
+    from recsys_benchmark_amd.graph_utils import get_adj
+    from recsys_benchmark_amd.optim import Adam
+
+    nu, ni = 60, 90
+    graph = _toy_graph(nu, ni)
+    adj = get_adj(graph, ni, nu, normalize=True).to(DEV)
+    torch.manual_seed(1)
+    model = pkg.HCCFModelCore(nu, ni, num_layers=2, hidden_size=16, p_dropout=0).to(DEV)
+    eager = copy.deepcopy(model)
+    model.train()
+    eager.train()
+    wd = 1e-3
+    gstep = trainer.GraphedCFTrainStep(model, adj, Adam(model.parameters(), lr=1e-2), wd, use_graph=True)
+    estep = trainer.GraphedCFTrainStep(eager, adj, Adam(eager.parameters(), lr=1e-2), wd, use_graph=False)
+    gen = torch.Generator().manual_seed(3)
+    for _ in range(5):
+        users, pos, neg = (torch.randint(0, n, (64,), generator=gen).to(DEV) for n in (nu, ni, ni))
+        got, want = gstep(users, pos, neg).cpu(), estep(users, pos, neg).cpu()
+        for key, a, b in zip(("loss", "rec_loss", "reg_loss", "cl_loss"), got.tolist(), want.tolist()):
+            assert abs(a - b) < 1e-4 * max(1.0, abs(b)), (key, a, b)
+    assert gstep._graph is not None, "the HCCF step was never captured"
+    assert gstep.steps == 5 and float(gstep.sums[0]) > 0
+    for (k, a), (_, b) in zip(model.state_dict().items(), eager.state_dict().items()):
+        assert_close(a, b, 5e-3, 1e-4, k + " graph vs eager")
+    pkg.check_index_errors()
+
+
+def test_train_and_validate_epoch_from_the_device_dataset():
+    from recsys_benchmark_amd.optim import Adam
+
+    graph = _toy_graph()
+    ds = pkg.DeviceCFGraphDataset(graph, adj_style="hccf", device=DEV)
+    torch.manual_seed(0)
+    model = pkg.HCCFModelCore(ds.num_users, ds.num_items, num_layers=2, hidden_size=16).to(DEV)       # p_dropout = 0.5
+    before = model.user_emb_table.weight.detach().clone()
+    loader = pkg.DeviceCFLoader(ds, 64, shuffle=True, seed=1)
+    out = trainer.train_epoch_cf(loader, model, Adam(model.parameters(), lr=1e-2), device=DEV, log_step=2, weight_decay=1e-3)
+    assert {"loss", "rec_loss", "reg_loss", "cl_loss"} <= set(out) and all(math.isfinite(v) for v in out.values()), out
+    assert out["rec_loss"] > 0 and not torch.equal(before, model.user_emb_table.weight.detach())
+    gen = torch.Generator().manual_seed(2)
+    test = {u: sorted(set(torch.randint(0, ds.num_items, (3,), generator=gen).tolist())) for u in range(ds.num_users)}
+    val = pkg.DeviceCFTestLoader(pkg.DeviceCFTestDataset(test, device=DEV), 32)
+    res = trainer.validate_epoch_cf(ds, val, model, device=DEV, k=10, metrics=["ndcg", "recall"])
+    assert 0 <= res["ndcg"] <= 1 and 0 <= res["recall"] <= 1
+    # what validation scored with: the eval-mode propagation of the float64 block form
+    model.eval()
+    with torch.no_grad():
+        ue, ie = model(ds.get_norm_adj().to(DEV))
+    adj = ds.get_norm_adj().coalesce()
+    rue, rie, _ = hh.hccf_forward(adj.indices(), [adj.values()] * 2, model.user_emb_table.weight.detach().cpu(),
+                                  model.item_emb_table.weight.detach().cpu(), 0.5)
+    assert_close(ue.double(), rue, 1e-5, 1e-5, "user_emb after training")
+    assert_close(ie.double(), rie, 1e-5, 1e-5, "item_emb after training")
+    pkg.check_index_errors()
