@@ -33,6 +33,9 @@ inline int grid_for_waves(int64_t n_wave_items) {
 
 __host__ __device__ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// the row widths of the float4 kernels: a row of D floats is LPR = D / 4 lanes x float4, LPR one of 1, 2, 4 .. 64
+inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
+
 // ---- device helpers ----------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -97,3 +100,17 @@ __device__ __forceinline__ float read_partial(const float *p) {
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (hipStream_t)(stream),     \
                          __VA_ARGS__);                                                  \
   } while (0)
+
+// Expands `CALL(LPR)` with the compile-time LPR that equals the run-time `lpr` (= D / 4 of a vec_ok(D)); any other
+// value returns MI_ERR_UNSUPPORTED from the calling function.
+#define MI_DISPATCH_LPR(lpr, CALL)      \
+  switch (lpr) {                        \
+    case 1: CALL(1); break;             \
+    case 2: CALL(2); break;             \
+    case 4: CALL(4); break;             \
+    case 8: CALL(8); break;             \
+    case 16: CALL(16); break;           \
+    case 32: CALL(32); break;           \
+    case 64: CALL(64); break;           \
+    default: return MI_ERR_UNSUPPORTED; \
+  }

@@ -691,7 +691,6 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows_q(const int64_t *__restr
   if (bad && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
 }
 
-inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
 inline int grid_for_elems(int64_t total) {
   int64_t g = (total + kBlock - 1) / kBlock;
   if (g < 1) g = 1;
@@ -736,16 +735,7 @@ int mi_dual_gather_fwd_off(const int64_t *idx, const int64_t *offsets, int64_t *
     else if (xform == XF_SOFT) MI_LAUNCH("dual_gather_fwd", (k_dual_fwd<LPR, XF_SOFT>), grid, kBlock, stream, idx, t, out, n, F, op, err, offsets, rows_out); \
     else MI_LAUNCH("dual_gather_fwd", (k_dual_fwd<LPR, XF_MASK>), grid, kBlock, stream, idx, t, out, n, F, op, err, offsets, rows_out); \
   } while (0)
-    switch (lpr) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      case 64: CALL(64); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+    MI_DISPATCH_LPR(lpr, CALL)
 #undef CALL
   } else {
     if (offsets) return MI_ERR_UNSUPPORTED;      // (the element-per-thread form takes finished row ids)
@@ -791,15 +781,7 @@ int mi_dual_gather_bwd_rows(const int64_t *idx, const float *g_out, const float 
     if (fg < 1) fg = 1;
     float *ws = (workspace && n1 * De <= kBlock && kBlock % (n1 * De) == 0) ? workspace : nullptr;
 #define CALL(LPR) MI_LAUNCH("dual_gather_bwd_rows", (k_dual_bwd_rows4<LPR>), (int)fg, kBlock, stream, idx, t, g_out, gT1, g2vals, rows2, n, F, op, ws)
-    switch (lpr) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      default: CALL(64); break;
-    }
+    MI_DISPATCH_LPR(lpr, CALL)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
 #undef CALL
     return launch_status();
   }
@@ -915,16 +897,7 @@ int mi_fm_fwd(const float *emb, const int64_t *rows, const float *w1, const floa
   const int grid = grid_for_waves(B);
   if (vec_ok(D) && aligned16(emb)) {
 #define CALL(LPR) MI_LAUNCH("fm_fwd", (k_fm_fwd<LPR>), grid, kBlock, stream, emb, rows, w1, bias, yfm, B, F, N, err)
-    switch (D / 4) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      case 64: CALL(64); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+    MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
   } else {
     MI_LAUNCH("fm_fwd", k_fm_fwd_anyD, grid, kBlock, stream, emb, rows, w1, bias, yfm, B, F, D, N, err);

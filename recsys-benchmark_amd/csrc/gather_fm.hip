@@ -706,7 +706,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter_add_rows_anyD(
 }
 
 // ------------------------------------------------------------- dispatch ------
-inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
 inline int nit_for(int F, int LPR) {
   const int RS = kWave / LPR;
   const int n = (F + RS - 1) / RS;
@@ -732,17 +731,6 @@ inline int nit_for(int F, int LPR) {
     case 3: CALL(LPR, 3); break;        \
     case 4: CALL(LPR, 4); break;        \
     default: CALL(LPR, 0); break;       \
-  }
-#define MI_DISPATCH_LPR(lpr, CALL)      \
-  switch (lpr) {                        \
-    case 1: CALL(1); break;             \
-    case 2: CALL(2); break;             \
-    case 4: CALL(4); break;             \
-    case 8: CALL(8); break;             \
-    case 16: CALL(16); break;           \
-    case 32: CALL(32); break;           \
-    case 64: CALL(64); break;           \
-    default: return MI_ERR_UNSUPPORTED; \
   }
 
 }  // namespace

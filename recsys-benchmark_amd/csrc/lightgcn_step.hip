@@ -557,15 +557,7 @@ static int bpr_fwd_impl(bool zero_ticket, const float *U, const int64_t *ui, con
   if (D % 4 == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && aligned16(U) && aligned16(P) && aligned16(Nn)) {
     const int gv = grid_for_waves((B + 64 / lpr - 1) / (64 / lpr));
 #define BPRV(L) MI_LAUNCH("bpr_fwd", (k_bpr_fwd_v<L>), gv, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, sig, workspace, ticket, loss, plus, plus_w)
-    switch (lpr) {
-      case 1: BPRV(1); break;
-      case 2: BPRV(2); break;
-      case 4: BPRV(4); break;
-      case 8: BPRV(8); break;
-      case 16: BPRV(16); break;
-      case 32: BPRV(32); break;
-      default: BPRV(64); break;
-    }
+    MI_DISPATCH_LPR(lpr, BPRV)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
 #undef BPRV
     return launch_status();
   }
@@ -620,15 +612,7 @@ static int rowsq_fwd_impl(bool zero_ticket, const float *U, const int64_t *ui, c
   if (D % 4 == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && aligned16(U) && aligned16(P) && aligned16(Nn)) {
     const int gv = grid_for_waves((B + 64 / lpr - 1) / (64 / lpr));
 #define RSQV(L) MI_LAUNCH("rowsq_fwd", (k_rowsq_fwd_v<L>), gv, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, workspace, ticket, out)
-    switch (lpr) {
-      case 1: RSQV(1); break;
-      case 2: RSQV(2); break;
-      case 4: RSQV(4); break;
-      case 8: RSQV(8); break;
-      case 16: RSQV(16); break;
-      case 32: RSQV(32); break;
-      default: RSQV(64); break;
-    }
+    MI_DISPATCH_LPR(lpr, RSQV)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
 #undef RSQV
     return launch_status();
   }

@@ -287,7 +287,6 @@ __global__ __launch_bounds__(kBlock) void k_scatter_axpy(const int64_t *__restri
   }
 }
 
-inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
 }  // namespace
 
 extern "C" {
@@ -342,16 +341,9 @@ static int launch_sorted_rows(AdamArgs a, int32_t D, const float *vals, const vo
   } else if (D == 2) {
     CALL(2, 1);
   } else if (vec_ok(D) && aligned16(vals) && aligned16(W) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(acc)) {
-    switch (D / 4) {
-      case 1: CALL(1, 4); break;
-      case 2: CALL(2, 4); break;
-      case 4: CALL(4, 4); break;
-      case 8: CALL(8, 4); break;
-      case 16: CALL(16, 4); break;
-      case 32: CALL(32, 4); break;
-      case 64: CALL(64, 4); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+#define CALL4(LPR) CALL(LPR, 4)
+    MI_DISPATCH_LPR(D / 4, CALL4)
+#undef CALL4
 #undef CALL
   } else {
     MI_LAUNCH("sparse_adam", k_sparse_adam_anyD, grid_for_waves(n), kBlock, stream, a, D);

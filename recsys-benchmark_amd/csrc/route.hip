@@ -388,9 +388,6 @@ __global__ __launch_bounds__(kBlock) void k_unpack_rows(const float *__restrict_
   }
 }
 
-inline bool vec_ok(int D) {
-  return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0;
-}
 inline int64_t route_groups(int64_t n) { return (n + kChunk - 1) / kChunk; }
 
 }  // namespace
@@ -458,16 +455,9 @@ int mi_gather_pack_rows(const int64_t *rows, const float *W, const float *w1, fl
   if (!vec_ok(D) || !aligned16(W) || !aligned16(out)) return MI_ERR_UNSUPPORTED;
   const int64_t rows_per_tile = (int64_t)(kWave / (D / 4)) * 4;
   const int grid = grid_for_waves((m + rows_per_tile - 1) / rows_per_tile);
-  switch (D / 4) {
-#define CASE(LPR)                                                                            \
-  case LPR:                                                                                  \
-    MI_LAUNCH("gather_pack", (k_gather_pack<LPR>), grid, kBlock, stream, rows, W, w1, out, m, \
-              Nl, err);                                                                      \
-    break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return MI_ERR_UNSUPPORTED;
-  }
+#define CALL(LPR) MI_LAUNCH("gather_pack", (k_gather_pack<LPR>), grid, kBlock, stream, rows, W, w1, out, m, Nl, err)
+  MI_DISPATCH_LPR(D / 4, CALL)
+#undef CALL
   return launch_status();
 }
 
@@ -478,15 +468,9 @@ int mi_unpack_rows(const float *packed, float *vals, float *lin, int64_t m, int3
   if (!vec_ok(D) || !aligned16(packed) || !aligned16(vals)) return MI_ERR_UNSUPPORTED;
   const int64_t rows_per_wave = kWave / (D / 4);
   const int grid = grid_for_waves((m + rows_per_wave - 1) / rows_per_wave);
-  switch (D / 4) {
-#define CASE(LPR)                                                                                 \
-  case LPR:                                                                                       \
-    MI_LAUNCH("unpack_rows", (k_unpack_rows<LPR>), grid, kBlock, stream, packed, vals, lin, m);  \
-    break;
-    CASE(1) CASE(2) CASE(4) CASE(8) CASE(16) CASE(32) CASE(64)
-#undef CASE
-    default: return MI_ERR_UNSUPPORTED;
-  }
+#define CALL(LPR) MI_LAUNCH("unpack_rows", (k_unpack_rows<LPR>), grid, kBlock, stream, packed, vals, lin, m)
+  MI_DISPATCH_LPR(D / 4, CALL)
+#undef CALL
   return launch_status();
 }
 

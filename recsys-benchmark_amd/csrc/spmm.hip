@@ -16,28 +16,40 @@
 namespace {
 using namespace mi;
 
-struct Seg2 {            // rows [0,split) live at a, rows [split, ..) at b (b may alias a + split*D)
+struct Seg2 {            // rows [0,split) live at a, rows [split, ..) at b
   const float *a, *b;
   int split;
 };
+// b == nullptr: one table, every row lives at a
+inline Seg2 seg2(const float *a, const float *b, int split) { return Seg2{a, b ? b : a, b ? split : 0x7fffffff}; }
+// every pointer of the list is 16-byte aligned (a null one, i.e. an operand that is not given, passes)
+template <class... P>
+inline bool all_aligned16(const P *...p) { return (aligned16(p) && ...); }
 __device__ __forceinline__ const float *seg_row(const Seg2 &s, int row, int D) {
   return row < s.split ? s.a + (int64_t)row * D : s.b + (int64_t)(row - s.split) * D;
 }
 
-// xmask (nullable): one bit per row of X, 0 = the row is all zeros and is not fetched.  The first layer of a backward
+// The gather loop of every row-per-wave kernel: this lane's part of  sum_j val[j] * X[col[j], 4 q .. 4 q + 3]  over the
+// edges lo + slot, lo + slot + nslots, .. < hi of a row, 4 gathers in flight.
+// MASKED: xmask holds one bit per row of X, 0 = the row is all zeros and is not fetched.  The first layer of a backward
 // propagation multiplies A^T with a gradient that is non-zero only on the batch's rows (BPR: <= 3 B of 69 716 rows at
 // Yelp2018 size), and the gather traffic — what bounds this kernel — shrinks with the fraction of rows that are not.
-template <int LPR>
-__device__ __forceinline__ float4 row_dot(const int *__restrict__ col, const float *__restrict__ val,
-                                          const Seg2 &X, int lo, int hi, int slot, int nslots, int q,
-                                          const uint32_t *__restrict__ xmask = nullptr) {
+// SIGNED (the HCCF backward, below): every gathered row is scaled, element by element, by 1 or `slope` from the row's
+// sign word in `bits`.
+template <int LPR, bool MASKED, bool SIGNED>
+__device__ __forceinline__ float4 row_dot(const int *__restrict__ col, const float *__restrict__ val, const Seg2 &X, int lo,
+                                          int hi, int slot, int nslots, int q, const uint32_t *__restrict__ xmask = nullptr,
+                                          const uint32_t *__restrict__ bits = nullptr, float slope = 1.f) {
   constexpr int D = LPR * 4;
+  constexpr int W = (D + 31) / 32;
   constexpr int U = 4;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 a = z4;
   for (int j0 = lo + slot; j0 < hi; j0 += nslots * U) {
     int c[U];
     float v[U];
     float4 x[U];
+    uint32_t sw[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int j = j0 + u * nslots;
@@ -45,23 +57,42 @@ __device__ __forceinline__ float4 row_dot(const int *__restrict__ col, const flo
       c[u] = ok ? col[j] : 0;
       v[u] = ok ? val[j] : 0.f;
     }
-    if (xmask) {
+    if (MASKED) {
       uint32_t mw[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) mw[u] = xmask[c[u] >> 5];
 #pragma unroll
-      for (int u = 0; u < U; ++u)
-        x[u] = ((mw[u] >> (c[u] & 31)) & 1u) ? ld4(seg_row(X, c[u], D) + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int u = 0; u < U; ++u) x[u] = ((mw[u] >> (c[u] & 31)) & 1u) ? ld4(seg_row(X, c[u], D) + q * 4) : z4;
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) x[u] = ld4(seg_row(X, c[u], D) + q * 4);
     }
+    if (SIGNED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) sw[u] = bits[(int64_t)c[u] * W + (q >> 3)] >> ((q & 7) * 4);
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      if (SIGNED) {
+        // one gathered row at a time: the empty statement ties x[u] to the sum so far.  Left to the scheduler, the 16
+        // products x * slope are all formed before the first select (30 more VGPRs, occupancy 6 instead of 8)
+        asm volatile("" : "+v"(x[u].x), "+v"(x[u].y), "+v"(x[u].z), "+v"(x[u].w), "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+        x[u].x = (sw[u] & 1u) ? x[u].x : x[u].x * slope; x[u].y = (sw[u] & 2u) ? x[u].y : x[u].y * slope;
+        x[u].z = (sw[u] & 4u) ? x[u].z : x[u].z * slope; x[u].w = (sw[u] & 8u) ? x[u].w : x[u].w * slope;
+      }
       a.x += v[u] * x[u].x; a.y += v[u] * x[u].y; a.z += v[u] * x[u].z; a.w += v[u] * x[u].w;
     }
   }
   return a;
+}
+
+// the plain product for a kernel whose xmask is nullable at run time: MASKED is chosen once, outside the gather loop
+template <int LPR>
+__device__ __forceinline__ float4 row_dot_xmask(const int *__restrict__ col, const float *__restrict__ val, const Seg2 &X,
+                                                int lo, int hi, int slot, int nslots, int q,
+                                                const uint32_t *__restrict__ xmask) {
+  return xmask ? row_dot<LPR, true, false>(col, val, X, lo, hi, slot, nslots, q, xmask)
+               : row_dot<LPR, false, false>(col, val, X, lo, hi, slot, nslots, q);
 }
 
 // mask[w] bit b = row 32 w + b of X has a non-zero element; a wave builds one word, RPP = min(32, 64 / LPR) rows per pass
@@ -123,59 +154,86 @@ __global__ __launch_bounds__(kBlock) void k_spmm_wave_rows(
   for (int it = wave0; it < n_items; it += nwaves) {
     const int row = rows ? rows[it] : it;
     const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, X, lo, hi, k, NPW, q);
+    float4 a = row_dot<LPR, false, false>(col, val, X, lo, hi, k, NPW, q);
     a = slot_sum<LPR>(a);
     if (k == 0) epilogue4(a, row, q, D, Y, acc_in, has_acc_in != 0, acc_out, scale);
   }
 }
 
+// ------------------------------------------------------------------------------------------------ the planned row walk ----
 // ONE launch of 1024-thread workgroups (16 waves): workgroups [0, n_long) each take a hub row
 // (16 x NPW neighbour slots stride the row, combined through LDS); the remaining workgroups give
 // every wave its own short row.  Hubs start first and overlap with the short rows instead of
 // serialising behind them as a second kernel.
+// A kernel is this walk plus two callables:
+//   dot(lo, hi, slot, nslots, q)   this lane's partial sum over the edges [lo, hi) of a row, as neighbour slot `slot` of `nslots`
+//   epi(sum, row, q, writer)       called by ALL lanes of the wave that holds the row's sum (an epilogue may shuffle); the
+//                                  `writer` lanes (k == 0) hold it for elements 4 q .. 4 q + 3 and store
 constexpr int kHubWaves = 16;
+
+// A hub row on a whole workgroup of WAVES waves; wave 0 adds the waves' sums in wave order, UNROLL additions per trip.
+// hub_need (nullable, one byte per row): a hub row is computed only when its byte is set (mi_batch_row_list sets it for
+// the hubs of the batch) and the byte is cleared again here, after the row's epilogue: the array is all zeros between launches
+template <int LPR, int WAVES, int UNROLL, class Dot, class Epi>
+__device__ __forceinline__ void hub_row(const int *__restrict__ crow, int row, uint8_t *__restrict__ hub_need, Dot dot, Epi epi) {
+  constexpr int NPW = kWave / LPR;
+  __shared__ float4 part[WAVES][LPR];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int q = lane % LPR, k = lane / LPR;
+  if (hub_need && !hub_need[row]) return;
+  const int lo = crow[row], hi = crow[row + 1];
+  float4 a = dot(lo, hi, w * NPW + k, NPW * WAVES, q);
+  a = slot_sum<LPR>(a);
+  if (k == 0) part[w][q] = a;
+  __syncthreads();
+  if (w == 0) {
+    float4 s = part[0][q];
+#pragma unroll UNROLL
+    for (int i = 1; i < WAVES; ++i) {
+      const float4 p = part[i][q];
+      s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+    }
+    epi(s, row, q, k == 0);
+  }
+  if (hub_need && threadIdx.x == 0) hub_need[row] = 0;
+}
+
+// short_rows nullable: the short rows are then 0 .. n_short - 1
+template <int LPR, int HUB_UNROLL, class Dot, class Epi>
+__device__ __forceinline__ void planned_rows(const int *__restrict__ crow, const int *__restrict__ short_rows, int n_short,
+                                             const int *__restrict__ long_rows, int n_long, uint8_t *__restrict__ hub_need,
+                                             Dot dot, Epi epi) {
+  constexpr int NPW = kWave / LPR;
+  if ((int)blockIdx.x < n_long) {
+    hub_row<LPR, kHubWaves, HUB_UNROLL>(crow, long_rows[blockIdx.x], hub_need, dot, epi);
+    return;
+  }
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int q = lane % LPR, k = lane / LPR;
+  const int nblk = gridDim.x - n_long;
+  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
+    const int row = short_rows ? short_rows[it] : it;
+    const int lo = crow[row], hi = crow[row + 1];
+    float4 a = dot(lo, hi, k, NPW, q);
+    a = slot_sum<LPR>(a);
+    epi(a, row, q, k == 0);
+  }
+}
+
 template <int LPR>
 __global__ __launch_bounds__(kHubWaves * kWave) void k_spmm_planned(
     const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 X,
     float *__restrict__ Y, Seg2 acc_in, int has_acc_in, float *__restrict__ acc_out, float scale,
     const int *__restrict__ short_rows, int n_short, const int *__restrict__ long_rows, int n_long,
     const uint32_t *__restrict__ xmask, uint8_t *__restrict__ hub_need) {
-  constexpr int NPW = kWave / LPR;
-  constexpr int D = LPR * 4;
-  __shared__ float4 part[kHubWaves][LPR];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int q = lane % LPR, k = lane / LPR;
-  if ((int)blockIdx.x < n_long) {
-    const int row = long_rows[blockIdx.x];
-    // hub_need (nullable, one byte per row): a hub row is computed only when its byte is set (mi_batch_row_list sets it for
-    // the hubs of the batch) and the byte is cleared again here: the array is all zeros between launches
-    if (hub_need && !hub_need[row]) return;
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, X, lo, hi, w * NPW + k, NPW * kHubWaves, q, xmask);
-    a = slot_sum<LPR>(a);
-    if (k == 0) part[w][q] = a;
-    __syncthreads();
-    if (w == 0 && k == 0) {
-      float4 s = part[0][q];
-#pragma unroll
-      for (int i = 1; i < kHubWaves; ++i) {
-        const float4 p = part[i][q];
-        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-      }
-      epilogue4(s, row, q, D, Y, acc_in, has_acc_in != 0, acc_out, scale);
-    }
-    if (hub_need && threadIdx.x == 0) hub_need[row] = 0;
-    return;
-  }
-  const int nblk = gridDim.x - n_long;
-  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
-    const int row = short_rows[it];
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, X, lo, hi, k, NPW, q, xmask);
-    a = slot_sum<LPR>(a);
-    if (k == 0) epilogue4(a, row, q, D, Y, acc_in, has_acc_in != 0, acc_out, scale);
-  }
+  planned_rows<LPR, kHubWaves>(
+      crow, short_rows, n_short, long_rows, n_long, hub_need,
+      [&](int lo, int hi, int slot, int nslots, int q) { return row_dot_xmask<LPR>(col, val, X, lo, hi, slot, nslots, q, xmask); },
+      [&](float4 y, int row, int q, bool writer) {
+        if (writer) epilogue4(y, row, q, LPR * 4, Y, acc_in, has_acc_in != 0, acc_out, scale);
+      });
 }
 
 
@@ -216,26 +274,16 @@ __global__ __launch_bounds__(kTaskWaves * kWave, 6) void k_spmm_sliced(
   constexpr int NPW = kWave / LPR;
   constexpr int D = LPR * 4;
   constexpr int U = 4;
-  __shared__ float4 part[kTaskWaves][LPR];
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int q = lane % LPR, k = lane / LPR;
   if ((int)blockIdx.x < n_long) {          // a hub row: the whole workgroup strides it
-    const int row = long_rows[blockIdx.x];
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, X, lo, hi, w * NPW + k, NPW * kTaskWaves, q, xmask);
-    a = slot_sum<LPR>(a);
-    if (k == 0) part[w][q] = a;
-    __syncthreads();
-    if (w == 0 && k == 0) {
-      float4 s = part[0][q];
-#pragma unroll
-      for (int i = 1; i < kTaskWaves; ++i) {
-        const float4 p = part[i][q];
-        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-      }
-      epilogue4(s, row, q, D, Y, acc_in, has_acc_in != 0, acc_out, scale);
-    }
+    hub_row<LPR, kTaskWaves, kTaskWaves>(
+        crow, long_rows[blockIdx.x], nullptr,
+        [&](int lo, int hi, int slot, int nslots, int q) { return row_dot_xmask<LPR>(col, val, X, lo, hi, slot, nslots, q, xmask); },
+        [&](float4 y, int row, int q, bool writer) {
+          if (writer) epilogue4(y, row, q, D, Y, acc_in, has_acc_in != 0, acc_out, scale);
+        });
     return;
   }
   const int nblk = gridDim.x - n_long;
@@ -396,8 +444,6 @@ __global__ __launch_bounds__(kBlock) void k_spmm_anyD(
   }
 }
 
-inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
-
 // ------------------------------------------------------------------------------------- HCCF layer (src/models/hccf.py:53-63) ----
 // With S = [U; I] and A = [[0, M], [M^T, 0]] (one dropout draw serves both blocks, so A is symmetric, values included) a layer is
 //   pre = A S;  S' = S + leaky(pre);  R' = (R + S') * scale
@@ -438,88 +484,12 @@ __global__ __launch_bounds__(kHubWaves * kWave) void k_hccf_fwd(
     const int *__restrict__ crow, const int *__restrict__ col, const float *__restrict__ val, Seg2 S,
     float *__restrict__ S_out, Seg2 R, float *__restrict__ R_out, float scale, float slope, uint32_t *__restrict__ bits,
     const int *__restrict__ short_rows, int n_short, const int *__restrict__ long_rows, int n_long) {
-  constexpr int NPW = kWave / LPR;
-  __shared__ float4 part[kHubWaves][LPR];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int q = lane % LPR, k = lane / LPR;
-  if ((int)blockIdx.x < n_long) {
-    const int row = long_rows[blockIdx.x];
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, S, lo, hi, w * NPW + k, NPW * kHubWaves, q);
-    a = slot_sum<LPR>(a);
-    if (k == 0) part[w][q] = a;
-    __syncthreads();
-    if (w == 0) {
-      float4 s = part[0][q];
-#pragma unroll
-      for (int i = 1; i < kHubWaves; ++i) {
-        const float4 p = part[i][q];
-        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-      }
-      hccf_fwd_epilogue<LPR>(s, row, q, k == 0, S, S_out, R, R_out, scale, slope, bits);
-    }
-    return;
-  }
-  const int nblk = gridDim.x - n_long;
-  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
-    const int row = short_rows ? short_rows[it] : it;
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot<LPR>(col, val, S, lo, hi, k, NPW, q);
-    a = slot_sum<LPR>(a);
-    hccf_fwd_epilogue<LPR>(a, row, q, k == 0, S, S_out, R, R_out, scale, slope, bits);
-  }
-}
-
-// row_dot with every gathered row scaled, element by element, by 1 or `slope` from the row's sign word
-template <int LPR, bool MASKED, bool SIGNED>
-__device__ __forceinline__ float4 row_dot_signed(const int *__restrict__ col, const float *__restrict__ val, const Seg2 &X,
-                                                 const uint32_t *__restrict__ bits, float slope, int lo, int hi, int slot,
-                                                 int nslots, int q, const uint32_t *__restrict__ xmask) {
-  constexpr int D = LPR * 4;
-  constexpr int W = (D + 31) / 32;
-  constexpr int U = 4;
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 a = z4;
-  for (int j0 = lo + slot; j0 < hi; j0 += nslots * U) {
-    int c[U];
-    float v[U];
-    float4 x[U];
-    uint32_t sw[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int j = j0 + u * nslots;
-      const bool ok = j < hi;
-      c[u] = ok ? col[j] : 0;
-      v[u] = ok ? val[j] : 0.f;
-    }
-    if (MASKED) {
-      uint32_t mw[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) mw[u] = xmask[c[u] >> 5];
-#pragma unroll
-      for (int u = 0; u < U; ++u) x[u] = ((mw[u] >> (c[u] & 31)) & 1u) ? ld4(seg_row(X, c[u], D) + q * 4) : z4;
-    } else {
-#pragma unroll
-      for (int u = 0; u < U; ++u) x[u] = ld4(seg_row(X, c[u], D) + q * 4);
-    }
-    if (SIGNED) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) sw[u] = bits[(int64_t)c[u] * W + (q >> 3)] >> ((q & 7) * 4);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (SIGNED) {
-        // one gathered row at a time: the empty statement ties x[u] to the sum so far.  Left to the scheduler, the 16
-        // products x * slope are all formed before the first select (30 more VGPRs, occupancy 6 instead of 8)
-        asm volatile("" : "+v"(x[u].x), "+v"(x[u].y), "+v"(x[u].z), "+v"(x[u].w), "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
-        x[u].x = (sw[u] & 1u) ? x[u].x : x[u].x * slope; x[u].y = (sw[u] & 2u) ? x[u].y : x[u].y * slope;
-        x[u].z = (sw[u] & 4u) ? x[u].z : x[u].z * slope; x[u].w = (sw[u] & 8u) ? x[u].w : x[u].w * slope;
-      }
-      a.x += v[u] * x[u].x; a.y += v[u] * x[u].y; a.z += v[u] * x[u].z; a.w += v[u] * x[u].w;
-    }
-  }
-  return a;
+  planned_rows<LPR, kHubWaves>(
+      crow, short_rows, n_short, long_rows, n_long, nullptr,
+      [&](int lo, int hi, int slot, int nslots, int q) { return row_dot<LPR, false, false>(col, val, S, lo, hi, slot, nslots, q); },
+      [&](float4 pre, int row, int q, bool writer) {
+        hccf_fwd_epilogue<LPR>(pre, row, q, writer, S, S_out, R, R_out, scale, slope, bits);
+      });
 }
 
 // out[row] = xscale (A[row, :] (G . f) + G[row]) + cg g[row]
@@ -538,38 +508,15 @@ __global__ __launch_bounds__(kHubWaves * kWave) void k_hccf_bwd(
     const uint32_t *__restrict__ bits, float slope, Seg2 g, float cg, float *__restrict__ out,
     const int *__restrict__ short_rows, int n_short, const int *__restrict__ long_rows, int n_long,
     const uint32_t *__restrict__ xmask) {
-  constexpr int NPW = kWave / LPR;
-  constexpr int D = LPR * 4;
-  __shared__ float4 part[kHubWaves][LPR];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int q = lane % LPR, k = lane / LPR;
-  if ((int)blockIdx.x < n_long) {
-    const int row = long_rows[blockIdx.x];
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot_signed<LPR, MASKED, SIGNED>(col, val, G, bits, slope, lo, hi, w * NPW + k, NPW * kHubWaves, q, xmask);
-    a = slot_sum<LPR>(a);
-    if (k == 0) part[w][q] = a;
-    __syncthreads();
-    if (w == 0 && k == 0) {
-      float4 s = part[0][q];
-#pragma unroll 4          // (fully unrolled, the 15 LDS reads and the epilogue's loads are all in flight at once: 70 VGPRs)
-      for (int i = 1; i < kHubWaves; ++i) {
-        const float4 p = part[i][q];
-        s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-      }
-      hccf_bwd_epilogue(s, row, q, D, G, xscale, g, cg, out);
-    }
-    return;
-  }
-  const int nblk = gridDim.x - n_long;
-  for (int it = (blockIdx.x - n_long) * kHubWaves + w; it < n_short; it += nblk * kHubWaves) {
-    const int row = short_rows ? short_rows[it] : it;
-    const int lo = crow[row], hi = crow[row + 1];
-    float4 a = row_dot_signed<LPR, MASKED, SIGNED>(col, val, G, bits, slope, lo, hi, k, NPW, q, xmask);
-    a = slot_sum<LPR>(a);
-    if (k == 0) hccf_bwd_epilogue(a, row, q, D, G, xscale, g, cg, out);
-  }
+  // hub sum unrolled by 4 (fully unrolled, the 15 LDS reads and the epilogue's loads are all in flight at once: 70 VGPRs)
+  planned_rows<LPR, 4>(
+      crow, short_rows, n_short, long_rows, n_long, nullptr,
+      [&](int lo, int hi, int slot, int nslots, int q) {
+        return row_dot<LPR, MASKED, SIGNED>(col, val, G, lo, hi, slot, nslots, q, xmask, bits, slope);
+      },
+      [&](float4 p, int row, int q, bool writer) {
+        if (writer) hccf_bwd_epilogue(p, row, q, LPR * 4, G, xscale, g, cg, out);
+      });
 }
 
 // any D: one wave per row, lane l takes columns l, l + 64, ...; a ballot of a 64-column trip is two sign words
@@ -627,6 +574,12 @@ __global__ __launch_bounds__(kBlock) void k_hccf_bwd_anyD(
   }
 }
 
+// workgroups of a planned launch: one per hub row, then 16 short rows per workgroup and trip
+inline int planned_grid(int n_short, int n_long) {
+  const int sb = (n_short + kHubWaves - 1) / kHubWaves;
+  return n_long + (sb > 1024 ? 1024 : sb);
+}
+
 }  // namespace
 
 extern "C" {
@@ -644,18 +597,12 @@ int mi_row_mask(const float *Xa, const float *Xb, int32_t x_split, int32_t n_row
   if (n_rows < 0 || D <= 0 || x_split < 0) return MI_ERR_INVALID_ARG;
   if (n_rows == 0) return MI_OK;
   if (!Xa || !mask) return MI_ERR_INVALID_ARG;
-  if (!vec_ok(D) || D > 256 || (D / 4 & (D / 4 - 1)) || !aligned16(Xa) || (Xb && !aligned16(Xb))) return MI_ERR_UNSUPPORTED;
-  Seg2 X{Xa, Xb ? Xb : Xa + (int64_t)x_split * D, Xb ? x_split : 0x7fffffff};
+  if (!vec_ok(D) || !all_aligned16(Xa, Xb)) return MI_ERR_UNSUPPORTED;
+  const Seg2 X = seg2(Xa, Xb, x_split);
   const int n_words = (n_rows + 31) / 32, grid = (n_words + kWavesPerBlock - 1) / kWavesPerBlock;
-  switch (D / 4) {
-    case 1: MI_LAUNCH("row_mask", k_row_mask<1>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    case 2: MI_LAUNCH("row_mask", k_row_mask<2>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    case 4: MI_LAUNCH("row_mask", k_row_mask<4>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    case 8: MI_LAUNCH("row_mask", k_row_mask<8>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    case 16: MI_LAUNCH("row_mask", k_row_mask<16>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    case 32: MI_LAUNCH("row_mask", k_row_mask<32>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-    default: MI_LAUNCH("row_mask", k_row_mask<64>, grid, kBlock, stream, X, n_rows, mask, n_words); break;
-  }
+#define CALL(LPR) MI_LAUNCH("row_mask", (k_row_mask<LPR>), grid, kBlock, stream, X, n_rows, mask, n_words)
+  MI_DISPATCH_LPR(D / 4, CALL)
+#undef CALL
   return launch_status();
 }
 
@@ -705,14 +652,11 @@ int mi_spmm_csr_sel(const int32_t *crow, const int32_t *col, const float *val, c
   if (n_rows == 0) return MI_OK;
   if (!crow || !Xa || (!Y && !acc_out)) return MI_ERR_INVALID_ARG;
   if ((n_short > 0 && !short_rows) || (n_long > 0 && !long_rows)) return MI_ERR_INVALID_ARG;
-  Seg2 X{Xa, Xb ? Xb : Xa + (int64_t)x_split * D, Xb ? x_split : 0x7fffffff};
+  const Seg2 X = seg2(Xa, Xb, x_split), A = seg2(acc_in_a, acc_in_b, acc_split);
   const int has_acc = acc_in_a != nullptr;
-  Seg2 A{acc_in_a, acc_in_b ? acc_in_b : acc_in_a, acc_in_b ? acc_split : 0x7fffffff};
   const bool planned = short_rows || long_rows;
   // (xmask only lets the planned float4 kernel skip fetches of all-zero rows; the other paths ignore it — same result)
-  const bool al = aligned16(Xa) && (!Xb || aligned16(Xb)) && (!Y || aligned16(Y)) &&
-                  (!acc_in_a || aligned16(acc_in_a)) && (!acc_in_b || aligned16(acc_in_b)) &&
-                  (!acc_out || aligned16(acc_out));
+  const bool al = all_aligned16(Xa, Xb, Y, acc_in_a, acc_in_b, acc_out);
   if (planned && n_long > 60000) return MI_ERR_UNSUPPORTED;
   if (vec_ok(D) && al) {
 #define CALL(LPR)                                                                                       \
@@ -721,23 +665,12 @@ int mi_spmm_csr_sel(const int32_t *crow, const int32_t *col, const float *val, c
       MI_LAUNCH("spmm_csr_rows", (k_spmm_wave_rows<LPR>), grid_for_waves(n_rows), kBlock, stream, crow, \
                 col, val, X, Y, A, has_acc, acc_out, scale, nullptr, n_rows);                           \
     } else {                                                                                            \
-      int sb = (n_short + kHubWaves - 1) / kHubWaves;                                                   \
-      if (sb > 1024) sb = 1024;                                                                         \
-      MI_LAUNCH("spmm_csr", (k_spmm_planned<LPR>), n_long + sb, kHubWaves * kWave, stream, crow, col,   \
-                val, X, Y, A, has_acc, acc_out, scale, short_rows, n_short, long_rows, n_long, xmask,   \
-                hub_need);                                                                              \
+      MI_LAUNCH("spmm_csr", (k_spmm_planned<LPR>), planned_grid(n_short, n_long), kHubWaves * kWave,    \
+                stream, crow, col, val, X, Y, A, has_acc, acc_out, scale, short_rows, n_short, long_rows, \
+                n_long, xmask, hub_need);                                                               \
     }                                                                                                   \
   } while (0)
-    switch (D / 4) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      case 64: CALL(64); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+    MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
   } else {
     MI_LAUNCH("spmm_csr_rows", k_spmm_anyD, grid_for_waves(n_rows), kBlock, stream, crow, col, val, X, Y, A,
@@ -756,28 +689,14 @@ int mi_hccf_fwd(const int32_t *crow, const int32_t *col, const float *val, const
   if (!crow || !Sa || !Ra || !R_out || S_out == Sa || (Sb && S_out == Sb)) return MI_ERR_INVALID_ARG;
   if ((n_short > 0 && !short_rows) || (n_long > 0 && !long_rows)) return MI_ERR_INVALID_ARG;
   if (n_long > 60000) return MI_ERR_UNSUPPORTED;
-  Seg2 S{Sa, Sb ? Sb : Sa + (int64_t)s_split * D, Sb ? s_split : 0x7fffffff};
-  Seg2 R{Ra, Rb ? Rb : Ra, Rb ? r_split : 0x7fffffff};
+  const Seg2 S = seg2(Sa, Sb, s_split), R = seg2(Ra, Rb, r_split);
   const bool planned = short_rows || long_rows;
   if (!planned) n_short = n_rows;
-  const bool al = aligned16(Sa) && (!Sb || aligned16(Sb)) && (!S_out || aligned16(S_out)) && aligned16(Ra) &&
-                  (!Rb || aligned16(Rb)) && aligned16(R_out);
-  if (vec_ok(D) && al) {
-    int sb = (n_short + kHubWaves - 1) / kHubWaves;
-    if (sb > 1024) sb = 1024;
+  if (vec_ok(D) && all_aligned16(Sa, Sb, S_out, Ra, Rb, R_out)) {
 #define CALL(LPR)                                                                                                         \
-  MI_LAUNCH("hccf_fwd", (k_hccf_fwd<LPR>), n_long + sb, kHubWaves * kWave, stream, crow, col, val, S, S_out, R, R_out, scale, \
-            slope, bits, short_rows, n_short, long_rows, n_long)
-    switch (D / 4) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      case 64: CALL(64); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+  MI_LAUNCH("hccf_fwd", (k_hccf_fwd<LPR>), planned_grid(n_short, n_long), kHubWaves * kWave, stream, crow, col, val, S, S_out, \
+            R, R_out, scale, slope, bits, short_rows, n_short, long_rows, n_long)
+    MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
   } else {
     MI_LAUNCH("hccf_fwd_rows", k_hccf_fwd_anyD, grid_for_waves(n_rows), kBlock, stream, crow, col, val, S, S_out, R, R_out,
@@ -796,18 +715,14 @@ int mi_hccf_bwd(const int32_t *crow, const int32_t *col, const float *val, const
   if (!crow || !Ga || !ga || !out || out == Ga || out == ga || (Gb && out == Gb) || (gb && out == gb)) return MI_ERR_INVALID_ARG;
   if ((n_short > 0 && !short_rows) || (n_long > 0 && !long_rows)) return MI_ERR_INVALID_ARG;
   if (n_long > 60000) return MI_ERR_UNSUPPORTED;
-  Seg2 G{Ga, Gb ? Gb : Ga + (int64_t)G_split * D, Gb ? G_split : 0x7fffffff};
-  Seg2 g{ga, gb ? gb : ga + (int64_t)g_split * D, gb ? g_split : 0x7fffffff};
+  const Seg2 G = seg2(Ga, Gb, G_split), g = seg2(ga, gb, g_split);
   const bool planned = short_rows || long_rows;
   if (!planned) n_short = n_rows;
   // (xmask only lets the float4 kernel skip fetches of all-zero rows; the generic path ignores it — same result)
-  const bool al = aligned16(Ga) && (!Gb || aligned16(Gb)) && aligned16(ga) && (!gb || aligned16(gb)) && aligned16(out);
-  if (vec_ok(D) && al) {
-    int sb = (n_short + kHubWaves - 1) / kHubWaves;
-    if (sb > 1024) sb = 1024;
+  if (vec_ok(D) && all_aligned16(Ga, Gb, ga, gb, out)) {
 #define CALL2(LPR, M, S)                                                                                                 \
-  MI_LAUNCH("hccf_bwd", (k_hccf_bwd<LPR, M, S>), n_long + sb, kHubWaves * kWave, stream, crow, col, val, G, xscale, bits, slope, \
-            g, cg, out, short_rows, n_short, long_rows, n_long, xmask)
+  MI_LAUNCH("hccf_bwd", (k_hccf_bwd<LPR, M, S>), planned_grid(n_short, n_long), kHubWaves * kWave, stream, crow, col, val, G, \
+            xscale, bits, slope, g, cg, out, short_rows, n_short, long_rows, n_long, xmask)
 #define CALL(LPR)                                                                                                        \
   do {                                                                                                                   \
     if (xmask && bits) CALL2(LPR, true, true);                                                                           \
@@ -815,16 +730,7 @@ int mi_hccf_bwd(const int32_t *crow, const int32_t *col, const float *val, const
     else if (bits) CALL2(LPR, false, true);                                                                              \
     else CALL2(LPR, false, false);                                                                                       \
   } while (0)
-    switch (D / 4) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 4: CALL(4); break;
-      case 8: CALL(8); break;
-      case 16: CALL(16); break;
-      case 32: CALL(32); break;
-      case 64: CALL(64); break;
-      default: return MI_ERR_UNSUPPORTED;
-    }
+    MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
 #undef CALL2
   } else {
@@ -847,12 +753,9 @@ int mi_spmm_tiled(const int32_t *tile_edge0, const int32_t *tile_row0, int32_t n
   if (!tile_edge0 || !tile_row0 || !ecr || !eval || !Xa || (!Y && !acc_out)) return MI_ERR_INVALID_ARG;
   const size_t lds = (size_t)max_tile_rows * D * sizeof(float);
   if (!vec_ok(D) || max_tile_rows > 512 || lds > 64 * 1024) return MI_ERR_UNSUPPORTED;      // 64 KiB: no opt-in needed
-  if (!aligned16(Xa) || (Xb && !aligned16(Xb)) || (Y && !aligned16(Y)) || (acc_in_a && !aligned16(acc_in_a)) ||
-      (acc_in_b && !aligned16(acc_in_b)) || (acc_out && !aligned16(acc_out)))
-    return MI_ERR_UNSUPPORTED;
-  Seg2 X{Xa, Xb ? Xb : Xa + (int64_t)x_split * D, Xb ? x_split : 0x7fffffff};
+  if (!all_aligned16(Xa, Xb, Y, acc_in_a, acc_in_b, acc_out)) return MI_ERR_UNSUPPORTED;
+  const Seg2 X = seg2(Xa, Xb, x_split), A = seg2(acc_in_a, acc_in_b, acc_split);
   const int has_acc = acc_in_a != nullptr;
-  Seg2 A{acc_in_a, acc_in_b ? acc_in_b : acc_in_a, acc_in_b ? acc_split : 0x7fffffff};
   hipEvent_t ea, eb;
   const bool timed = mi::prof_acquire("spmm_tiled", &ea, &eb);
 #define CALL(LPR)                                                                                                       \
@@ -864,16 +767,7 @@ int mi_spmm_tiled(const int32_t *tile_edge0, const int32_t *tile_row0, int32_t n
       hipLaunchKernelGGL((k_spmm_tiled<LPR>), dim3(ntiles), dim3(kTileThreads), lds, (hipStream_t)stream, tile_edge0,  \
                          tile_row0, ecr, eval, X, Y, A, has_acc, acc_out, scale);                                       \
   } while (0)
-  switch (D / 4) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    case 8: CALL(8); break;
-    case 16: CALL(16); break;
-    case 32: CALL(32); break;
-    case 64: CALL(64); break;
-    default: return MI_ERR_UNSUPPORTED;
-  }
+  MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
   return launch_status();
 }
@@ -894,27 +788,15 @@ int mi_spmm_sliced(const int32_t *crow, const int32_t *col, const float *val, co
   if (!Xa || (!Y && !acc_out) || (n_tasks > 0 && (!tptr || !trows || !twide || !ecol || !eval))) return MI_ERR_INVALID_ARG;
   if (n_long > 0 && (!long_rows || !crow || !col || !val)) return MI_ERR_INVALID_ARG;
   if (!vec_ok(D) || n_long > 60000) return MI_ERR_UNSUPPORTED;
-  if (!aligned16(Xa) || (Xb && !aligned16(Xb)) || (Y && !aligned16(Y)) || (acc_in_a && !aligned16(acc_in_a)) ||
-      (acc_in_b && !aligned16(acc_in_b)) || (acc_out && !aligned16(acc_out)))
-    return MI_ERR_UNSUPPORTED;
-  Seg2 X{Xa, Xb ? Xb : Xa + (int64_t)x_split * D, Xb ? x_split : 0x7fffffff};
+  if (!all_aligned16(Xa, Xb, Y, acc_in_a, acc_in_b, acc_out)) return MI_ERR_UNSUPPORTED;
+  const Seg2 X = seg2(Xa, Xb, x_split), A = seg2(acc_in_a, acc_in_b, acc_split);
   const int has_acc = acc_in_a != nullptr;
-  Seg2 A{acc_in_a, acc_in_b ? acc_in_b : acc_in_a, acc_in_b ? acc_split : 0x7fffffff};
   int tb = (n_tasks + kTaskWaves - 1) / kTaskWaves;
   if (tb > 4096) tb = 4096;
 #define CALL(LPR)                                                                                                            \
   MI_LAUNCH("spmm_sliced", (k_spmm_sliced<LPR>), n_long + tb, kTaskWaves * kWave, stream, crow, col, val, tptr, trows, twide, \
             ecol, eval, n_tasks, X, Y, A, has_acc, acc_out, scale, long_rows, n_long, xmask)
-  switch (D / 4) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    case 8: CALL(8); break;
-    case 16: CALL(16); break;
-    case 32: CALL(32); break;
-    case 64: CALL(64); break;
-    default: return MI_ERR_UNSUPPORTED;
-  }
+  MI_DISPATCH_LPR(D / 4, CALL)
 #undef CALL
   return launch_status();
 }

@@ -88,11 +88,15 @@ def _check(got, want, L, what):
         assert_close(di.double(), rdi, 1e-4, 1e-5, what + " dXi")
 
 
-@pytest.mark.parametrize("D", [4, 6, 40, 64, 256])      # 6 and 40: no float4 kernel takes them (the one-wave-per-row path)
-@pytest.mark.parametrize("L", [1, 2, 3])
-@pytest.mark.parametrize("slope", [0.5, 0.25])
+# D x L x slope for 4, 6, 40, 64 and 256 (6 and 40: no float4 kernel takes them, the one-wave-per-row path), and the other
+# float4 widths once each: a width is a template instantiation of its own
+_DYADIC_CASES = ([(D, L, slope) for slope in (0.5, 0.25) for L in (1, 2, 3) for D in (4, 6, 40, 64, 256)] +
+                 [(D, 1, 0.5) for D in (8, 16, 32, 128)])
+
+
+@pytest.mark.parametrize("D,L,slope", _DYADIC_CASES, ids=[f"{slope}-{L}-{D}" for D, L, slope in _DYADIC_CASES])
 def test_dyadic_fixture(D, L, slope):
-    assert _kernels._float4_rows(D) == (D in (4, 64, 256))
+    assert _kernels._float4_rows(D) == (D in (4, 8, 16, 32, 64, 128, 256))
     fx, want = _dyadic(D, L, slope)
     _check(_run(fx, slope, L), want, L, f"D={D} L={L} slope={slope}")
 

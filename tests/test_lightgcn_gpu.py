@@ -1,8 +1,11 @@
 """GPU parity of the LightGCN propagation (fused CSR SpMM kernels) vs the reference goldens and
 the oracle.  fp32; only the per-row summation order differs: rtol 1e-5 / atol 1e-6."""
+import functools
+
 import pytest
 import torch
 
+import hccf_helpers as hh
 from conftest import assert_close, golden_names, load_golden
 from oracle import reference_ops as ro
 
@@ -118,6 +121,44 @@ def test_propagate_vs_oracle(U, I, nnz, D, L, form, monkeypatch):
         assert plan.pattern_symmetric
         if U == 1500:
             assert plan.long_rows.numel() > 0, "test graph should contain hub rows"
+
+
+@functools.lru_cache(maxsize=None)
+def _dyadic_product(D):
+    """The 300 x 280 graph of hccf_helpers.dyadic_fixture(D, 1) (one hub user, one hub item, an isolated row on each side)
+    as LightGCN's square operand, with the float64 dense result of one layer, forward and backward; computed once per
+    width and shared, never modified.  Tables and gradients are odd sixteenths, the nonzeros are from {0, 0.5, 1, 2}:
+    every term is a multiple of 1 / 32 below 2 and a row has at most 270 of them, so every partial sum is a multiple of
+    1 / 32 below 2^10 (15 bits) and the layer mean halves it: exact in float32 in ANY summation order, at every width."""
+    fx = hh.dyadic_fixture(D, 1)
+    U, (ii, v) = fx["U"], (fx["idx"], fx["vals"][0])
+    A = hh.block_adjacency(ii, v, U, fx["I"])                          # float64, symmetric
+    S, g = torch.cat([fx["Xu"], fx["Xi"]]).double(), torch.cat([fx["gu"], fx["gi"]]).double()
+    out, dS = (S + A @ S) / 2, (g + A.t() @ g) / 2
+    for x, y in ((S, out), (g, dS)):                                   # the claim, the way assert_dyadic_exact checks its own
+        assert torch.equal(((x.float() + A.float() @ x.float()) / 2).double(), y)
+        assert torch.equal(((x + A.flip(1) @ x.flip(0)) / 2).float().double(), y)
+    # the CSR keeps the nonzeros whose dropout factor is 0 as explicit zeros: the hubs stay hubs
+    ind = torch.cat([torch.stack([ii[0], ii[1] + U]), torch.stack([ii[1] + U, ii[0]])], 1)
+    adj = torch.sparse_coo_tensor(ind, torch.cat([v, v]), A.shape).coalesce().to_sparse_csr()
+    return fx, adj, out, dS
+
+
+@pytest.mark.parametrize("D", [4, 8, 16, 32, 64, 128, 256])
+def test_every_float4_width_with_a_hub_row_is_exact(D):
+    """All seven widths of the float4 kernels (the other tests reach 16 and 64 only), each with a hub row, an empty row and
+    ordinary rows, two-segment tables, forward and backward: equal to the float64 dense product bit for bit."""
+    assert _kernels._float4_rows(D)
+    fx, adj, out, dS = _dyadic_product(D)
+    adj = adj.to(DEV)
+    plan = _kernels.csr_plan(adj)
+    assert plan.long_rows.numel() == 2 and plan.pattern_symmetric
+    U = fx["U"]
+    Xu, Xi = fx["Xu"].to(DEV).requires_grad_(True), fx["Xi"].to(DEV).requires_grad_(True)
+    ou, oi = _kernels.lightgcn_propagate(adj, Xu, Xi, 1)
+    assert torch.equal(ou.detach().cpu().double(), out[:U]) and torch.equal(oi.detach().cpu().double(), out[U:])
+    torch.autograd.backward((ou, oi), (fx["gu"].to(DEV), fx["gi"].to(DEV)))
+    assert torch.equal(Xu.grad.cpu().double(), dS[:U]) and torch.equal(Xi.grad.cpu().double(), dS[U:])
 
 
 def test_nonsymmetric_values_use_true_transpose():
