@@ -10,6 +10,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
+from . import losses as _losses      # (the kept ticket workspaces; it imports this module in turn: neither uses the other at import)
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -1027,6 +1028,26 @@ class LightGCNPropagate(torch.autograd.Function):
         return None, gX[: ctx.split], gX[ctx.split:], None, None
 
 
+def rowsq_fwd(U, ui, P, pi, Nn, ni) -> torch.Tensor:
+    """mi_rowsq_fwd[_armed] on checked operands (fp32 contiguous [*, D] tables, int64 [B] indices): the [1] result."""
+    lib, dev, B = _lib.load(), U.device, ui.numel()
+    ws, armed = _losses._ticket_workspace("rowsq", dev, lib.mi_bpr_workspace_elems(B))
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.check((lib.mi_rowsq_fwd_armed if armed else lib.mi_rowsq_fwd)(
+        U.data_ptr(), ui.data_ptr(), P.data_ptr(), pi.data_ptr(), Nn.data_ptr(), ni.data_ptr(), B, U.shape[1], U.shape[0],
+        P.shape[0], Nn.shape[0], _lib.err_word(dev).data_ptr(), ws.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev)),
+        "mi_rowsq_fwd")
+    return out
+
+
+def rowsq_bwd(U, ui, P, pi, Nn, ni, g, dU, dP, dN) -> None:
+    """mi_rowsq_bwd: g[0] * row / B added (float atomics) into the given gradients, each of them optional."""
+    _lib.check(_lib.load().mi_rowsq_bwd(
+        U.data_ptr(), ui.data_ptr(), P.data_ptr(), pi.data_ptr(), Nn.data_ptr(), ni.data_ptr(), ui.numel(), U.shape[1],
+        U.shape[0], P.shape[0], Nn.shape[0], g.data_ptr(), _lib.ptr(dU), _lib.ptr(dP), _lib.ptr(dN),
+        _lib.stream_ptr(g.device)), "mi_rowsq_bwd")
+
+
 class LightGCNPropagateReg(torch.autograd.Function):
     """LightGCNPropagate of plain tables AND get_reg_loss over a batch's rows of those tables
     (src/models/lightgcn.py:79-100,166-173) as one node: (res_a, res_b, reg) for two tables, (res, reg) for one table
@@ -1037,7 +1058,7 @@ class LightGCNPropagateReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, val, Xa, Xb, plan, num_layers: int, users, pos, neg, batch_rows_only: bool = False, item_base: int = 0):
-        dev = _lib.require_gpu(val, Xa, Xb, users)
+        _lib.require_gpu(val, Xa, Xb, users)
         if val.requires_grad:
             raise NotImplementedError("gradients w.r.t. the adjacency values are not provided")
         valc, Xac = _f32c(val), _f32c(Xa)
@@ -1046,24 +1067,16 @@ class LightGCNPropagateReg(torch.autograd.Function):
         if n != plan.shape[0] or plan.shape[0] != plan.shape[1]:
             raise ValueError(f"adjacency is {plan.shape} but the embedding tables have {n} rows")
         ui, pi, ni = (_i64c(t).view(-1) for t in (users, pos, neg))
-        B, D = ui.numel(), Xac.shape[1]
+        B = ui.numel()
         if pi.numel() != B or ni.numel() != B or B == 0:
             raise ValueError("reg loss: users / positives / negatives must be [B] indices")
-        lib = _lib.load()
         if Xbc is None:              # one table: the item rows start at item_base
             item_tab, pr, nr = Xac, pi + item_base, ni + item_base
         else:
             item_tab, pr, nr, item_base = Xbc, pi, ni, Xac.shape[0]
         last_rows = (ui, pi, ni, item_base) if batch_rows_only else None
         res = _propagate(plan, False, valc, Xac, Xbc, num_layers, last_rows=last_rows)
-        from .losses import _ticket_workspace
-
-        ws, armed = _ticket_workspace("rowsq", dev, lib.mi_bpr_workspace_elems(B))
-        reg = torch.empty(1, dtype=torch.float32, device=dev)
-        _lib.check((lib.mi_rowsq_fwd_armed if armed else lib.mi_rowsq_fwd)(Xac.data_ptr(), ui.data_ptr(), item_tab.data_ptr(), pr.data_ptr(), item_tab.data_ptr(),
-                                    nr.data_ptr(), B, D, Xac.shape[0], item_tab.shape[0], item_tab.shape[0],
-                                    _lib.err_word(dev).data_ptr(), ws.data_ptr(), reg.data_ptr(), _lib.stream_ptr(dev)),
-                   "mi_rowsq_fwd")
+        reg = rowsq_fwd(Xac, ui, item_tab, pr, item_tab, nr)
         ctx.plan, ctx.num_layers = plan, num_layers
         ctx.split = None if Xbc is None else Xac.shape[0]
         ctx.save_for_backward(valc, Xac, item_tab, ui, pr, nr)
@@ -1093,11 +1106,7 @@ class LightGCNPropagateReg(torch.autograd.Function):
                 gX = _propagate(plan, True, val_t, ga, gb, ctx.num_layers, sparse_input=True)
             gXa, gXb = gX[:split], gX[split:]
         if greg is not None:
-            g = _f32c(greg).view(1)
-            _lib.check(_lib.load().mi_rowsq_bwd(Xac.data_ptr(), ui.data_ptr(), item_tab.data_ptr(), pr.data_ptr(),
-                                                item_tab.data_ptr(), nr.data_ptr(), ui.numel(), D, Xac.shape[0],
-                                                item_tab.shape[0], item_tab.shape[0], g.data_ptr(), gXa.data_ptr(),
-                                                gXb.data_ptr(), gXb.data_ptr(), _lib.stream_ptr(dev)), "mi_rowsq_bwd")
+            rowsq_bwd(Xac, ui, item_tab, pr, item_tab, nr, _f32c(greg).view(1), gXa, gXb, gXb)
         if split is None:
             return None, gX, None, None, None, None, None, None, None, None
         return None, gXa, gXb, None, None, None, None, None, None, None

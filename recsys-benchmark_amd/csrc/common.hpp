@@ -35,6 +35,9 @@ __host__ __device__ inline bool aligned16(const void *p) { return (reinterpret_c
 
 // the row widths of the float4 kernels: a row of D floats is LPR = D / 4 lanes x float4, LPR one of 1, 2, 4 .. 64
 inline bool vec_ok(int D) { return D >= 4 && D <= 256 && (D & 3) == 0 && ((D >> 2) & ((D >> 2) - 1)) == 0; }
+// every pointer of the list is 16-byte aligned (a null one, i.e. an operand that is not given, passes)
+template <class... P>
+inline bool all_aligned16(const P *...p) { return (aligned16(p) && ...); }
 
 // ---- device helpers ----------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
@@ -71,19 +74,69 @@ __device__ __forceinline__ void st4_nt(float *p, float4 v) {
 }
 
 // "last workgroup sums the partials" without agent-scope fences (on gfx950 a __threadfence() is an L2 write-back +
-// invalidate per workgroup: the loss kernels took 13 us with it).  ONE lane per workgroup publishes: the partial travels
-// as a device-scope (sc1, write-through) store, an explicit `s_waitcnt vmcnt(0)` holds the lane until that store has
+// invalidate per workgroup: the loss kernels took 13 us with it).  ONE lane per workgroup publishes: the partials travel
+// as device-scope (sc1, write-through) stores, an explicit `s_waitcnt vmcnt(0)` holds the lane until those stores have
 // been acknowledged by the coherence point behind the per-XCD L2s, and only then is the ticket taken (a workgroup-scope
 // fence emits NO wait between the store and the atomic — checked in the .s — so the two, at different addresses, could
 // be observed out of order).  The workgroup whose ticket came back last reads the partials with sc1 loads after its
 // atomic has returned, behind a workgroup barrier (MI355X_MICROARCH.md, hand-offs measured with sc1 loads, row 1).
-__device__ __forceinline__ void publish_partial(float *part, unsigned *ticket, float s, bool &last) {
-  __hip_atomic_store(part + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+// These launches run up to kMaxGrid / 256 = 8 workgroups per CU, while that measured row says "one per CU".
+//
+// block_sum: v[i] summed over the workgroup, valid in thread 0 (wave sums, then thread 0 adds the waves in order).
+// All NV wave sums come before the one masked LDS write, so that their cross-lane chains interleave.
+template <int NV>
+__device__ __forceinline__ void block_sum(float (&v)[NV], float (&red)[NV][kWavesPerBlock]) {
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[i][threadIdx.x >> 6] = v[i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      v[i] = 0.f;
+      for (int j = 0; j < kWavesPerBlock; ++j) v[i] += red[i][j];
+    }
+  }
 }
-__device__ __forceinline__ float read_partial(const float *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
+// block_join: thread 0 holds the workgroup's NV totals in v.  They go to part[NV * blockIdx.x + i]; the last workgroup
+// to arrive adds all of them in index order (a fixed summation tree: deterministic), its thread 0 runs
+// finish(const float (&total)[NV]) and re-arms the ticket (zero on entry, zero again on exit) for the next launch.
+template <int NV, class Finish>
+__device__ __forceinline__ void block_join(float (&v)[NV], float (&red)[NV][kWavesPerBlock], float *part, unsigned *ticket,
+                                           Finish finish) {
+  __shared__ bool last;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      __hip_atomic_store(part + NV * blockIdx.x + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = 0.f;
+  for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] += __hip_atomic_load(part + NV * j + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  block_sum(v, red);
+  if (threadIdx.x == 0) {
+    finish(v);
+    *ticket = 0;
+  }
+}
+
+// grid_join: every thread's NV accumulators in, finish(totals over the whole grid) out
+template <int NV, class Finish>
+__device__ __forceinline__ void grid_join(float (&v)[NV], float *part, unsigned *ticket, Finish finish) {
+  __shared__ float red[NV][kWavesPerBlock];
+  block_sum(v, red);
+  block_join(v, red, part, ticket, finish);
 }
 
 }  // namespace mi

@@ -65,10 +65,9 @@ __global__ __launch_bounds__(kBlock) void k_lse_diag_fwd(const float *__restrict
                                                          float *__restrict__ lse, float *__restrict__ part,
                                                          unsigned *ticket, float *__restrict__ loss) {
   __shared__ MaxSum red[kWavesPerBlock];
-  __shared__ float redf[kWavesPerBlock];
-  __shared__ bool last;
+  __shared__ float redf[1][kWavesPerBlock];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float term = 0.f;                            // thread 0: this workgroup's sum of (lse_i - s_ii)
+  float term[1] = {0.f};                       // thread 0: this workgroup's sum of (lse_i - s_ii)
   // a few hundred workgroups walk the rows: one ticket per workgroup, not per row (same-address atomics serialise)
   for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
     if (valid && !valid[row]) {                  // workgroup-uniform
@@ -123,25 +122,12 @@ __global__ __launch_bounds__(kBlock) void k_lse_diag_fwd(const float *__restrict
       for (int j = 1; j < kWavesPerBlock; ++j) t = ms_merge(t, red[j]);
       const float l = t.mx + logf(t.sum);
       lse[row] = l;
-      term += l - s[row] * inv_t;
+      term[0] += l - s[row] * inv_t;
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) publish_partial(part, ticket, term, last);
-  __syncthreads();
-  if (last) {                                  // fixed summation order over the rows: deterministic
-    float t = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) t += read_partial(part + j);
-    t = wave_sum(t);
-    if (lane == 0) redf[wv] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float u = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) u += redf[j];
-      loss[0] = u / (count ? count[0] : (float)n);
-      *ticket = 0;
-    }
-  }
+  // fixed summation order over the workgroups' terms: deterministic
+  block_join(term, redf, part, ticket, [&](const float (&t)[1]) { loss[0] = t[0] / (count ? count[0] : (float)n); });
 }
 
 // S[i, j] <- g/n/T * (exp(S[i, j]/T - lse_i) - [i == j])

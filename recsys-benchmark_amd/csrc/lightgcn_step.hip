@@ -10,18 +10,33 @@
 //
 // Ordering of the top-k: score descending, ties by ascending item index (a strict total order, so
 // the result does not depend on scheduling).
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace {
 using namespace mi;
 
-// row counts of the three tables the index arrays address, and the sticky error word (common convention of the lookups:
-// an out-of-range id never touches memory, it is skipped and MI_IDX_OUT_OF_RANGE is OR-ed into *err)
-struct RowBounds {
-  int64_t nU, nP, nN;
+// The batch's (user, positive, negative) triples: three tables with their row counts, the index arrays (NULL = row b; the
+// host allows that for BPR only, see rows<Nullable>) and the sticky error word (common convention of the lookups: an out-of-range id never
+// touches memory, it is skipped and MI_IDX_OUT_OF_RANGE is OR-ed into *err).
+struct Triples {
+  const float *U;
+  const int64_t *ui;
+  const float *P;
+  const int64_t *pi;
+  const float *Nn;
+  const int64_t *ni;
+  int64_t B, nU, nP, nN;
+  int D;
   int *err;
-  __device__ __forceinline__ bool ok(int64_t u, int64_t p, int64_t n) const {
-    return (uint64_t)u < (uint64_t)nU && (uint64_t)p < (uint64_t)nP && (uint64_t)n < (uint64_t)nN;
+  // the table rows of triple b; false when one of them lies outside its table (Nullable: the loss is one whose index
+  // arrays may be NULL; the other pays no test for it)
+  template <bool Nullable>
+  __device__ __forceinline__ bool rows(int64_t b, int64_t &ur, int64_t &pr, int64_t &nr) const {
+    if constexpr (Nullable) ur = ui ? ui[b] : b, pr = pi ? pi[b] : b, nr = ni ? ni[b] : b;
+    else ur = ui[b], pr = pi[b], nr = ni[b];
+    return (uint64_t)ur < (uint64_t)nU && (uint64_t)pr < (uint64_t)nP && (uint64_t)nr < (uint64_t)nN;
   }
 };
 
@@ -29,145 +44,112 @@ __device__ __forceinline__ float softplus(float x) {   // log(1 + e^x), stable
   return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
 }
 
-// 16 lanes (one float4 each) per sample when D == 64; generic D: lanes stride over d.
-// part[blockIdx.x] = sum over the block's samples of softplus(-(u.p - u.n)); the last block to finish
-// adds the partials in index order (deterministic) and writes the mean.
-__global__ __launch_bounds__(kBlock) void k_bpr_fwd(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, float *__restrict__ sig, float *__restrict__ part, unsigned *ticket,
-    float *__restrict__ loss, const float *__restrict__ plus, float plus_w) {
-  __shared__ float red[kWavesPerBlock];
-  __shared__ bool last;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+// The forward walk over the triples, in two lane mappings:
+//   LPR > 0: rows of D = 4 LPR floats (LPR a power of two <= 64, 16-byte aligned tables): LPR lanes x float4 per sample,
+//            64 / LPR samples per wave side by side.  A quarter of the workgroups of the other form at D = 64 — the launch
+//            is a chain of round trips (ids, rows, partial, ticket, partials) and the ticket is ONE word every workgroup
+//            adds to: same-address atomics serialise at ~26 ns apiece, 512 of them were most of the kernel's 10 us.
+//   LPR = 0: any D, a wave per sample, lanes stride over d.
+// The loss is a small type:
+//   term(u, p, n)  the summand of one element (float) or of one lane's four (float4);
+//   kNullable      whether its index arrays may be NULL;
+//   kPerSample     true: the terms of a sample are summed over its lanes to d — an out-of-range triple reads nothing and
+//                  counts as u = p = n = 0, d = 0 — and the sample's first lane accumulates epi(b, d);
+//                  false: no per-sample step, every lane accumulates its own terms across samples and an out-of-range
+//                  triple is skipped.
+// Returns the lane's accumulator.
+template <int LPR, class Loss>
+__device__ __forceinline__ float walk_triples(const Triples &t, const Loss &loss) {
+  constexpr int SPW = LPR ? kWave / LPR : 1;
+  const int lane = threadIdx.x & 63, q = LPR ? lane % LPR : lane, k = LPR ? lane / LPR : 0;
+  const int64_t step = (int64_t)gridDim.x * kWavesPerBlock * SPW;
   float acc = 0.f;
   bool bad = false;
-  const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + wv;
-  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t b = wave0; b < B; b += nwaves) {
-    const int64_t ur = ui ? ui[b] : b, pr = pi ? pi[b] : b, nr = ni ? ni[b] : b;
-    float d = 0.f;
-    if (nb.ok(ur, pr, nr)) {               // an out-of-range triple reads nothing and counts as u = p = n = 0
-      const float *u = U + ur * D, *p = P + pr * D, *q = Nn + nr * D;
-      for (int j = lane; j < D; j += kWave) d += u[j] * (p[j] - q[j]);
+  for (int64_t b0 = ((int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * SPW; b0 < t.B; b0 += step) {
+    const int64_t b = b0 + k;
+    const bool valid = b < t.B;
+    int64_t ur, pr, nr;
+    const bool ok = valid && t.rows<Loss::kNullable>(b, ur, pr, nr);
+    bad |= valid && !ok;
+    float d = Loss::kPerSample ? 0.f : acc;      // the sum the terms go to: this sample's own, or the lane's running one
+    if (ok) {
+      const float *u = t.U + ur * t.D, *p = t.P + pr * t.D, *n = t.Nn + nr * t.D;
+      if constexpr (LPR != 0) d += loss.term(ld4(u + q * 4), ld4(p + q * 4), ld4(n + q * 4));
+      else for (int j = lane; j < t.D; j += kWave) d += loss.term(u[j], p[j], n[j]);
+    }
+    if constexpr (Loss::kPerSample) {
+      if constexpr (LPR != 0) {
+#pragma unroll
+        for (int m = 1; m < LPR; m <<= 1) d += __shfl_xor(d, m);
+      } else {
+        d = wave_sum(d);
+      }
+      if (q == 0 && valid) acc += loss.epi(b, d);
     } else {
-      bad = true;
-    }
-    d = wave_sum(d);                       // y_pos - y_neg
-    if (lane == 0) {
-      sig[b] = 1.f / (1.f + expf(d));      // sigmoid(-d) = -dL_b/dd
-      acc += softplus(-d);                 // -logsigmoid(d)
+      acc = d;
     }
   }
-  if (bad && lane == 0 && nb.err) atomicOr(nb.err, MI_IDX_OUT_OF_RANGE);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) s += red[j];
-    publish_partial(part, ticket, s, last);
-  }
-  __syncthreads();
-  if (last) {                              // fixed summation tree over the partials: deterministic
-    float s = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) s += read_partial(part + j);
-    s = wave_sum(s);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) t += red[j];
-      // plus (nullable): another term of the step's objective (the trainer's reg_weight * get_reg_loss, a scalar an earlier
-      // launch wrote) joins here instead of through a scale launch and an add launch
-      loss[0] = t / (float)B + (plus ? plus_w * plus[0] : 0.f);
-      if (plus) loss[1] = t / (float)B;      // (the bare BPR term beside the sum: what a trainer logs)
-      *ticket = 0;                         // re-armed for the next launch
-    }
-  }
+  if (__any(bad) && lane == 0 && t.err) atomicOr(t.err, MI_IDX_OUT_OF_RANGE);
+  return acc;
 }
 
-// The same for rows of D = 4 LPR floats (LPR a power of two <= 64, 16-byte aligned tables): LPR lanes x float4 per sample,
-// 64 / LPR samples per wave side by side.  A quarter of the workgroups of the form above at D = 64 — the launch is a chain
-// of round trips (ids, rows, partial, ticket, partials) and the ticket is ONE word every workgroup adds to: same-address
-// atomics serialise at ~26 ns apiece, 512 of them were most of the kernel's 10 us.
+// BPR: d = u . (p - n) = y_pos - y_neg per sample; sig[b] = sigmoid(-d) = -dL_b/dd; loss = mean_b -logsigmoid(d).
+// part[blockIdx.x] = the workgroup's sum, joined by the last workgroup (grid_join).
+// plus (nullable): another term of the step's objective (the trainer's reg_weight * get_reg_loss, a scalar an earlier
+// launch wrote) joins in the last workgroup instead of through a scale launch and an add launch; loss[1] is then the bare
+// BPR term beside the sum (what a trainer logs).
+struct Bpr {
+  static constexpr bool kNullable = true, kPerSample = true;
+  float *sig;
+  __device__ float term(float u, float p, float n) const { return u * (p - n); }
+  __device__ float term(float4 u, float4 p, float4 n) const {
+    return u.x * (p.x - n.x) + u.y * (p.y - n.y) + u.z * (p.z - n.z) + u.w * (p.w - n.w);
+  }
+  __device__ float epi(int64_t b, float d) const {
+    sig[b] = 1.f / (1.f + expf(d));
+    return softplus(-d);
+  }
+};
+
 template <int LPR>
-__global__ __launch_bounds__(kBlock) void k_bpr_fwd_v(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, float *__restrict__ sig, float *__restrict__ part, unsigned *ticket,
-    float *__restrict__ loss, const float *__restrict__ plus, float plus_w) {
-  constexpr int SPW = kWave / LPR;
-  __shared__ float red[kWavesPerBlock];
-  __shared__ bool last;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int q = lane % LPR, k = lane / LPR;
-  float acc = 0.f;
-  bool bad = false;
-  const int64_t step = (int64_t)gridDim.x * kWavesPerBlock * SPW;
-  for (int64_t b0 = ((int64_t)blockIdx.x * kWavesPerBlock + wv) * SPW; b0 < B; b0 += step) {
-    const int64_t b = b0 + k;
-    const bool valid = b < B;
-    const int64_t ur = !valid ? 0 : (ui ? ui[b] : b), pr = !valid ? 0 : (pi ? pi[b] : b), nr = !valid ? 0 : (ni ? ni[b] : b);
-    float d = 0.f;
-    if (valid && nb.ok(ur, pr, nr)) {
-      const float4 u = ld4(U + ur * D + q * 4), p = ld4(P + pr * D + q * 4), n = ld4(Nn + nr * D + q * 4);
-      d = u.x * (p.x - n.x) + u.y * (p.y - n.y) + u.z * (p.z - n.z) + u.w * (p.w - n.w);
-    } else if (valid) {
-      bad = true;                          // (an out-of-range triple reads nothing and counts as u = p = n = 0)
-    }
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) d += __shfl_xor(d, m);
-    if (q == 0 && valid) {
-      sig[b] = 1.f / (1.f + expf(d));
-      acc += softplus(-d);
-    }
-  }
-  if (__any(bad) && lane == 0 && nb.err) atomicOr(nb.err, MI_IDX_OUT_OF_RANGE);
-  acc = wave_sum(acc);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) s += red[j];
-    publish_partial(part, ticket, s, last);
-  }
-  __syncthreads();
-  if (last) {
-    float s = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) s += read_partial(part + j);
-    s = wave_sum(s);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) t += red[j];
-      loss[0] = t / (float)B + (plus ? plus_w * plus[0] : 0.f);
-      if (plus) loss[1] = t / (float)B;
-      *ticket = 0;
-    }
-  }
+__device__ __forceinline__ void bpr_fwd(const Triples &t, float *sig, float *part, unsigned *ticket, float *loss,
+                                        const float *plus, float plus_w) {
+  float acc[1] = {walk_triples<LPR>(t, Bpr{sig})};
+  grid_join(acc, part, ticket, [&](const float (&s)[1]) {
+    loss[0] = s[0] / (float)t.B + (plus ? plus_w * plus[0] : 0.f);
+    if (plus) loss[1] = s[0] / (float)t.B;
+  });
+}
+
+__global__ __launch_bounds__(kBlock) void k_bpr_fwd(Triples t, float *__restrict__ sig, float *__restrict__ part,
+                                                    unsigned *ticket, float *__restrict__ loss,
+                                                    const float *__restrict__ plus, float plus_w) {
+  bpr_fwd<0>(t, sig, part, ticket, loss, plus, plus_w);
+}
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void k_bpr_fwd_v(Triples t, float *__restrict__ sig, float *__restrict__ part,
+                                                      unsigned *ticket, float *__restrict__ loss,
+                                                      const float *__restrict__ plus, float plus_w) {
+  bpr_fwd<LPR>(t, sig, part, ticket, loss, plus, plus_w);
 }
 
 // dU[ui[b]] += c (p - n), dP[pi[b]] += c u, dN[ni[b]] -= c u with c = -g * sig[b] / B
 // (float atomics when an index array is given — rows repeat —, plain stores otherwise)
-__global__ __launch_bounds__(kBlock) void k_bpr_bwd(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, const float *__restrict__ sig, const float *__restrict__ g,
-    float *__restrict__ dU, float *__restrict__ dP, float *__restrict__ dN) {
-  const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kBlock) void k_bpr_bwd(Triples t, const float *__restrict__ sig, const float *__restrict__ g,
+                                                    float *__restrict__ dU, float *__restrict__ dP, float *__restrict__ dN) {
+  const int lane = threadIdx.x & 63, D = t.D;
   const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  const float scale = -g[0] / (float)B;
-  for (int64_t b = wave0; b < B; b += nwaves) {
-    const int64_t ur = ui ? ui[b] : b, pr = pi ? pi[b] : b, nr = ni ? ni[b] : b;
-    if (!nb.ok(ur, pr, nr)) continue;      // flagged by the forward; nothing is read or added out of bounds
+  const float scale = -g[0] / (float)t.B;
+  for (int64_t b = wave0; b < t.B; b += nwaves) {
+    int64_t ur, pr, nr;
+    if (!t.rows<Bpr::kNullable>(b, ur, pr, nr)) continue;  // flagged by the forward; nothing is read or added out of bounds
     const float c = scale * sig[b];
     for (int j = lane; j < D; j += kWave) {
-      const float u = U[ur * D + j], p = P[pr * D + j], q = Nn[nr * D + j];
-      if (dU) { if (ui) atomicAdd(dU + ur * D + j, c * (p - q)); else dU[ur * D + j] = c * (p - q); }
-      if (dP) { if (pi) atomicAdd(dP + pr * D + j, c * u); else dP[pr * D + j] = c * u; }
-      if (dN) { if (ni) atomicAdd(dN + nr * D + j, -c * u); else dN[nr * D + j] = -c * u; }
+      const float u = t.U[ur * D + j], p = t.P[pr * D + j], q = t.Nn[nr * D + j];
+      if (dU) { if (t.ui) atomicAdd(dU + ur * D + j, c * (p - q)); else dU[ur * D + j] = c * (p - q); }
+      if (dP) { if (t.pi) atomicAdd(dP + pr * D + j, c * u); else dP[pr * D + j] = c * u; }
+      if (dN) { if (t.ni) atomicAdd(dN + nr * D + j, -c * u); else dN[nr * D + j] = -c * u; }
     }
   }
 }
@@ -176,110 +158,41 @@ __global__ __launch_bounds__(kBlock) void k_bpr_bwd(
 //   reg = ( ||U[ui]||_F^2 + ||P[pi]||_F^2 + ||Nn[ni]||_F^2 ) / (2 B)
 // (x.norm(2).pow(2) of the three gathered [B, D] blocks): gathers, squares and the deterministic mean-style join in
 // one launch; backward dU[ui[b]] += g * U[ui[b]] / B etc. (float atomics into caller-zeroed dense gradients).
-__global__ __launch_bounds__(kBlock) void k_rowsq_fwd(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, float *__restrict__ part, unsigned *ticket, float *__restrict__ out) {
-  __shared__ float red[kWavesPerBlock];
-  __shared__ bool last;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float acc = 0.f;
-  bool bad = false;
-  const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + wv;
-  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t b = wave0; b < B; b += nwaves) {
-    const int64_t ur = ui[b], pr = pi[b], nr = ni[b];
-    if (!nb.ok(ur, pr, nr)) { bad = true; continue; }
-    const float *u = U + ur * D, *p = P + pr * D, *q = Nn + nr * D;
-    for (int j = lane; j < D; j += kWave) acc += u[j] * u[j] + p[j] * p[j] + q[j] * q[j];
-  }
-  if (bad && lane == 0 && nb.err) atomicOr(nb.err, MI_IDX_OUT_OF_RANGE);
-  acc = wave_sum(acc);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) s += red[j];
-    publish_partial(part, ticket, s, last);
-  }
-  __syncthreads();
-  if (last) {
-    float s = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) s += read_partial(part + j);
-    s = wave_sum(s);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) t += red[j];
-      out[0] = t / (2.f * (float)B);
-      *ticket = 0;
-    }
-  }
+struct RowSq {
+  static constexpr bool kNullable = false, kPerSample = false;
+  __device__ float term(float u, float p, float n) const { return u * u + p * p + n * n; }
+  __device__ float term(float4 u, float4 p, float4 n) const { return dot4(u, u) + dot4(p, p) + dot4(n, n); }
+};
+
+template <int LPR>
+__device__ __forceinline__ void rowsq_fwd(const Triples &t, float *part, unsigned *ticket, float *out) {
+  float acc[1] = {walk_triples<LPR>(t, RowSq{})};
+  grid_join(acc, part, ticket, [&](const float (&s)[1]) { out[0] = s[0] / (2.f * (float)t.B); });
 }
 
-template <int LPR>      // (the float4 form, as k_bpr_fwd_v)
-__global__ __launch_bounds__(kBlock) void k_rowsq_fwd_v(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, float *__restrict__ part, unsigned *ticket, float *__restrict__ out) {
-  constexpr int SPW = kWave / LPR;
-  __shared__ float red[kWavesPerBlock];
-  __shared__ bool last;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int q = lane % LPR, k = lane / LPR;
-  float acc = 0.f;
-  bool bad = false;
-  const int64_t step = (int64_t)gridDim.x * kWavesPerBlock * SPW;
-  for (int64_t b0 = ((int64_t)blockIdx.x * kWavesPerBlock + wv) * SPW; b0 < B; b0 += step) {
-    const int64_t b = b0 + k;
-    if (b >= B) continue;
-    const int64_t ur = ui[b], pr = pi[b], nr = ni[b];
-    if (!nb.ok(ur, pr, nr)) { bad = true; continue; }
-    const float4 u = ld4(U + ur * D + q * 4), p = ld4(P + pr * D + q * 4), n = ld4(Nn + nr * D + q * 4);
-    acc += dot4(u, u) + dot4(p, p) + dot4(n, n);
-  }
-  if (__any(bad) && lane == 0 && nb.err) atomicOr(nb.err, MI_IDX_OUT_OF_RANGE);
-  acc = wave_sum(acc);
-  if (lane == 0) red[wv] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) s += red[j];
-    publish_partial(part, ticket, s, last);
-  }
-  __syncthreads();
-  if (last) {
-    float s = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) s += read_partial(part + j);
-    s = wave_sum(s);
-    if (lane == 0) red[wv] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) t += red[j];
-      out[0] = t / (2.f * (float)B);
-      *ticket = 0;
-    }
-  }
+__global__ __launch_bounds__(kBlock) void k_rowsq_fwd(Triples t, float *__restrict__ part, unsigned *ticket,
+                                                      float *__restrict__ out) {
+  rowsq_fwd<0>(t, part, ticket, out);
+}
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void k_rowsq_fwd_v(Triples t, float *__restrict__ part, unsigned *ticket,
+                                                        float *__restrict__ out) {
+  rowsq_fwd<LPR>(t, part, ticket, out);
 }
 
-__global__ __launch_bounds__(kBlock) void k_rowsq_bwd(
-    const float *__restrict__ U, const int64_t *__restrict__ ui, const float *__restrict__ P,
-    const int64_t *__restrict__ pi, const float *__restrict__ Nn, const int64_t *__restrict__ ni,
-    int64_t B, int D, RowBounds nb, const float *__restrict__ g, float *__restrict__ dU, float *__restrict__ dP,
-    float *__restrict__ dN) {
-  const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(kBlock) void k_rowsq_bwd(Triples t, const float *__restrict__ g, float *__restrict__ dU,
+                                                      float *__restrict__ dP, float *__restrict__ dN) {
+  const int lane = threadIdx.x & 63, D = t.D;
   const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-  const float c = g[0] / (float)B;          // d/dw of w^2 / (2B) = w / B
-  for (int64_t b = wave0; b < B; b += nwaves) {
-    const int64_t ur = ui[b], pr = pi[b], nr = ni[b];
-    if (!nb.ok(ur, pr, nr)) continue;
+  const float c = g[0] / (float)t.B;        // d/dw of w^2 / (2B) = w / B
+  for (int64_t b = wave0; b < t.B; b += nwaves) {
+    int64_t ur, pr, nr;
+    if (!t.rows<RowSq::kNullable>(b, ur, pr, nr)) continue;
     for (int j = lane; j < D; j += kWave) {
-      if (dU) atomicAdd(dU + ur * D + j, c * U[ur * D + j]);
-      if (dP) atomicAdd(dP + pr * D + j, c * P[pr * D + j]);
-      if (dN) atomicAdd(dN + nr * D + j, c * Nn[nr * D + j]);
+      if (dU) atomicAdd(dU + ur * D + j, c * t.U[ur * D + j]);
+      if (dP) atomicAdd(dP + pr * D + j, c * t.P[pr * D + j]);
+      if (dN) atomicAdd(dN + nr * D + j, c * t.Nn[nr * D + j]);
     }
   }
 }
@@ -290,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_rowsq_bwd(
 //   out[1] = prune = -( sum_{b: uvalid[b]} |tanh(K U[ui[b]])|^2 + sum_b |tanh(K I[pi[b]])|^2 + sum_k |tanh(K I[ni[k]])|^2 )
 // B users and positives, Bn negatives; uvalid flags the first occurrence of each user (the reference's torch.unique).
 // Row x of the B + B + Bn is one wave's; an id outside its table is skipped and flagged.  The workgroup partials (two
-// per workgroup) are joined by the last workgroup to take a ticket, in index order, as in k_rowsq_fwd.
+// per workgroup) are joined by the last workgroup to take a ticket, in index order (grid_join).
 struct BatchRows {
   const float *U, *I;
   const int64_t *ui, *pi, *ni;
@@ -310,10 +223,8 @@ struct BatchRows {
 
 __global__ __launch_bounds__(kBlock) void k_reg_prune_fwd(BatchRows a, float k_tanh, int *err, float *__restrict__ part,
                                                           unsigned *ticket, float *__restrict__ out) {
-  __shared__ float red[2][kWavesPerBlock];
-  __shared__ bool last;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  float sq = 0.f, th = 0.f;
+  float acc[2] = {0.f, 0.f};                   // squares, tanh squares
   bool any_bad = false;
   const int64_t R = 2 * a.B + a.Bn;
   for (int64_t x = (int64_t)blockIdx.x * kWavesPerBlock + wv; x < R; x += (int64_t)gridDim.x * kWavesPerBlock) {
@@ -323,44 +234,15 @@ __global__ __launch_bounds__(kBlock) void k_reg_prune_fwd(BatchRows a, float k_t
     if (bad) { any_bad = true; continue; }
     for (int j = lane; j < a.D; j += kWave) {
       const float v = w[j], t = tanhf(k_tanh * v);
-      sq += v * v;
-      th += prune ? t * t : 0.f;
+      acc[0] += v * v;
+      acc[1] += prune ? t * t : 0.f;
     }
   }
   if (any_bad && lane == 0 && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
-  sq = wave_sum(sq);
-  th = wave_sum(th);
-  if (lane == 0) { red[0][wv] = sq; red[1][wv] = th; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s0 = 0.f, s1 = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) { s0 += red[0][j]; s1 += red[1][j]; }
-    // (publish_partial with two words per workgroup: both stores acknowledged before the ticket is taken)
-    __hip_atomic_store(part + 2 * blockIdx.x, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(part + 2 * blockIdx.x + 1, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (last) {
-    float s0 = 0.f, s1 = 0.f;
-    for (unsigned j = threadIdx.x; j < gridDim.x; j += kBlock) {
-      s0 += read_partial(part + 2 * j);
-      s1 += read_partial(part + 2 * j + 1);
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    __syncthreads();
-    if (lane == 0) { red[0][wv] = s0; red[1][wv] = s1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t0 = 0.f, t1 = 0.f;
-      for (int j = 0; j < kWavesPerBlock; ++j) { t0 += red[0][j]; t1 += red[1][j]; }
-      out[0] = t0 / (2.f * (float)a.B);
-      out[1] = -t1;
-      *ticket = 0;
-    }
-  }
+  grid_join(acc, part, ticket, [&](const float (&s)[2]) {
+    out[0] = s[0] / (2.f * (float)a.B);
+    out[1] = -s[1];
+  });
 }
 
 // dTable[row] += g[0] w / B + g[1] d(-tanh^2(K w))/dw,   d(-tanh^2(K w))/dw = -2 K tanh(K w) (1 - tanh^2(K w))
@@ -413,7 +295,6 @@ __device__ __forceinline__ void scan_row(const float *__restrict__ row, int64_t 
   }
   for (int64_t j = done + tid; j < ncol; j += kBlock) f(row[j], (int)j);
 }
-__device__ __forceinline__ bool aligned16_dev(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 __device__ __forceinline__ bool before(float av, int ai, float bv, int bi) {
   return av > bv || (av == bv && ai < bi);
 }
@@ -444,7 +325,7 @@ __global__ __launch_bounds__(kBlock) void k_mask_topk(
   // pass 1 over a PREFIX of the row (a full second read of a 150 KB row would come from HBM again: 2048
   // rows are in flight): every thread's best element of the sample; the k-th best of those 256 bounds the
   // k-th best of the whole row from below
-  const bool vec = ((ld & 3) == 0) && aligned16_dev(scores);
+  const bool vec = ((ld & 3) == 0) && aligned16(scores);
   float bv = ninf;
   int bi = 0x7fffffff;
   scan_row(row, ncol < kSample ? ncol : (int64_t)kSample, vec, [&](float v, int j) {
@@ -534,6 +415,37 @@ __global__ __launch_bounds__(kBlock) void k_mask_topk(
 
 }  // namespace
 
+// the argument checks of the six triple entry points (index arrays may be NULL where `nullable`: row b, which the table
+// must then have)
+static bool triples(Triples &t, bool nullable, const float *U, const int64_t *ui, const float *P, const int64_t *pi,
+                    const float *Nn, const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP, int64_t nN, int32_t *err) {
+  if (B <= 0 || D <= 0 || !U || !P || !Nn) return false;
+  if (nullable ? (!ui && nU < B) || (!pi && nP < B) || (!ni && nN < B) : !ui || !pi || !ni) return false;
+  t = Triples{U, ui, P, pi, Nn, ni, B, nU, nP, nN, D, err};
+  return true;
+}
+
+// The forward launch of both losses: workspace = per-workgroup partials, then the ticket word at
+// workspace[mi_bpr_workspace_elems(B) - 1] in either form — zeroed here once per call (captured as a memset node in a
+// graph) unless the caller keeps it armed.  launch(LPR constant, grid, ticket) starts the float4 kernel of LPR lanes per
+// row, or for LPR = 0 the any-D one.
+template <class Launch>
+static int triples_fwd(const Triples &t, bool zero_ticket, float *workspace, void *stream, Launch launch) {
+  const int grid = grid_for_waves(t.B);
+  if (zero_ticket && hipMemsetAsync(workspace + grid, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess)
+    return MI_ERR_LAUNCH;
+  unsigned *ticket = reinterpret_cast<unsigned *>(workspace + grid);
+  if (vec_ok(t.D) && all_aligned16(t.U, t.P, t.Nn)) {
+    const int lpr = t.D / 4, spw = kWave / lpr;
+#define FWDV(L) launch(std::integral_constant<int, L>{}, grid_for_waves((t.B + spw - 1) / spw), ticket)
+    MI_DISPATCH_LPR(lpr, FWDV)
+#undef FWDV
+  } else {
+    launch(std::integral_constant<int, 0>{}, grid, ticket);
+  }
+  return launch_status();
+}
+
 extern "C" {
 
 int64_t mi_bpr_workspace_elems(int64_t B) {
@@ -544,25 +456,14 @@ int64_t mi_bpr_workspace_elems(int64_t B) {
 static int bpr_fwd_impl(bool zero_ticket, const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
                const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP, int64_t nN, int32_t *err,
                float *sig, float *workspace, float *loss, void *stream, const float *plus = nullptr, float plus_w = 0.f) {
-  if (B <= 0 || D <= 0) return MI_ERR_INVALID_ARG;
-  if ((!ui && nU < B) || (!pi && nP < B) || (!ni && nN < B)) return MI_ERR_INVALID_ARG;
-  const RowBounds nb{nU, nP, nN, err};
-  if (!U || !P || !Nn || !sig || !workspace || !loss) return MI_ERR_INVALID_ARG;
-  const int grid = grid_for_waves(B);
-  // workspace[grid] is the ticket: zeroed here once per call (captured as a memset node in a graph)
-  if (zero_ticket && hipMemsetAsync(workspace + grid, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess)
-    return MI_ERR_LAUNCH;
-  unsigned *ticket = reinterpret_cast<unsigned *>(workspace + grid);      // workspace[mi_bpr_workspace_elems(B) - 1], both forms
-  const int lpr = D / 4;
-  if (D % 4 == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && aligned16(U) && aligned16(P) && aligned16(Nn)) {
-    const int gv = grid_for_waves((B + 64 / lpr - 1) / (64 / lpr));
-#define BPRV(L) MI_LAUNCH("bpr_fwd", (k_bpr_fwd_v<L>), gv, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, sig, workspace, ticket, loss, plus, plus_w)
-    MI_DISPATCH_LPR(lpr, BPRV)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
-#undef BPRV
-    return launch_status();
-  }
-  MI_LAUNCH("bpr_fwd", k_bpr_fwd, grid, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, sig, workspace, ticket, loss, plus, plus_w);
-  return launch_status();
+  Triples t;
+  if (!triples(t, true, U, ui, P, pi, Nn, ni, B, D, nU, nP, nN, err) || !sig || !workspace || !loss) return MI_ERR_INVALID_ARG;
+  return triples_fwd(t, zero_ticket, workspace, stream, [&](auto lpr, int grid, unsigned *ticket) {
+    if constexpr (decltype(lpr)::value != 0)
+      MI_LAUNCH("bpr_fwd", (k_bpr_fwd_v<decltype(lpr)::value>), grid, kBlock, stream, t, sig, workspace, ticket, loss, plus, plus_w);
+    else
+      MI_LAUNCH("bpr_fwd", k_bpr_fwd, grid, kBlock, stream, t, sig, workspace, ticket, loss, plus, plus_w);
+  });
 }
 
 int mi_bpr_fwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
@@ -589,35 +490,23 @@ int mi_bpr_fwd_plus(const float *U, const int64_t *ui, const float *P, const int
 int mi_bpr_bwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
                const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP, int64_t nN, const float *sig,
                const float *g, float *dU, float *dP, float *dN, void *stream) {
-  if (B <= 0 || D <= 0) return MI_ERR_INVALID_ARG;
-  if ((!ui && nU < B) || (!pi && nP < B) || (!ni && nN < B)) return MI_ERR_INVALID_ARG;
-  const RowBounds nb{nU, nP, nN, nullptr};
-  if (!U || !P || !Nn || !sig || !g) return MI_ERR_INVALID_ARG;
-  MI_LAUNCH("bpr_bwd", k_bpr_bwd, grid_for_waves(B), kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, sig, g,
-            dU, dP, dN);
+  Triples t;
+  if (!triples(t, true, U, ui, P, pi, Nn, ni, B, D, nU, nP, nN, nullptr) || !sig || !g) return MI_ERR_INVALID_ARG;
+  MI_LAUNCH("bpr_bwd", k_bpr_bwd, grid_for_waves(B), kBlock, stream, t, sig, g, dU, dP, dN);
   return launch_status();
 }
 
 static int rowsq_fwd_impl(bool zero_ticket, const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
                  const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP, int64_t nN, int32_t *err,
                  float *workspace, float *out, void *stream) {
-  if (B <= 0 || D <= 0) return MI_ERR_INVALID_ARG;
-  const RowBounds nb{nU, nP, nN, err};
-  if (!U || !P || !Nn || !ui || !pi || !ni || !workspace || !out) return MI_ERR_INVALID_ARG;
-  const int grid = grid_for_waves(B);
-  if (zero_ticket && hipMemsetAsync(workspace + grid, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess)
-    return MI_ERR_LAUNCH;
-  unsigned *ticket = reinterpret_cast<unsigned *>(workspace + grid);
-  const int lpr = D / 4;
-  if (D % 4 == 0 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && aligned16(U) && aligned16(P) && aligned16(Nn)) {
-    const int gv = grid_for_waves((B + 64 / lpr - 1) / (64 / lpr));
-#define RSQV(L) MI_LAUNCH("rowsq_fwd", (k_rowsq_fwd_v<L>), gv, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, workspace, ticket, out)
-    MI_DISPATCH_LPR(lpr, RSQV)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
-#undef RSQV
-    return launch_status();
-  }
-  MI_LAUNCH("rowsq_fwd", k_rowsq_fwd, grid, kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, workspace, ticket, out);
-  return launch_status();
+  Triples t;
+  if (!triples(t, false, U, ui, P, pi, Nn, ni, B, D, nU, nP, nN, err) || !workspace || !out) return MI_ERR_INVALID_ARG;
+  return triples_fwd(t, zero_ticket, workspace, stream, [&](auto lpr, int grid, unsigned *ticket) {
+    if constexpr (decltype(lpr)::value != 0)
+      MI_LAUNCH("rowsq_fwd", (k_rowsq_fwd_v<decltype(lpr)::value>), grid, kBlock, stream, t, workspace, ticket, out);
+    else
+      MI_LAUNCH("rowsq_fwd", k_rowsq_fwd, grid, kBlock, stream, t, workspace, ticket, out);
+  });
 }
 
 int mi_rowsq_fwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
@@ -635,10 +524,9 @@ int mi_rowsq_fwd_armed(const float *U, const int64_t *ui, const float *P, const 
 int mi_rowsq_bwd(const float *U, const int64_t *ui, const float *P, const int64_t *pi, const float *Nn,
                  const int64_t *ni, int64_t B, int32_t D, int64_t nU, int64_t nP, int64_t nN, const float *g,
                  float *dU, float *dP, float *dN, void *stream) {
-  if (B <= 0 || D <= 0) return MI_ERR_INVALID_ARG;
-  const RowBounds nb{nU, nP, nN, nullptr};
-  if (!U || !P || !Nn || !ui || !pi || !ni || !g) return MI_ERR_INVALID_ARG;
-  MI_LAUNCH("rowsq_bwd", k_rowsq_bwd, grid_for_waves(B), kBlock, stream, U, ui, P, pi, Nn, ni, B, D, nb, g, dU, dP, dN);
+  Triples t;
+  if (!triples(t, false, U, ui, P, pi, Nn, ni, B, D, nU, nP, nN, nullptr) || !g) return MI_ERR_INVALID_ARG;
+  MI_LAUNCH("rowsq_bwd", k_rowsq_bwd, grid_for_waves(B), kBlock, stream, t, g, dU, dP, dN);
   return launch_status();
 }
 

@@ -22,9 +22,6 @@ struct Seg2 {            // rows [0,split) live at a, rows [split, ..) at b
 };
 // b == nullptr: one table, every row lives at a
 inline Seg2 seg2(const float *a, const float *b, int split) { return Seg2{a, b ? b : a, b ? split : 0x7fffffff}; }
-// every pointer of the list is 16-byte aligned (a null one, i.e. an operand that is not given, passes)
-template <class... P>
-inline bool all_aligned16(const P *...p) { return (aligned16(p) && ...); }
 __device__ __forceinline__ const float *seg_row(const Seg2 &s, int row, int D) {
   return row < s.split ? s.a + (int64_t)row * D : s.b + (int64_t)(row - s.split) * D;
 }

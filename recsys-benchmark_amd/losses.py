@@ -121,6 +121,17 @@ def _ticket_workspace(kind: str, dev, elems: int):
     return torch.empty(int(elems), dtype=torch.float32, device=dev), False
 
 
+def _segment_grads(U, P):
+    """Two [*, D] tables that are adjacent row segments of ONE matrix (LightGCN's propagation returns user and item rows
+    that way; SingleLightGCN's table): their zero-filled gradients as two views of one buffer — one fill launch instead
+    of two.  None when the tables are anything else.  (Both callers' forwards have checked: 2-D tables of one D.)"""
+    if not (U.is_contiguous() and P.is_contiguous() and P.data_ptr() == U.data_ptr() + U.numel() * 4
+            and U.untyped_storage().data_ptr() == P.untyped_storage().data_ptr()):
+        return None
+    joint = torch.zeros((U.shape[0] + P.shape[0], U.shape[1]), dtype=torch.float32, device=U.device)
+    return joint[: U.shape[0]], joint[U.shape[0]:]
+
+
 class _BPRFn(torch.autograd.Function):
     """-logsigmoid(u.p - u.n).mean() with u = U[ui], p = P[pi], n = Nn[ni] (None index = row b)."""
 
@@ -174,20 +185,14 @@ class _BPRFn(torch.autograd.Function):
         same = (idx[1] is not None and idx[2] is not None and need[1] and need[2]
                 and P.data_ptr() == Nn.data_ptr() and P.shape == Nn.shape)
         grads = []
-        # user and item tables that are the two row segments of ONE matrix (LightGCN's propagation returns them that way):
-        # their zero-filled gradients are two views of one buffer — one fill launch instead of two
-        joint = None
-        if (need[0] and need[1] and idx[0] is not None and idx[1] is not None and U.dim() == 2 and U.shape[1:] == P.shape[1:]
-                and U.is_contiguous() and P.is_contiguous() and P.data_ptr() == U.data_ptr() + U.numel() * 4
-                and U.untyped_storage().data_ptr() == P.untyped_storage().data_ptr()):
-            joint = torch.zeros((U.shape[0] + P.shape[0],) + tuple(U.shape[1:]), dtype=torch.float32, device=U.device)
+        joint = _segment_grads(U, P) if need[0] and need[1] and idx[0] is not None and idx[1] is not None else None
         for k, (t, i) in enumerate(zip((U, P, Nn), idx)):
             if not need[k]:
                 grads.append(None)
             elif k == 2 and same:
                 grads.append(grads[1])
             elif joint is not None and k < 2:
-                grads.append(joint[: U.shape[0]] if k == 0 else joint[U.shape[0]:])
+                grads.append(joint[k])
             else:   # rows repeat under an index array: the kernel accumulates with atomics into zeros
                 grads.append(torch.zeros_like(t) if i is not None else torch.empty_like(t))
         _lib.check(_lib.load().mi_bpr_bwd(U.data_ptr(), _lib.ptr(idx[0]), P.data_ptr(), _lib.ptr(idx[1]), Nn.data_ptr(),
@@ -237,20 +242,14 @@ class _RowSqFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, P, Nn, ui, pi, ni):
-        dev = _lib.require_gpu(U, P, Nn, ui)
-        lib = _lib.load()
+        _lib.require_gpu(U, P, Nn, ui)
         U, P, Nn = _kernels._f32c(U), _kernels._f32c(P), _kernels._f32c(Nn)
         ui, pi, ni = (_kernels._i64c(t).view(-1) for t in (ui, pi, ni))
         B, D = ui.numel(), U.shape[1]
         if pi.numel() != B or ni.numel() != B or P.shape[1] != D or Nn.shape[1] != D or B == 0:
             raise ValueError("reg loss: users / positives / negatives must be [B] indices into [*, D] tables")
-        ws, armed = _ticket_workspace("rowsq", dev, lib.mi_bpr_workspace_elems(B))
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-        _lib.check((lib.mi_rowsq_fwd_armed if armed else lib.mi_rowsq_fwd)(U.data_ptr(), ui.data_ptr(), P.data_ptr(), pi.data_ptr(), Nn.data_ptr(), ni.data_ptr(),
-                                    B, D, U.shape[0], P.shape[0], Nn.shape[0], _lib.err_word(dev).data_ptr(),
-                                    ws.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev)), "mi_rowsq_fwd")
         ctx.save_for_backward(U, P, Nn, ui, pi, ni)
-        return out.view(())
+        return _kernels.rowsq_fwd(U, ui, P, pi, Nn, ni).view(())
 
     @staticmethod
     def backward(ctx, g):
@@ -260,10 +259,7 @@ class _RowSqFn(torch.autograd.Function):
         dU = torch.zeros_like(U) if ctx.needs_input_grad[0] else None
         dP = torch.zeros_like(P) if (ctx.needs_input_grad[1] or (same and ctx.needs_input_grad[2])) else None
         dN = dP if same else (torch.zeros_like(Nn) if ctx.needs_input_grad[2] else None)
-        _lib.check(_lib.load().mi_rowsq_bwd(U.data_ptr(), ui.data_ptr(), P.data_ptr(), pi.data_ptr(), Nn.data_ptr(),
-                                            ni.data_ptr(), ui.numel(), U.shape[1], U.shape[0], P.shape[0], Nn.shape[0],
-                                            g.data_ptr(), _lib.ptr(dU),
-                                            _lib.ptr(dP), _lib.ptr(dN), _lib.stream_ptr(g.device)), "mi_rowsq_bwd")
+        _kernels.rowsq_bwd(U, ui, P, pi, Nn, ni, g, dU, dP, dN)
         # one buffer holds both item contributions when the tables coincide: hand it to the first, nothing to the second
         return dU, dP, (None if same else dN), None, None, None
 
@@ -301,12 +297,9 @@ class _RegPruneFn(torch.autograd.Function):
         U, I, ui, pi, ni, uvalid = ctx.saved_tensors
         g = torch.stack([_kernels._f32c(g_reg).view(()), _kernels._f32c(g_prune).view(())])
         need_u, need_i = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        # users and items that are the two row segments of ONE matrix (SingleLightGCN's table): one zero-filled gradient
-        joint = None
-        if (need_u and need_i and U.is_contiguous() and I.is_contiguous() and I.data_ptr() == U.data_ptr() + U.numel() * 4
-                and U.untyped_storage().data_ptr() == I.untyped_storage().data_ptr()):
-            joint = torch.zeros((U.shape[0] + I.shape[0], U.shape[1]), dtype=torch.float32, device=U.device)
-            dU, dI = joint[: U.shape[0]], joint[U.shape[0]:]
+        joint = _segment_grads(U, I) if need_u and need_i else None
+        if joint is not None:
+            dU, dI = joint
         else:
             dU = torch.zeros_like(U) if need_u else None
             dI = torch.zeros_like(I) if need_i else None

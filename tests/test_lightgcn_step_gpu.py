@@ -15,19 +15,46 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 
 
-@pytest.mark.parametrize("B,D", [(1, 64), (7, 5), (2048, 64), (5000, 16)])
-def test_bpr_loss_matches_reference(B, D):
+def _misaligned(t):
+    """The same values on the device as a contiguous matrix whose base lies one float past a 16-byte boundary: (leaf, view)."""
+    flat = torch.cat([torch.zeros(1), t.detach().reshape(-1)]).to(DEV).requires_grad_(True)
+    return flat, flat[1:].view(t.shape)
+
+
+def _check_bpr_loss(B, D, misaligned=False):
     g = torch.Generator().manual_seed(B + D)
     u, p, n = (torch.randn(B, D, generator=g, requires_grad=True) for _ in range(3))
     ref = ro.bpr_loss(u, p, n)
     (ref * 1.7).backward()
-    hu, hp, hn = (t.detach().to(DEV).requires_grad_(True) for t in (u, p, n))
-    out = bpr_loss(hu, hp, hn)
+    if misaligned:
+        (hu, hp, hn), views = zip(*(_misaligned(t) for t in (u, p, n)))
+        assert all(v.data_ptr() % 16 == 4 and v.is_contiguous() for v in views)
+        out = bpr_loss(*views)
+    else:
+        hu, hp, hn = (t.detach().to(DEV).requires_grad_(True) for t in (u, p, n))
+        out = bpr_loss(hu, hp, hn)
     (out * 1.7).backward()
     # fp32 row dots of length D and a mean over B in a different order
     assert_close(out, ref, 1e-5, 1e-6, "loss")
     for a, b, name in ((hu, u, "du"), (hp, p, "dp"), (hn, n, "dn")):
-        assert_close(a.grad, b.grad, 1e-5, 1e-7, name)
+        assert_close(a.grad[1:].view(B, D) if misaligned else a.grad, b.grad, 1e-5, 1e-7, name)
+
+
+# 4 samples per workgroup in the any-D form, 64 / (D / 4) per wave in the float4 form (D / 4 a power of two <= 64); the
+# last workgroup's 256 threads stride over the partials, the grid is capped at 2048 workgroups
+@pytest.mark.parametrize("B,D", [(1, 64), (7, 5), (2048, 64), (5000, 16),
+                                 (4200, 64), (1100, 5),        # 263 / 275 workgroups: a second trip over the partials
+                                 (33000, 64), (8200, 5),       # past the grid cap: the batch loop strides
+                                 (64, 4), (64, 8), (64, 32), (64, 128), (64, 256),      # the other float4 widths
+                                 (64, 70),                     # any-D, two elements per lane
+                                 (64, 260)])                   # a multiple of 4 above 256: any-D
+def test_bpr_loss_matches_reference(B, D):
+    _check_bpr_loss(B, D)
+
+
+def test_bpr_loss_matches_reference_on_tables_off_the_16_byte_boundary():
+    """Contiguous [65, 64] tables that start one float past a 16-byte boundary: the any-D form takes them."""
+    _check_bpr_loss(65, 64, misaligned=True)
 
 
 def test_bpr_loss_is_stable_for_huge_margins():
@@ -213,6 +240,77 @@ def test_reg_loss_rows_matches_reference_formula_and_model_uses_it():
     assert_close(got, ref, 1e-5, 1e-5, "LightGCN.get_reg_loss")
     got.backward()
     assert_close(model.user_emb_table._emb_module.weight.grad * 3.0, U.grad, 1e-4, 1e-7)
+
+
+def _reg_case(B, D, integers):
+    """(U, I, users, pos, neg) on the CPU; integers: table entries from {0, +-1, +-2}."""
+    g = torch.Generator().manual_seed(B + D)
+    nu, ni = 300, 500
+    if integers:
+        U, I = (torch.randint(-2, 3, (r, D), generator=g).float() for r in (nu, ni))
+    else:
+        U, I = torch.randn(nu, D, generator=g), torch.randn(ni, D, generator=g)
+    users = torch.randint(0, nu, (B,), generator=g)
+    pos, neg = torch.randint(0, ni, (B,), generator=g), torch.randint(0, ni, (B,), generator=g)
+    return U, I, users, pos, neg
+
+
+def _reg_both_ways(U, I, users, pos, neg):
+    """reg_loss_rows on the device and the formula in float64: (out, dU, dI), (ref, dU, dI)."""
+    from recsys_benchmark_amd.losses import reg_loss_rows
+
+    U64, I64 = U.double().requires_grad_(True), I.double().requires_grad_(True)
+    ref = (U64[users].pow(2).sum() + I64[pos].pow(2).sum() + I64[neg].pow(2).sum()) / (2 * users.numel())
+    ref.backward()
+    hU, hI = U.to(DEV).requires_grad_(True), I.to(DEV).requires_grad_(True)
+    out = reg_loss_rows(hU, hI, users.to(DEV), pos.to(DEV), neg.to(DEV))
+    out.backward()
+    _lib.check_index_errors()
+    return (out.cpu(), hU.grad.cpu(), hI.grad.cpu()), (ref.detach(), U64.grad, I64.grad)
+
+
+@pytest.mark.parametrize("B,D", [(8192, 64), (2048, 5)])      # 512 workgroups in the float4 and in the any-D form
+def test_reg_loss_rows_is_exact_on_small_integer_tables(B, D):
+    """Entries from {0, +-1, +-2}: every partial sum of squares is an integer below 2^24 (at most 3 * 8192 * 64 * 4), so
+    exact in fp32 in any order, and B is a power of two, so the division by 2B and the gradient rows (integer / B, added
+    up with atomics) are exact too: the kernels' results equal the float64 formula bit for bit."""
+    got, ref = _reg_both_ways(*_reg_case(B, D, integers=True))
+    for a, b, name in zip(got, ref, ("reg loss", "dU", "dI")):
+        assert torch.equal(a, b.float()), name
+
+
+@pytest.mark.parametrize("D", [4, 8, 32, 128, 256, 70, 260])
+def test_reg_loss_rows_matches_float64_at_every_width(D):
+    got, ref = _reg_both_ways(*_reg_case(64, D, integers=False))
+    assert_close(got[0], ref[0].float(), 1e-5, 1e-5, "reg loss")
+    assert_close(got[1], ref[1].float(), 1e-4, 1e-7, "dU")
+    assert_close(got[2], ref[2].float(), 1e-4, 1e-7, "dI (positives + negatives)")
+
+
+@pytest.mark.parametrize("B,D", [(1100, 5), (4200, 64)])      # any-D form (275 workgroups), float4 form (263)
+def test_ticket_is_rearmed_three_calls_on_one_kept_workspace_agree_bit_for_bit(B, D):
+    """The last workgroup leaves the ticket word zero, so the kept workspace (losses.ARMED_WORKSPACES) of bpr_loss_rows,
+    reg_loss_rows and reg_prune_loss_rows serves the next launch as it is; all three launch more than 256 workgroups here
+    and sum in a fixed order.  info_nce (300 workgroups) takes a fresh workspace and zeroes its ticket per call: for it
+    only the fixed order is on trial."""
+    from recsys_benchmark_amd import losses
+
+    assert losses.ARMED_WORKSPACES
+    g = torch.Generator().manual_seed(7)
+    nu, ni = 300, 500
+    U, I = torch.randn(nu, D, generator=g).to(DEV), torch.randn(ni, D, generator=g).to(DEV)
+    users = torch.randint(0, nu, (B,), generator=g).to(DEV)
+    pos, neg = torch.randint(0, ni, (B,), generator=g).to(DEV), torch.randint(0, ni, (B,), generator=g).to(DEV)
+    v = torch.randn(300, 64, generator=g).to(DEV)
+    calls = {"bpr_loss_rows": lambda: bpr_loss_rows(U, I, users, pos, neg),
+             "reg_loss_rows": lambda: losses.reg_loss_rows(U, I, users, pos, neg),
+             "reg_prune_loss_rows": lambda: torch.stack(losses.reg_prune_loss_rows(U * 0.01, I * 0.01, users, pos, neg)),
+             "info_nce": lambda: info_nce(v, v, 0.2)}
+    for name, call in calls.items():
+        first, second, third = call(), call(), call()
+        assert torch.isfinite(first).all(), name
+        assert torch.equal(first, second) and torch.equal(first, third), name
+    _lib.check_index_errors()
 
 
 # ------------------------------------------------------------------ info_nce / bpr_loss_multi (src/losses.py:25-68)
