@@ -63,7 +63,8 @@ MI_API const char *mi_strerror(int code);
  *   0.5*sum_d[(sum_f e)^2 - sum_f e^2]   (:91-92,98)
  *   EmbeddingBag(N,1,"sum")(x) + bias    (:95)
  * idx      int64[B,F] raw per-field ids (no offsets added)
- * offsets  int64[F]
+ * offsets  int64[F]; NULL = the ids are row numbers already, where the float4 kernels run (D = 4, 8, 16 .. 256, W and
+ *          emb_out 16-byte aligned, ldw % 4 == 0); MI_ERR_INVALID_ARG with NULL on the scalar path
  * W        fp32[N,D], w1 fp32[N] (fc.weight viewed flat), bias fp32[1] (nullable)
  * emb_out  fp32[B,F,D]   rows_out int64[B,F] (= idx+offsets; nullable)
  * yfm_out  fp32[B]

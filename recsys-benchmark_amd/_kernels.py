@@ -164,13 +164,8 @@ class GatherFM(torch.autograd.Function):
                 "mi_gather_fm_bwd_rows",
             )
             gb_done = True
-            # a table that wants a dense gradient next to one in row form (the reference's sparse config keeps the
-            # first-order table dense): scatter-add the values just computed — never a second pass over a zeroed [N, D]
-            if need_W:
-                gW = _coo(rows, gvals, Wshape) if sparse_W else _scatter_rows(rows, gvals, N, D, stream).view(Wshape)
-            if need_w1:
-                gw1 = (_coo(rows, g1vals.view((-1,) + (1,) * (len(w1shape) - 1)), w1shape) if sparse_w1
-                       else _scatter_rows(rows, g1vals, N, 1, stream).view(w1shape))
+            gW, gw1 = _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1,
+                                   stream)
         elif dense_form:
             gWd = torch.zeros((N, D), dtype=torch.float32, device=dev)
             gw1d = torch.zeros((N,), dtype=torch.float32, device=dev)
@@ -230,6 +225,19 @@ def _scatter_rows(rows, vals, N, D, stream):
     _lib.check(_lib.load().mi_scatter_axpy_rows(rows.data_ptr(), vals.data_ptr(), 1.0, out.data_ptr(), rows.numel(), D, N,
                                                 stream), "mi_scatter_axpy_rows")
     return out
+
+
+def _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1, stream):
+    """(gW, gw1) of the two lookup tables from the row-form values gvals[B*F, D] / g1vals[B*F] at `rows`.  A table that
+    wants a dense gradient next to one in row form (the reference's sparse config keeps the first-order table dense)
+    gets the values just computed scatter-added — never a second pass over a zeroed [N, D]."""
+    gW = gw1 = None
+    if need_W:
+        gW = _coo(rows, gvals, Wshape) if sparse_W else _scatter_rows(rows, gvals, N, D, stream).view(Wshape)
+    if need_w1:
+        gw1 = (_coo(rows, g1vals.view((-1,) + (1,) * (len(w1shape) - 1)), w1shape) if sparse_w1
+               else _scatter_rows(rows, g1vals, N, 1, stream).view(w1shape))
+    return gW, gw1
 
 
 def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False):

@@ -45,9 +45,6 @@ inline Cut cut_of(int64_t N, int64_t mod1, int64_t div2) {
   return Cut{chunks_for((N + mod1 - 1) / mod1), chunks_for(div2 < N ? div2 : N)};
 }
 
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-
 template <int XF>
 __global__ __launch_bounds__(kBlock) void k_dual_table_fwd(TableArgs a, float *__restrict__ out) {
   const uint32_t total = a.N * a.C, De = a.C * 4;

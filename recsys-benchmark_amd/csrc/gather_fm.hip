@@ -24,6 +24,32 @@
 namespace {
 using namespace mi;
 
+// ------------------------------------------------------------ small helpers ----
+// dE_bf = g_emb_bf + g_b (S_b - e_bf): the lookup's gradient row through the FM term (src/models/deepfm.py:91-92)
+__device__ __forceinline__ float4 fm_grad_row(float4 ge, float gy, float4 S, float4 e) {
+  return make_float4(ge.x + gy * (S.x - e.x), ge.y + gy * (S.y - e.y), ge.z + gy * (S.z - e.z), ge.w + gy * (S.w - e.w));
+}
+
+// SLOT = false: gvals[i,:] / g1vals[i] in lookup order (the reference's COO values), i = b*F + f.
+// SLOT = true : the row goes to gvals + slot[i]*(D+4), its first-order gradient into column D of
+//               the same packed row; slots >= nslot (the dump slot of route.hip) are skipped.
+template <int LPR, bool SLOT>
+__device__ __forceinline__ void store_grad_row(float *__restrict__ gvals, float *__restrict__ g1vals,
+                                               const int64_t *__restrict__ slot, int64_t nslot, int64_t i, int q,
+                                               float4 o4, float gy) {
+  constexpr int D = LPR * 4;
+  if constexpr (SLOT) {
+    const int64_t s = slot[i];
+    if ((uint64_t)s < (uint64_t)nslot) {
+      st4(gvals + s * (D + 4) + q * 4, o4);
+      if (q == 0) st4(gvals + s * (D + 4) + D, make_float4(gy, 0.f, 0.f, 0.f));
+    }
+  } else {
+    st4(gvals + i * D + q * 4, o4);
+    if (q == 0) g1vals[i] = gy;
+  }
+}
+
 // ---------------------------------------------------------------- forward ----
 // SHFL (F <= 64): the sample's F ids arrive by ONE coalesced load (lane l < F takes idx[b, l] + offsets[l]) and reach
 // the row slots by shuffles — one dependent vector-memory instruction in front of the row gathers instead of NIT id
@@ -246,9 +272,23 @@ __device__ __forceinline__ bool bias_grad_block(const float *__restrict__ g_y, i
 }
 
 // ----------------------------------------------------- backward, row form ----
-// SLOT = false: gvals[b,f,:] / g1vals[b,f] in lookup order (the reference's COO values).
-// SLOT = true : the row goes to gvals + slot[b,f]*(D+4), its first-order gradient into column D of
-//               the same packed row; slots >= nslot (the dump slot of route.hip) are skipped.
+// e[k] / ge[k] = the lane's float4 of emb / g_emb (zeros without one) at field f + k*RS of the sample at `base`; zeros past F
+template <int LPR, int NSTEP>
+__device__ __forceinline__ void load_chunk(const float *__restrict__ emb, const float *__restrict__ g_emb, int64_t base, int f,
+                                           int F, int q, float4 (&e)[NSTEP], float4 (&ge)[NSTEP]) {
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int k = 0; k < NSTEP; ++k, f += kWave / LPR) {
+    const bool act = f < F;
+    const int64_t o = (base + f) * (LPR * 4) + q * 4;
+    e[k] = act ? ld4(emb + o) : z;
+    ge[k] = (act && g_emb) ? ld4(g_emb + o) : z;
+  }
+}
+
+// The gradient rows, stored by store_grad_row in either form.  NIT > 0: e[] and g_emb's rows are read once, all NIT loads
+// in flight, and e[] stays in registers between the sum over the fields and the write; NIT = 0: one-step chunks, e read
+// again in the second walk.
 template <int LPR, int NIT, bool SLOT>
 __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
     const float *__restrict__ emb, const float *__restrict__ g_y,
@@ -256,6 +296,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
     int64_t B, int F, const int64_t *__restrict__ slot, int64_t nslot, float *__restrict__ gbias) {
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
+  constexpr int NSTEP = NIT > 0 ? NIT : 1;
   int blk, nblk;
   if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   const int lane = threadIdx.x & 63;
@@ -263,72 +304,25 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
   const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int fend = NIT > 0 ? 1 : F;      // (NIT > 0: the chunk loops below run once)
 
   for (int64_t b = wave0; b < B; b += nwaves) {
     const int64_t base = b * F;
     const float gy = g_y[b];
     float4 S = z;
-    if constexpr (NIT > 0) {
-      float4 e[NIT], ge[NIT];
+    float4 e[NSTEP], ge[NSTEP];
+    for (int f0 = 0; f0 < fend; f0 += NSTEP * RS) {
+      load_chunk<LPR, NSTEP>(emb, NIT > 0 ? g_emb : nullptr, base, f0 + r, F, q, e, ge);
 #pragma unroll
-      for (int k = 0; k < NIT; ++k) {
-        const int f = r + k * RS;
-        const bool act = f < F;
-        const int64_t o = (base + f) * D + q * 4;
-        e[k] = act ? ld4(emb + o) : z;
-        ge[k] = (act && g_emb) ? ld4(g_emb + o) : z;
-      }
+      for (int k = 0; k < NSTEP; ++k) acc4(S, e[k]);
+    }
+    S = slot_sum<LPR>(S);
+    for (int f0 = 0; f0 < fend; f0 += NSTEP * RS) {
+      if constexpr (NIT == 0) load_chunk<LPR, NSTEP>(emb, g_emb, base, f0 + r, F, q, e, ge);
 #pragma unroll
-      for (int k = 0; k < NIT; ++k) {
-        S.x += e[k].x; S.y += e[k].y; S.z += e[k].z; S.w += e[k].w;
-      }
-      S = slot_sum<LPR>(S);
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) {
-        const int f = r + k * RS;
-        if (f < F) {
-          float4 o4;
-          o4.x = ge[k].x + gy * (S.x - e[k].x);
-          o4.y = ge[k].y + gy * (S.y - e[k].y);
-          o4.z = ge[k].z + gy * (S.z - e[k].z);
-          o4.w = ge[k].w + gy * (S.w - e[k].w);
-          if constexpr (SLOT) {
-            const int64_t s = slot[base + f];
-            if ((uint64_t)s < (uint64_t)nslot) {
-              st4(gvals + s * (D + 4) + q * 4, o4);
-              if (q == 0) st4(gvals + s * (D + 4) + D, make_float4(gy, 0.f, 0.f, 0.f));
-            }
-          } else {
-            st4(gvals + (base + f) * D + q * 4, o4);
-            if (q == 0) g1vals[base + f] = gy;
-          }
-        }
-      }
-    } else {
-      for (int f = r; f < F; f += RS) {
-        const float4 e = ld4(emb + (base + f) * D + q * 4);
-        S.x += e.x; S.y += e.y; S.z += e.z; S.w += e.w;
-      }
-      S = slot_sum<LPR>(S);
-      for (int f = r; f < F; f += RS) {
-        const int64_t o = (base + f) * D + q * 4;
-        const float4 e = ld4(emb + o);
-        const float4 ge = g_emb ? ld4(g_emb + o) : z;
-        float4 o4;
-        o4.x = ge.x + gy * (S.x - e.x);
-        o4.y = ge.y + gy * (S.y - e.y);
-        o4.z = ge.z + gy * (S.z - e.z);
-        o4.w = ge.w + gy * (S.w - e.w);
-        if constexpr (SLOT) {
-          const int64_t s = slot[base + f];
-          if ((uint64_t)s < (uint64_t)nslot) {
-            st4(gvals + s * (D + 4) + q * 4, o4);
-            if (q == 0) st4(gvals + s * (D + 4) + D, make_float4(gy, 0.f, 0.f, 0.f));
-          }
-        } else {
-          st4(gvals + o, o4);
-          if (q == 0) g1vals[base + f] = gy;
-        }
+      for (int k = 0; k < NSTEP; ++k) {
+        const int f = f0 + r + k * RS;
+        if (f < F) store_grad_row<LPR, SLOT>(gvals, g1vals, slot, nslot, base + f, q, fm_grad_row(ge[k], gy, S, e[k]), gy);
       }
     }
   }
@@ -371,6 +365,17 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD(
 //            staged as zeros (x + 0 = x), which keeps the adding loop's trip count fixed.
 constexpr int kLongSeg = 32;
 
+// slot s's lookups are order[beg .. end); an empty range for a slot past the last one or with bounds outside [0, n]
+__device__ __forceinline__ void seg_range(const int32_t *__restrict__ seg, int64_t s, int64_t nslot, int64_t n, int &beg,
+                                          int &end) {
+  beg = end = 0;
+  if (s < nslot) {
+    beg = seg[2 * s];
+    end = seg[2 * s + 1];
+    if (beg < 0 || end > n || end < beg) beg = end = 0;
+  }
+}
+
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restrict__ seg,
                                                         const float *__restrict__ gvals,
@@ -393,12 +398,8 @@ __global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restric
   // ---- phase 1 (+1: the dump row nslot is written as zeros, nobody's gradient)
   for (int64_t tile = wave0; tile * RS < nslot + 1; tile += nwaves) {
     const int64_t s = tile * RS + r;
-    int beg = 0, end = 0;
-    if (s < nslot) {
-      beg = seg[2 * s];
-      end = seg[2 * s + 1];
-      if (beg < 0 || end > n || end < beg) beg = end = 0;
-    }
+    int beg, end;
+    seg_range(seg, s, nslot, n, beg, end);
     if (s > nslot || end - beg > kLongSeg) continue;
     float4 acc = z;
     float a1 = 0.f;
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restric
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (t + u < end) {
-          acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
+          acc4(acc, v[u]);
           a1 += l[u];
         }
       }
@@ -428,12 +429,8 @@ __global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restric
   // ---- phase 2: lane k looks at slot base + k * nwaves + wave0, the wave then takes its long ones in turn
   for (int64_t base = 0; base < nslot; base += (int64_t)kWave * nwaves) {
     const int64_t sl = base + (int64_t)lane * nwaves + wave0;
-    int lb = 0, le = 0;
-    if (sl < nslot) {
-      lb = seg[2 * sl];
-      le = seg[2 * sl + 1];
-      if (lb < 0 || le > n || le < lb) lb = le = 0;
-    }
+    int lb, le;
+    seg_range(seg, sl, nslot, n, lb, le);
     unsigned long long m = __ballot(le - lb > kLongSeg);
     while (m) {
       const int src = __ffsll((long long)m) - 1;
@@ -522,7 +519,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
     float4 S = z;
     for (int f = r; f < F; f += RS) {
       const float4 e = ld4(emb + (base + f) * D + q * 4);
-      S.x += e.x; S.y += e.y; S.z += e.z; S.w += e.w;
+      acc4(S, e);
     }
     S = slot_sum<LPR>(S);
     const int nsteps = NIT > 0 ? NSTEP : (F + RS - 1) / RS;
@@ -537,10 +534,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
         const float4 ge = g_emb ? ld4(g_emb + o) : z;
         row = rows[base + f];
         if ((uint64_t)row >= (uint64_t)N) row = -1;
-        o4.x = ge.x + gy * (S.x - e.x);
-        o4.y = ge.y + gy * (S.y - e.y);
-        o4.z = ge.z + gy * (S.z - e.z);
-        o4.w = ge.w + gy * (S.w - e.w);
+        o4 = fm_grad_row(ge, gy, S, e);
         if (q == 0 && row >= 0) atomicAdd(gw1 + row, gy);
       }
       st4(my + lane * 4, o4);
@@ -733,6 +727,48 @@ inline int nit_for(int F, int LPR) {
     default: CALL(LPR, 0); break;       \
   }
 
+// ---- the forward's one launcher ----
+// the operands the float4 forward takes (the others go to the scalar kernel, or are refused)
+inline bool fwd_float4_ok(int D, const float *W, int64_t ldw, const float *emb_out) {
+  return vec_ok(D) && aligned16(W) && (ldw & 3) == 0 && aligned16(emb_out);
+}
+inline bool fwd_shfl(int F, int nit) { return nit > 0 && F <= kWave; }
+
+// Chooses (LPR, NIT, SHFL), or the scalar kernel, and launches; the entry point has checked its arguments.  offsets == nullptr
+// (the ids are row numbers) is for the float4 form only: k_gather_fm_fwd_anyD reads offsets[f] unconditionally.
+int launch_gather_fm_fwd(const char *name, const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw,
+                         const float *w1, int64_t ldw1, const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out,
+                         float *sum_out, int64_t B, int F, int D, int64_t N, int *err, void *stream) {
+  if (B == 0) return MI_OK;
+  const int grid = grid_for_waves(B);
+  if (fwd_float4_ok(D, W, ldw, emb_out)) {
+    const int lpr = D / 4, nit = nit_for(F, lpr);
+    const bool shfl = fwd_shfl(F, nit);
+    decltype(&k_gather_fm_fwd<1, 0, false>) kernel = nullptr;
+#define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd<LPR, NIT, true> : k_gather_fm_fwd<LPR, NIT, false>
+    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+    MI_LAUNCH(name, kernel, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1,
+              err, sum_out);
+  } else {
+    if (!offsets) return MI_ERR_INVALID_ARG;
+    if (ldw != D || ldw1 != 1) return MI_ERR_UNSUPPORTED;      // the scalar fallback reads the reference's two tensors only
+    MI_LAUNCH(name, k_gather_fm_fwd_anyD, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F,
+              D, N, err, sum_out);
+  }
+  return launch_status();
+}
+
+// mi_gather_fm_fwd_sum: its argument checks, then the launcher (also where mi_gather_fm_fwd_ride ends without a ride)
+int gather_fm_fwd_sum(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1, int64_t ldw1,
+                      const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out, float *sum_out, int64_t B, int F,
+                      int D, int64_t N, int *err, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1) return MI_ERR_INVALID_ARG;
+  if (B > 0 && (!idx || !W || !w1 || !emb_out || !yfm_out)) return MI_ERR_INVALID_ARG;
+  return launch_gather_fm_fwd("gather_fm_fwd", idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F,
+                              D, N, err, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -740,38 +776,14 @@ extern "C" {
 int mi_gather_fm_fwd_sum(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1,
                          int64_t ldw1, const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out, float *sum_out,
                          int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, void *stream) {
-  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1) return MI_ERR_INVALID_ARG;
-  if (B == 0) return MI_OK;
-  if (!idx || !offsets || !W || !w1 || !emb_out || !yfm_out) return MI_ERR_INVALID_ARG;
-  const int grid = grid_for_waves(B);
-  if (vec_ok(D) && aligned16(W) && (ldw & 3) == 0 && aligned16(emb_out)) {
-    const int lpr = D / 4, nit = nit_for(F, lpr);
-    if (nit > 0 && F <= kWave) {
-#define CALL(LPR, NIT)                                                                                \
-  MI_LAUNCH("gather_fm_fwd", (k_gather_fm_fwd<LPR, NIT, true>), grid, kBlock, stream, idx, offsets,   \
-            W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1, err, sum_out)
-      MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
-#undef CALL
-    } else {
-#define CALL(LPR, NIT)                                                                               \
-  MI_LAUNCH("gather_fm_fwd", (k_gather_fm_fwd<LPR, NIT, false>), grid, kBlock, stream, idx, offsets, \
-            W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1, err, sum_out)
-      MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
-#undef CALL
-    }
-  } else {
-    if (ldw != D || ldw1 != 1) return MI_ERR_UNSUPPORTED;      // the scalar fallback reads the reference's two tensors only
-    MI_LAUNCH("gather_fm_fwd", k_gather_fm_fwd_anyD, grid, kBlock, stream, idx, offsets, W, w1,
-              bias, emb_out, yfm_out, rows_out, B, F, D, N, err, sum_out);
-  }
-  return launch_status();
+  return gather_fm_fwd_sum(idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F, D, N, err, stream);
 }
 
 int mi_gather_fm_fwd_ride(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1,
                           int64_t ldw1, const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out, float *sum_out,
                           int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, const mi_tail_mask_ride *ride,
                           void *stream) {
-  if (!ride) return mi_gather_fm_fwd_sum(idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F, D, N, err, stream);
+  if (!ride) return gather_fm_fwd_sum(idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F, D, N, err, stream);
   if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1) return MI_ERR_INVALID_ARG;
   MaskRide r;
   int64_t extra = 0;
@@ -790,8 +802,8 @@ int mi_gather_fm_fwd_ride(const int64_t *idx, const int64_t *offsets, const floa
     if (rc2 != MI_OK) return rc2;
   }
   const int lpr = D / 4, nit = vec_ok(D) ? nit_for(F, lpr) : 0;
-  const bool fits = B > 0 && idx && W && w1 && emb_out && yfm_out && vec_ok(D) && aligned16(W) && (ldw & 3) == 0 &&
-                    aligned16(emb_out) && nit > 0 && F <= kWave;      // (offsets may be NULL: slot lookups, mi_slot_fm_fwd's operands)
+  const bool fits = B > 0 && idx && W && w1 && emb_out && yfm_out && fwd_float4_ok(D, W, ldw, emb_out) &&
+                    fwd_shfl(F, nit);      // (offsets may be NULL: slot lookups, mi_slot_fm_fwd's operands)
   // (mask workgroups: a quarter of what the job would take alone — each walks four strides — so the launch stays one wave
   //  of workgroups over the chip's slots)
   int nmask = (int)((extra + 3) / 4);
@@ -803,7 +815,7 @@ int mi_gather_fm_fwd_ride(const int64_t *idx, const int64_t *offsets, const floa
       const int st = launch_status();
       if (st != MI_OK) return st;
     }
-    return mi_gather_fm_fwd_sum(idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F, D, N, err, stream);
+    return gather_fm_fwd_sum(idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out, sum_out, B, F, D, N, err, stream);
   }
   const int ngather = grid_for_waves(B);
 #define CALL(LPR, NIT)                                                                                         \
@@ -927,26 +939,9 @@ int mi_slot_fm_fwd(const int64_t *slot, const float *buf, int64_t nrows, const f
   if (B < 0 || F < 0 || D <= 0 || nrows < 0) return MI_ERR_INVALID_ARG;
   if (B == 0) return MI_OK;
   if (!slot || !buf || !emb_out || !yfm_out) return MI_ERR_INVALID_ARG;
-  if (!vec_ok(D) || !aligned16(buf) || !aligned16(emb_out)) return MI_ERR_UNSUPPORTED;
-  const int grid = grid_for_waves(B);
-  const int lpr = D / 4, nit = nit_for(F, lpr);
-  const int64_t ld = D + 4;
-  if (nit > 0 && F <= kWave) {
-#define CALL(LPR, NIT)                                                                                 \
-  MI_LAUNCH("slot_fm_fwd", (k_gather_fm_fwd<LPR, NIT, true>), grid, kBlock, stream, slot,              \
-            (const int64_t *)nullptr, buf, buf + D, bias, emb_out, yfm_out, (int64_t *)nullptr,        \
-            B, F, nrows, ld, ld, err, (float *)nullptr)
-    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
-#undef CALL
-  } else {
-#define CALL(LPR, NIT)                                                                               \
-  MI_LAUNCH("slot_fm_fwd", (k_gather_fm_fwd<LPR, NIT, false>), grid, kBlock, stream, slot,           \
-            (const int64_t *)nullptr, buf, buf + D, bias, emb_out, yfm_out, (int64_t *)nullptr,      \
-            B, F, nrows, ld, ld, err, (float *)nullptr)
-    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
-#undef CALL
-  }
-  return launch_status();
+  if (!fwd_float4_ok(D, buf, D + 4, emb_out)) return MI_ERR_UNSUPPORTED;
+  return launch_gather_fm_fwd("slot_fm_fwd", slot, nullptr, buf, D + 4, buf + D, D + 4, bias, emb_out, yfm_out, nullptr,
+                              nullptr, B, F, D, nrows, err, stream);
 }
 
 int mi_slot_fm_bwd(const int64_t *slot, const float *emb, const float *g_y, const float *g_emb,

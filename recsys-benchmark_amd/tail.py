@@ -722,15 +722,8 @@ class DeepFMFusedFn(torch.autograd.Function):
         g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev) if need_w1 else None
         gvals, _, grads, db_head = _tail_backward(ctx.st, saved[:ctx.st.n_saved], g, True, need[11:], False,
                                                   fm=(esum, g1vals, D), beside_wgrad=ctx.prefetch)
-        gvals = gvals.view(B * F, D)
-        stream = _lib.stream_ptr(dev)
-        gW = gw1 = None
-        if need_W:
-            gW = (_kernels._coo(rows, gvals, Wshape) if sparse_W
-                  else _kernels._scatter_rows(rows, gvals, N, D, stream).view(Wshape))
-        if need_w1:
-            gw1 = (_kernels._coo(rows, g1vals.view((-1,) + (1,) * (len(w1shape) - 1)), w1shape) if sparse_w1
-                   else _kernels._scatter_rows(rows, g1vals, N, 1, stream).view(w1shape))
+        gW, gw1 = _kernels._table_grads(rows, gvals.view(B * F, D), g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1,
+                                        need_W, need_w1, _lib.stream_ptr(dev))
         # the scalar bias is added to every logit, like the head's bias: the same gradient, sum_m g[m]
         gb = db_head if (has_bias and need_b) else None            # (the twin word the join wrote: no copy)
         return (None, None, None, None, None, gW, gw1, gb, None, None, None, *grads)

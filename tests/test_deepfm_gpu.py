@@ -116,6 +116,10 @@ CASES = [
     (21, [4, 9, 2], 7),                 # D not a multiple of 4: scalar kernels
     (9, [6, 5], 12),                    # D multiple of 4 but LPR=3 not a power of two: scalar kernels
     (5000, [1000, 3, 70000, 12], 8),    # more samples than resident waves: grid-stride
+    (5, [3] * 100, 4),                  # LPR=1, NIT=2, F > 64: the unrolled form without the shuffled ids
+    (6, [4] * 60, 16),                  # NIT=4 with the shuffled ids
+    (3, [5] * 9, 16),                   # NIT=1
+    (4, [3] * 300, 4),                  # LPR=1, generic NIT=0 loop
 ]
 
 

@@ -121,8 +121,7 @@ def test_gather_pack_rejects_unsupported_width_loudly():
                                   torch.zeros(5, 1, device=DEV))
 
 
-@pytest.mark.parametrize("B,F,D", [(1, 1, 16), (33, 26, 16), (64, 39, 16), (17, 100, 8), (9, 5, 64)])
-def test_slot_fm_forward_backward(B, F, D):
+def _slot_fm_operands(B, F, D):
     g = torch.Generator().manual_seed(B + F + D)
     S = B * F + 11                                     # some slots stay unused (padding)
     buf = torch.randn(S + 1, D + 4, generator=g) * 0.1        # embedding-like magnitudes
@@ -131,6 +130,13 @@ def test_slot_fm_forward_backward(B, F, D):
     slot = torch.randperm(S, generator=g)[:B * F].view(B, F)
     slot[0, 0] = S                                     # one dropped lookup -> the dump row
     bias = torch.tensor([0.3])
+    return g, S, buf, slot, bias
+
+
+# (4, 20, 64): LPR = 16, four rows per step, five steps -> the generic field loop of the forward and of the backward
+@pytest.mark.parametrize("B,F,D", [(1, 1, 16), (33, 26, 16), (64, 39, 16), (17, 100, 8), (9, 5, 64), (4, 20, 64)])
+def test_slot_fm_forward_backward(B, F, D):
+    g, S, buf, slot, bias = _slot_fm_operands(B, F, D)
     g_emb, g_y = torch.randn(B, F, D, generator=g), torch.randn(B, generator=g)
 
     rb, rbias = buf.clone().requires_grad_(True), bias.clone().requires_grad_(True)
@@ -151,6 +157,41 @@ def test_slot_fm_forward_backward(B, F, D):
     unused[slot.view(-1)[slot.view(-1) < S]] = False
     assert not hb.grad[:S][unused.to(DEV)].any()
     assert_close(hbias.grad, rbias.grad, 1e-5, 1e-6, "bias grad")
+    pkg.check_index_errors()
+
+
+def _fwd_ride_without_offsets(slot, buf, bias, D):
+    """mi_gather_fm_fwd_ride on mi_slot_fm_fwd's operands: offsets = NULL, no mask job, no rows_out."""
+    B, F = slot.shape
+    emb = torch.full((B, F, D), float("nan"), device=DEV)
+    yfm = torch.full((B,), float("nan"), device=DEV)
+    esum = torch.full((B, D), float("nan"), device=DEV)
+    rc = _lib.load().mi_gather_fm_fwd_ride(
+        slot.data_ptr(), None, buf.data_ptr(), D + 4, buf.data_ptr() + 4 * D, D + 4, bias.data_ptr(), emb.data_ptr(),
+        yfm.data_ptr(), None, esum.data_ptr(), B, F, D, buf.shape[0], _lib.err_word(DEV).data_ptr(), None,
+        _lib.stream_ptr(DEV))
+    return rc, emb, yfm, esum
+
+
+@pytest.mark.parametrize("B,F,D", [(33, 26, 16), (17, 100, 8)])
+def test_fwd_ride_takes_slot_operands_without_offsets(B, F, D):
+    """The lookup launch of the sharded fused step when it carries no mask job (deterministic mode, ...): ids that are
+    row numbers already, offsets == NULL.  Same kernel as mi_slot_fm_fwd, so the same bits."""
+    _, S, buf, slot, bias = _slot_fm_operands(B, F, D)
+    buf, slot, bias = buf.to(DEV), slot.to(DEV), bias.to(DEV)
+    e_ref, y_ref = _kernels.slot_fm(buf, slot, bias)
+    rc, emb, yfm, esum = _fwd_ride_without_offsets(slot, buf, bias, D)
+    assert rc == 0                                                            # MI_OK
+    assert torch.equal(emb, e_ref) and torch.equal(yfm, y_ref)
+    assert_close(esum, emb.view(B, F, D).sum(1), 1e-5, 1e-5, "sum over the fields")      # fp32 sum order
+    pkg.check_index_errors()
+
+
+def test_fwd_ride_without_offsets_is_refused_on_the_scalar_path():
+    B, F, D = 33, 26, 12                               # D = 12: no float4 form, and the scalar kernel reads offsets[f]
+    _, S, buf, slot, bias = _slot_fm_operands(B, F, D)
+    rc, _, _, _ = _fwd_ride_without_offsets(slot.to(DEV), buf.to(DEV), bias.to(DEV), D)
+    assert rc == -1                                                           # MI_ERR_INVALID_ARG
     pkg.check_index_errors()
 
 

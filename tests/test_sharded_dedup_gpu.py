@@ -132,7 +132,9 @@ def test_route_unique_writes_into_static_buffers():
         assert all(torch.equal(a, b) for a, b in zip(got, fresh))
 
 
-@pytest.mark.parametrize("B,F,D", [(1, 1, 16), (33, 26, 16), (64, 39, 16), (17, 100, 8), (9, 5, 64), (300, 3, 4), (40, 2, 256)])
+# (4, 20, 64): LPR = 16, five steps -> the generic field loop of the slot forward and of the store pass in front of the sums
+@pytest.mark.parametrize("B,F,D", [(1, 1, 16), (33, 26, 16), (64, 39, 16), (17, 100, 8), (9, 5, 64), (300, 3, 4), (40, 2, 256),
+                                   (4, 20, 64)])
 def test_segment_backward_sums_shared_slots(B, F, D):
     """Repeated slots (one of them shared by more than kLongSeg = 32 lookups where the batch allows: the whole-wave
     path), unused slots and a dump-slot lookup, against autograd through the torch restatement."""

@@ -57,11 +57,28 @@ def test_sharded_world1_equals_unsharded(one_rank_group):
     pkg.check_index_errors()
 
 
-@pytest.mark.parametrize("graphed,criterion", [(False, "torch"), (True, "torch"), (True, "package")])
-def test_sharded_training_steps_track_the_unsharded_model(one_rank_group, graphed, criterion):
+@pytest.mark.parametrize("graphed,criterion,deterministic",
+                         [(False, "torch", False), (True, "torch", False), (True, "package", False), (False, "package", True)],
+                         ids=["False-torch", "True-torch", "True-package", "False-package-deterministic"])
+def test_sharded_training_steps_track_the_unsharded_model(one_rank_group, graphed, criterion, deterministic):
     """Same batches, same optimizers: after several steps the shards hold the unsharded model's tables.  criterion "package":
     recsys_benchmark_amd.BCEWithLogitsLoss — the graphed step then hands labels and its 1 / world seed to the local compute and
-    the criterion is evaluated inside the tail's head launch."""
+    the criterion is evaluated inside the tail's head launch.  deterministic: under use_deterministic_algorithms(True) the
+    fused local compute's lookup launch carries no mask job (mi_gather_fm_fwd_ride with ride == NULL on slot operands, i.e.
+    offsets == NULL)."""
+    from recsys_benchmark_amd import _kernels
+
+    before = _kernels.DETERMINISTIC
+    if deterministic != before:
+        pkg.use_deterministic_algorithms(deterministic)
+    try:
+        _sharded_steps_track_the_unsharded_model(graphed, criterion)
+    finally:
+        if deterministic != before:
+            pkg.use_deterministic_algorithms(before)
+
+
+def _sharded_steps_track_the_unsharded_model(graphed, criterion):
     from recsys_benchmark_amd.optim import get_optimizers
 
     torch.manual_seed(4)
