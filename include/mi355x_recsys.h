@@ -137,6 +137,37 @@ MI_API int mi_gather_fm_bwd_dense(const int64_t *rows, const float *emb,
                                   float *gW, float *gw1, float *gbias, int64_t B, int32_t F,
                                   int32_t D, int64_t N, void *stream);
 
+/* ---- the same three kernels with a KEPT WIDTH per looked-up row (DeepFM on OptEmbed) ----
+ * src/models/embeddings/deepfm_opt_embed.py:186-200 (a search candidate: emb * mask_d over the whole table, then the
+ * lookup) and :693-706 (RetrainOptEmbed: _weight * _mask every step) without the masked copy of the table:
+ *   row       = idx[b,f] + offsets[f]
+ *   kept(b,f) = min(keep ? keep[row] : D, fwidth ? fwidth[f] : D)
+ *   emb[b,f,d] = d < kept(b,f) ? W[row,d] : +0;  y_fm over the masked emb; the first-order term is NOT masked
+ * keep    uint8[N], nullable: the row's kept width, 0 = a dead row (the row mask times the per-feature width)
+ * fwidth  int32[F], nullable: one width per field (a search candidate of mode_threshold_d = "field")
+ * A value above D acts as D.  D <= MI_GATHER_FM_MASKED_MAX_D (a width is one byte), else MI_ERR_UNSUPPORTED.
+ * Forward: the other arguments as mi_gather_fm_fwd_ld (out-of-range rows flagged in *err and read as zeros).
+ * Backward, row form: gvals[i,d] = g_emb[i,d] + g_y[b] (S[b,d] - emb[i,d]) for d < kept(i) and exactly 0 past it;
+ *   g1vals[i] = g_y[b]; rows int64[B,F] = the forward's rows_out (needed with keep).
+ * Backward, dense form: the same values scatter-added into the caller-zeroed gW / gw1; an element at or past its row's
+ *   kept width issues no atomic (gW stays the caller's zero there).
+ */
+#define MI_GATHER_FM_MASKED_MAX_D 255
+MI_API int mi_gather_fm_masked_fwd(const int64_t *idx, const int64_t *offsets,
+                                   const float *W, int64_t ldw, const float *w1, int64_t ldw1, const float *bias,
+                                   const uint8_t *keep, const int32_t *fwidth,
+                                   float *emb_out, float *yfm_out, int64_t *rows_out,
+                                   int64_t B, int32_t F, int32_t D, int64_t N,
+                                   int32_t *err, void *stream);
+MI_API int mi_gather_fm_masked_bwd_rows(const int64_t *rows, const uint8_t *keep, const int32_t *fwidth,
+                                        const float *emb, const float *g_y, const float *g_emb,
+                                        float *gvals, float *g1vals, float *gbias,
+                                        int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
+MI_API int mi_gather_fm_masked_bwd_dense(const int64_t *rows, const uint8_t *keep, const int32_t *fwidth,
+                                         const float *emb, const float *g_y, const float *g_emb,
+                                         float *gW, float *gw1, float *gbias,
+                                         int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
+
 /* ---- a2: plain row gather (IEmbedding.forward on a vanilla table) ----------
  * src/models/embeddings/base.py:74-75 (nn.Embedding on int64[n] ids, already
  * offset).  out fp32[n,D].

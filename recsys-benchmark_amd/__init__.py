@@ -8,6 +8,7 @@ from ._lib import MI355XLibraryError, check_index_errors
 from .cf_data import (DeviceCFGraphDataset, DeviceCFLoader, DeviceCFTestDataset, DeviceCFTestLoader, DeviceTruth)
 from .deepfm import DeepFM
 from .embeddings import IEmbedding, NAME_TO_CLS, VanillaEmbedding, get_embedding
+from .embeddings.deepfm_opt_embed import RetrainOptEmbed as DeepFMRetrainOptEmbed, build_retrain_deepfm, evol_search_deepfm
 from .factory import (get_ctr_model, get_graph_model, load_ctr_model, load_graph_model, save_cf_emb_checkpoint,
                       save_ctr_checkpoint)
 from .hccf import HCCFModelCore
@@ -51,5 +52,6 @@ __all__ = [
     "LightGCN", "SingleLightGCN", "HCCFModelCore", "get_ctr_model", "get_graph_model", "load_ctr_model", "load_graph_model",
     "save_cf_emb_checkpoint", "save_ctr_checkpoint", "MI355XLibraryError", "check_index_errors", "use_deterministic_algorithms",
     "BCEWithLogitsLoss", "NeuMF", "ModelFlag", "prune", "prune_table", "to_pruned_tables", "evaluate_pruned", "search_min_item",
+    "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm",
     "DeviceCFGraphDataset", "DeviceCFLoader", "DeviceCFTestDataset", "DeviceCFTestLoader", "DeviceTruth",
 ]

@@ -87,18 +87,43 @@ def sort_field_rows(rows_flat: torch.Tensor, N: int):
     return rows_sorted, perm
 
 
+MASKED_MAX_D = 255      # MI_GATHER_FM_MASKED_MAX_D: a kept width is one byte
+
+
+def _mask_operands(keep, fwidth, N: int, F: int):
+    """The two width sources of the masked gather_fm as the kernels read them: keep uint8 [N], fwidth int32 [F]."""
+    if keep is not None:
+        if keep.dtype != torch.uint8 or keep.numel() != N:
+            raise ValueError(f"keep must be uint8 [{N}], got {keep.dtype} {tuple(keep.shape)}")
+        keep = keep.contiguous()
+    if fwidth is not None:
+        if fwidth.dtype != torch.int32 or fwidth.numel() != F:
+            raise ValueError(f"fwidth must be int32 [{F}], got {fwidth.dtype} {tuple(fwidth.shape)}")
+        fwidth = fwidth.contiguous()
+    return keep, fwidth
+
+
 class GatherFM(torch.autograd.Function):
     """emb, y_fm = gather+FM+first-order (src/models/deepfm.py:88-98) in one kernel.
 
     sparse_W / sparse_w1 choose the gradient form of the two tables: row form
     (uncoalesced COO, what nn.Embedding(sparse=True) yields) or the reference's
     default dense weight.grad.
+
+    keep (uint8 [N]) / fwidth (int32 [F]), either or both: the kept-width form (mi_gather_fm_masked_*) —
+    emb[b, f, d] = W[row, d] for d < min(keep[row], fwidth[f]) and +0 past it, y_fm over the masked emb, the first-order
+    term unmasked; the table's gradient is exactly zero at the masked positions.  With both None every call is the
+    unmasked one.
     """
 
     @staticmethod
-    def forward(ctx, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool):
-        dev = _lib.require_gpu(idx, offsets, W, w1, bias)
+    def forward(ctx, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool, keep=None, fwidth=None):
+        dev = _lib.require_gpu(idx, offsets, W, w1, bias, keep, fwidth)
         lib = _lib.load()
+        masked = keep is not None or fwidth is not None
+        if masked and W.shape[-1] > MASKED_MAX_D:
+            raise NotImplementedError(f"the masked gather_fm keeps one byte per width: D <= {MASKED_MAX_D}, got "
+                                      f"{W.shape[-1]}")
         idx = _i64c(idx)
         offsets = _i64c(offsets.reshape(-1))
         if _float4_rows(W.shape[-1]):
@@ -116,17 +141,29 @@ class GatherFM(torch.autograd.Function):
         emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)
-        _lib.check(
-            lib.mi_gather_fm_fwd_ld(
-                idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
-                emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
-                _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
-            ),
-            "mi_gather_fm_fwd_ld",
-        )
+        if masked:
+            keep, fwidth = _mask_operands(keep, fwidth, N, F)
+            _lib.check(
+                lib.mi_gather_fm_masked_fwd(
+                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
+                    _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
+                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+                ),
+                "mi_gather_fm_masked_fwd",
+            )
+        else:
+            _lib.check(
+                lib.mi_gather_fm_fwd_ld(
+                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
+                    emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
+                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+                ),
+                "mi_gather_fm_fwd_ld",
+            )
         if sparse_W or sparse_w1 or DETERMINISTIC:
             note_field_layout(rows, offsets, N)
         ctx.save_for_backward(emb, rows)
+        ctx.mask = (keep, fwidth) if masked else None      # (constants of the step, not autograd inputs)
         ctx.shapes = (B, F, D, N, tuple(W.shape), tuple(w1.shape))
         ctx.sparse = (sparse_W, sparse_w1)
         ctx.has_bias = bias is not None
@@ -158,23 +195,41 @@ class GatherFM(torch.autograd.Function):
         if rows_form:
             gvals = torch.empty((B * F, D), dtype=torch.float32, device=dev)
             g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev)
-            _lib.check(
-                lib.mi_gather_fm_bwd_rows(emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb),
-                                          gvals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb), B, F, D, stream),
-                "mi_gather_fm_bwd_rows",
-            )
+            if ctx.mask is not None:
+                keep, fwidth = ctx.mask
+                _lib.check(
+                    lib.mi_gather_fm_masked_bwd_rows(rows.data_ptr(), _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(),
+                                                     g_y.data_ptr(), _lib.ptr(g_emb), gvals.data_ptr(), g1vals.data_ptr(),
+                                                     _lib.ptr(gb), B, F, D, N, stream),
+                    "mi_gather_fm_masked_bwd_rows",
+                )
+            else:
+                _lib.check(
+                    lib.mi_gather_fm_bwd_rows(emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb),
+                                              gvals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb), B, F, D, stream),
+                    "mi_gather_fm_bwd_rows",
+                )
             gb_done = True
             gW, gw1 = _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1,
                                    stream)
         elif dense_form:
             gWd = torch.zeros((N, D), dtype=torch.float32, device=dev)
             gw1d = torch.zeros((N,), dtype=torch.float32, device=dev)
-            _lib.check(
-                lib.mi_gather_fm_bwd_dense(rows.data_ptr(), emb.data_ptr(), g_y.data_ptr(),
-                                           _lib.ptr(g_emb), gWd.data_ptr(), gw1d.data_ptr(),
-                                           _lib.ptr(gb), B, F, D, N, stream),
-                "mi_gather_fm_bwd_dense",
-            )
+            if ctx.mask is not None:
+                keep, fwidth = ctx.mask
+                _lib.check(
+                    lib.mi_gather_fm_masked_bwd_dense(rows.data_ptr(), _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(),
+                                                      g_y.data_ptr(), _lib.ptr(g_emb), gWd.data_ptr(), gw1d.data_ptr(),
+                                                      _lib.ptr(gb), B, F, D, N, stream),
+                    "mi_gather_fm_masked_bwd_dense",
+                )
+            else:
+                _lib.check(
+                    lib.mi_gather_fm_bwd_dense(rows.data_ptr(), emb.data_ptr(), g_y.data_ptr(),
+                                               _lib.ptr(g_emb), gWd.data_ptr(), gw1d.data_ptr(),
+                                               _lib.ptr(gb), B, F, D, N, stream),
+                    "mi_gather_fm_bwd_dense",
+                )
             gb_done = True
             if need_W:
                 gW = gWd.view(Wshape)
@@ -182,7 +237,7 @@ class GatherFM(torch.autograd.Function):
                 gw1 = gw1d.view(w1shape)
         if gb is not None and not gb_done:          # neither table needs a gradient: nothing was launched
             gb = g_y.sum().view(1)
-        return None, None, gW, gw1, gb, None, None
+        return None, None, gW, gw1, gb, None, None, None, None
 
 
 # Deterministic mode (recsys_benchmark_amd.use_deterministic_algorithms): dense table gradients are built by SORTING the
@@ -240,8 +295,8 @@ def _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1
     return gW, gw1
 
 
-def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False):
-    emb, yfm, _rows = GatherFM.apply(idx, offsets, W, w1, bias, sparse_W, sparse_w1)
+def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False, keep=None, fwidth=None):
+    emb, yfm, _rows = GatherFM.apply(idx, offsets, W, w1, bias, sparse_W, sparse_w1, keep, fwidth)
     return emb, yfm
 
 

@@ -32,6 +32,9 @@ SIGNATURES = {
     "mi_prefetch_rows": [_p, _p, _p, _i64, _p, _i64, _i64, _i32, _i64, _p],
     "mi_gather_fm_bwd_rows": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p],
     "mi_gather_fm_bwd_dense": [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_fm_masked_fwd": [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_gather_fm_masked_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_fm_masked_bwd_dense": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
     "mi_gather_rows_fwd": [_p, _p, _p, _i64, _i32, _i64, _p, _p],
     "mi_scatter_add_rows": [_p, _p, _p, _i64, _i32, _i64, _p],
     "mi_fm_fwd": [_p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],

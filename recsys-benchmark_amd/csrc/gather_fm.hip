@@ -17,6 +17,8 @@
 // HBM-bound integer/copy work: no LDS staging is needed in the forward (each
 // byte is used once); the dense backward stages a 1 KiB tile per wave in LDS to
 // turn 16-B-strided float4 fragments into 256-B contiguous atomic instructions.
+#include <type_traits>
+
 #include "common.hpp"
 #include "prefetch_rows.hpp"
 #include "tail_masks.hpp"
@@ -50,6 +52,43 @@ __device__ __forceinline__ void store_grad_row(float *__restrict__ gvals, float 
   }
 }
 
+// The masked lookups (mi_gather_fm_masked_*) keep a PREFIX of every looked-up row:
+//   kept(b, f) = min(keep ? keep[row] : D, fwidth ? fwidth[f] : D),   emb[b, f, d] = d < kept ? W[row, d] : +0
+// keep uint8[N] (0 = a dead row), fwidth int32[F]; a value above D acts as D (d never reaches it), a negative fwidth as 0.
+// The lane's float4 holds columns q*4 .. q*4+3.  ONE vector select, not four scalar ones: behind scalar selects the
+// compiler turns dot4(v, v) into packed multiplies and adds instead of the unmasked kernels' fused multiply-add chain, and
+// y_fm under keep = D then differs from the unmasked kernel's in the last bit (tests/test_optembed_deepfm_gpu.py holds the
+// two to equal bits).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 keep_prefix(float4 v, int q, int kw) {
+  const i32x4 col = {0, 1, 2, 3};
+  const i32x4 c = (col + q * 4) < kw;
+  f32x4 x = {v.x, v.y, v.z, v.w};
+  x = c ? x : (f32x4)(0.f);
+  return make_float4(x.x, x.y, x.z, x.w);
+}
+__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+// the kept width of lookup i (field f) in the backward: `rows` is the forward's rows_out; a row it flagged keeps nothing
+__device__ __forceinline__ int kept_width(const int64_t *__restrict__ rows, const uint8_t *__restrict__ keep,
+                                          const int32_t *__restrict__ fwidth, int64_t i, int f, int64_t N, int D) {
+  int kw = fwidth ? fwidth[f] : D;
+  if (keep) {
+    const int64_t row = rows[i];
+    kw = (uint64_t)row < (uint64_t)N ? imin(kw, (int)keep[row]) : 0;
+  }
+  return kw;
+}
+struct KeptWidths {      // (the same operands as one kernel argument)
+  const int64_t *rows;
+  const uint8_t *keep;
+  const int32_t *fwidth;
+  int64_t N;
+};
+__device__ __forceinline__ int kept_width(KeptWidths m, int64_t i, int f, int D) {
+  return kept_width(m.rows, m.keep, m.fwidth, i, f, m.N, D);
+}
+
 // ---------------------------------------------------------------- forward ----
 // SHFL (F <= 64): the sample's F ids arrive by ONE coalesced load (lane l < F takes idx[b, l] + offsets[l]) and reach
 // the row slots by shuffles — one dependent vector-memory instruction in front of the row gathers instead of NIT id
@@ -62,12 +101,17 @@ __device__ __forceinline__ void store_grad_row(float *__restrict__ gvals, float 
 // lookup received (route.hip).
 // (SHFL is ignored by the generic NIT = 0 form.)
 // (blk of nblk: the workgroups of the launch that gather — a launch may carry others, k_gather_fm_fwd_ride)
-template <int LPR, int NIT, bool SHFL>
+// MASK: the kept-width form.  The keep[row] byte is loaded in the SAME step as the row gather it belongs to (both need
+// only the row id: one round trip, not two; the LPR lanes of a row slot read the same byte, one request), fwidth[f]
+// arrives like offsets[f] — in SHFL form once per wave, next to offsets[lane], and by shuffle from there.  Every row is
+// gathered whole whatever its width: the gather does not wait for the byte.  Without MASK none of this is compiled.
+template <int LPR, int NIT, bool SHFL, bool MASK = false>
 __device__ __forceinline__ void gather_fm_fwd_blocks(
     const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
     const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
     float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
-    int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out, int blk, int nblk) {
+    int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out, int blk, int nblk,
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
   const int lane = threadIdx.x & 63;
@@ -78,6 +122,8 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
   int bad = 0;
   int64_t myoff = 0;
   if constexpr (SHFL) myoff = (offsets && lane < F) ? offsets[lane] : 0;
+  int myfw = D;
+  if constexpr (SHFL && MASK) myfw = (fwidth && lane < F) ? fwidth[lane] : D;
 
   for (int64_t b = wave0; b < B; b += nwaves) {
     float4 S = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -88,6 +134,7 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
       bool act[NIT], ok[NIT];
       float4 v[NIT];
       float l[NIT];
+      int kw[NIT];      // (MASK only) the field's width, then the lookup's kept width
       if constexpr (SHFL) {
         const int64_t mine = lane < F ? idx[base + lane] + myoff : 0;
         if (rows_out && lane < F) rows_out[base + lane] = mine;
@@ -96,6 +143,7 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
           const int f = r + k * RS;
           act[k] = f < F;
           row[k] = __shfl(mine, f & 63);
+          if constexpr (MASK) kw[k] = __shfl(myfw, f & 63);
         }
       } else {
 #pragma unroll
@@ -103,6 +151,7 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
           const int f = r + k * RS;
           act[k] = f < F;
           row[k] = act[k] ? idx[base + f] + (offsets ? offsets[f] : 0) : 0;
+          if constexpr (MASK) kw[k] = (act[k] && fwidth) ? fwidth[f] : D;
         }
       }
 #pragma unroll
@@ -111,10 +160,12 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
         bad |= (act[k] && !ok[k]);
         v[k] = ok[k] ? ld4(W + row[k] * ldw + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         l[k] = (ok[k] && q == 0) ? w1[row[k] * ldw1] : 0.f;
+        if constexpr (MASK) kw[k] = imin(kw[k], (ok[k] && keep) ? (int)keep[row[k]] : D);
       }
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
         const int f = r + k * RS;
+        if constexpr (MASK) v[k] = keep_prefix(v[k], q, kw[k]);
         if (act[k]) {
           st4_nt(emb + (base + f) * D + q * 4, v[k]);
           if (!SHFL && rows_out && q == 0) rows_out[base + f] = row[k];
@@ -128,7 +179,11 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
         const int64_t row = idx[base + f] + (offsets ? offsets[f] : 0);
         const bool ok = (uint64_t)row < (uint64_t)N;
         bad |= !ok;
-        const float4 v = ok ? ld4(W + row * ldw + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 v = ok ? ld4(W + row * ldw + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (MASK) {
+          const int kb = (ok && keep) ? (int)keep[row] : D;
+          v = keep_prefix(v, q, imin(kb, fwidth ? fwidth[f] : D));
+        }
         if (ok && q == 0) lin += w1[row * ldw1];
         st4(emb + (base + f) * D + q * 4, v);
         if (rows_out && q == 0) rows_out[base + f] = row;
@@ -155,6 +210,16 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_fwd(
     int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out) {
   gather_fm_fwd_blocks<LPR, NIT, SHFL>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, N, ldw, ldw1, err, sum_out,
                                        (int)blockIdx.x, (int)gridDim.x);
+}
+template <int LPR, int NIT, bool SHFL>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_masked(
+    const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
+    const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
+    float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
+    int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth) {
+  gather_fm_fwd_blocks<LPR, NIT, SHFL, true>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, N, ldw, ldw1, err, sum_out,
+                                             (int)blockIdx.x, (int)gridDim.x, keep, fwidth);
 }
 // The same launch carrying the MLP tail's dropout keep bits and the zero fill of its accumulation buffer in workgroups
 // past the first `ngather` (tail_masks.hpp): in DeepFM's fused step this kernel is the first of the step, every reader of
@@ -187,11 +252,13 @@ __global__ __launch_bounds__(kBlock) void k_mask_job(MaskRide ride) {
 }
 
 // Any D (scalar accesses): wave per sample, lanes stride over d.
-__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD(
+template <bool MASK>
+__device__ __forceinline__ void gather_fm_fwd_anyD_blocks(
     const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
     const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
     float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
-    int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out) {
+    int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out,
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
@@ -212,7 +279,11 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD(
           if (rows_out) rows_out[base + f] = row;
         }
         if (d < D) {
-          const float v = ok ? W[row * D + d] : 0.f;
+          float v = ok ? W[row * D + d] : 0.f;
+          if constexpr (MASK) {
+            const int kb = (ok && keep) ? (int)keep[row] : D;
+            v = d < imin(kb, fwidth ? fwidth[f] : D) ? v : 0.f;
+          }
           emb[(base + f) * D + d] = v;
           S += v;
           ss += v * v;
@@ -225,6 +296,21 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD(
     if (lane == 0) yfm[b] = t + bv;
   }
   if (bad && err) atomicOr(err, MI_IDX_OUT_OF_RANGE);
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD(
+    const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
+    const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
+    float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
+    int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out) {
+  gather_fm_fwd_anyD_blocks<false>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, D, N, err, sum_out);
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD_masked(
+    const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
+    const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
+    float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
+    int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth) {
+  gather_fm_fwd_anyD_blocks<true>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, D, N, err, sum_out, keep, fwidth);
 }
 
 // bias gradient = sum_b g_y[b] (the bias is added to every sample's y_fm): ONE EXTRA workgroup of a backward launch —
@@ -289,14 +375,19 @@ __device__ __forceinline__ void load_chunk(const float *__restrict__ emb, const 
 // The gradient rows, stored by store_grad_row in either form.  NIT > 0: e[] and g_emb's rows are read once, all NIT loads
 // in flight, and e[] stays in registers between the sum over the fields and the write; NIT = 0: one-step chunks, e read
 // again in the second walk.
-template <int LPR, int NIT, bool SLOT>
+// The masked form (mi_gather_fm_masked_bwd_rows) is this kernel with ONE more argument, a KeptWidths, as the pack M
+// (empty otherwise: the plain kernel's arguments and code are what they were): columns at or past the lookup's kept
+// width are stored as exact zeros (emb holds zeros there already, so S needs nothing).
+template <int LPR, int NIT, bool SLOT, class... M>
 __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
     const float *__restrict__ emb, const float *__restrict__ g_y,
     const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
-    int64_t B, int F, const int64_t *__restrict__ slot, int64_t nslot, float *__restrict__ gbias) {
+    int64_t B, int F, const int64_t *__restrict__ slot, int64_t nslot, float *__restrict__ gbias, M... m) {
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
   constexpr int NSTEP = NIT > 0 ? NIT : 1;
+  constexpr bool MASK = sizeof...(M) > 0;
+  static_assert(sizeof...(M) <= 1 && (std::is_same_v<M, KeptWidths> && ...), "the pack is empty or one KeptWidths");
   int blk, nblk;
   if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   const int lane = threadIdx.x & 63;
@@ -311,6 +402,14 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
     const float gy = g_y[b];
     float4 S = z;
     float4 e[NSTEP], ge[NSTEP];
+    int kw[NSTEP];      // (MASK only)
+    if constexpr (MASK && NIT > 0) {      // the ids and their bytes travel with the rows of e / g_emb
+#pragma unroll
+      for (int k = 0; k < NSTEP; ++k) {
+        const int f = r + k * RS;
+        kw[k] = f < F ? kept_width(m..., base + f, f, D) : 0;
+      }
+    }
     for (int f0 = 0; f0 < fend; f0 += NSTEP * RS) {
       load_chunk<LPR, NSTEP>(emb, NIT > 0 ? g_emb : nullptr, base, f0 + r, F, q, e, ge);
 #pragma unroll
@@ -322,18 +421,25 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows(
 #pragma unroll
       for (int k = 0; k < NSTEP; ++k) {
         const int f = f0 + r + k * RS;
-        if (f < F) store_grad_row<LPR, SLOT>(gvals, g1vals, slot, nslot, base + f, q, fm_grad_row(ge[k], gy, S, e[k]), gy);
+        if (f < F) {
+          float4 o4 = fm_grad_row(ge[k], gy, S, e[k]);
+          if constexpr (MASK) {
+            if constexpr (NIT == 0) kw[k] = kept_width(m..., base + f, f, D);
+            o4 = keep_prefix(o4, q, kw[k]);
+          }
+          store_grad_row<LPR, SLOT>(gvals, g1vals, slot, nslot, base + f, q, o4, gy);
+        }
       }
     }
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD(
+template <bool MASK>
+__device__ __forceinline__ void gather_fm_bwd_rows_anyD_blocks(
     const float *__restrict__ emb, const float *__restrict__ g_y,
     const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
-    int64_t B, int F, int D, float *__restrict__ gbias) {
-  int blk, nblk;
-  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+    int64_t B, int F, int D, int blk, int nblk, const int64_t *__restrict__ rows = nullptr,
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr, int64_t N = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
@@ -346,10 +452,29 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD(
       for (int f = 0; f < F; ++f) S += emb[(base + f) * D + d];
       for (int f = 0; f < F; ++f) {
         const int64_t o = (base + f) * D + d;
-        gvals[o] = (g_emb ? g_emb[o] : 0.f) + gy * (S - emb[o]);
+        float g = (g_emb ? g_emb[o] : 0.f) + gy * (S - emb[o]);
+        if constexpr (MASK) g = d < kept_width(rows, keep, fwidth, base + f, f, N, D) ? g : 0.f;
+        gvals[o] = g;
       }
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD(
+    const float *__restrict__ emb, const float *__restrict__ g_y,
+    const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
+    int64_t B, int F, int D, float *__restrict__ gbias) {
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_rows_anyD_blocks<false>(emb, g_y, g_emb, gvals, g1vals, B, F, D, blk, nblk);
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD_masked(
+    const float *__restrict__ emb, const float *__restrict__ g_y,
+    const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
+    int64_t B, int F, int D, float *__restrict__ gbias, const int64_t *__restrict__ rows,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth, int64_t N) {
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_rows_anyD_blocks<true>(emb, g_y, g_emb, gvals, g1vals, B, F, D, blk, nblk, rows, keep, fwidth, N);
 }
 
 // ------------------------------------------- backward, summed per slot ----
@@ -494,16 +619,17 @@ __global__ __launch_bounds__(kBlock) void k_segment_sum(const int32_t *__restric
 // covers 64 CONSECUTIVE floats of the tile: whole 256-B runs per row (D >= 64)
 // or 64/D whole rows (D < 64) — the shape global float atomics run fastest at
 // (MI355X_MICROARCH.md, "Global float atomics").
-template <int LPR, int NIT>
-__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
+// MASK (mi_gather_fm_masked_bwd_dense): an element at or past its row's kept width issues NO atomic — gW stays the
+// caller's zero there, and a table kept to a fifth sends a fifth of the atomic traffic.  The first-order adds are unmasked.
+// (slab: the workgroup's kWavesPerBlock x 256 floats of LDS, declared by the kernel)
+template <int LPR, int NIT, bool MASK = false>
+__device__ __forceinline__ void gather_fm_bwd_dense_blocks(
     const int64_t *__restrict__ rows, const float *__restrict__ emb,
     const float *__restrict__ g_y, const float *__restrict__ g_emb,
-    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int64_t N, float *__restrict__ gbias) {
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int64_t N, float (*slab)[kWave * 4], int blk, int nblk,
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
-  __shared__ float slab[kWavesPerBlock][kWave * 4];
-  int blk, nblk;
-  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   const int q = lane % LPR, r = lane / LPR;
@@ -528,12 +654,17 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
       const bool act = f < F;
       int64_t row = -1;
       float4 o4 = z;
+      int kw = 0;      // (MASK only)
       if (act) {
         const int64_t o = (base + f) * D + q * 4;
         const float4 e = ld4(emb + o);
         const float4 ge = g_emb ? ld4(g_emb + o) : z;
         row = rows[base + f];
         if ((uint64_t)row >= (uint64_t)N) row = -1;
+        if constexpr (MASK) {
+          kw = fwidth ? fwidth[f] : D;
+          if (keep && row >= 0) kw = imin(kw, (int)keep[row]);
+        }
         o4 = fm_grad_row(ge, gy, S, e);
         if (q == 0 && row >= 0) atomicAdd(gw1 + row, gy);
       }
@@ -546,20 +677,46 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
         const int tr = el / D, tc = el % D;
         const int64_t trow = __shfl(row, tr * LPR);
         const float val = my[el];
-        if (trow >= 0) atomicAdd(gW + trow * D + tc, val);
+        if constexpr (MASK) {
+          const int tkw = __shfl(kw, tr * LPR);
+          if (trow >= 0 && tc < tkw) atomicAdd(gW + trow * D + tc, val);
+        } else {
+          if (trow >= 0) atomicAdd(gW + trow * D + tc, val);
+        }
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
   }
 }
-
-__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense_anyD(
+template <int LPR, int NIT>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense(
     const int64_t *__restrict__ rows, const float *__restrict__ emb,
     const float *__restrict__ g_y, const float *__restrict__ g_emb,
-    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int D, int64_t N, float *__restrict__ gbias) {
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int64_t N, float *__restrict__ gbias) {
+  __shared__ float slab[kWavesPerBlock][kWave * 4];
   int blk, nblk;
   if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_dense_blocks<LPR, NIT>(rows, emb, g_y, g_emb, gW, gw1, B, F, N, slab, blk, nblk);
+}
+template <int LPR, int NIT>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense_masked(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb,
+    const float *__restrict__ g_y, const float *__restrict__ g_emb,
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int64_t N, float *__restrict__ gbias,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth) {
+  __shared__ float slab[kWavesPerBlock][kWave * 4];
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_dense_blocks<LPR, NIT, true>(rows, emb, g_y, g_emb, gW, gw1, B, F, N, slab, blk, nblk, keep, fwidth);
+}
+
+template <bool MASK>
+__device__ __forceinline__ void gather_fm_bwd_dense_anyD_blocks(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb,
+    const float *__restrict__ g_y, const float *__restrict__ g_emb,
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int D, int64_t N, int blk, int nblk,
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
@@ -576,11 +733,29 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense_anyD(
       for (int f = 0; f < F; ++f) {
         const int64_t o = (base + f) * D + d;
         const int64_t row = rows[base + f];
-        if ((uint64_t)row < (uint64_t)N)
-          atomicAdd(gW + row * D + d, (g_emb ? g_emb[o] : 0.f) + gy * (S - emb[o]));
+        bool add = (uint64_t)row < (uint64_t)N;
+        if constexpr (MASK) add = add && d < kept_width(rows, keep, fwidth, base + f, f, N, D);
+        if (add) atomicAdd(gW + row * D + d, (g_emb ? g_emb[o] : 0.f) + gy * (S - emb[o]));
       }
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense_anyD(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb,
+    const float *__restrict__ g_y, const float *__restrict__ g_emb,
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int D, int64_t N, float *__restrict__ gbias) {
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_dense_anyD_blocks<false>(rows, emb, g_y, g_emb, gW, gw1, B, F, D, N, blk, nblk);
+}
+__global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_dense_anyD_masked(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb,
+    const float *__restrict__ g_y, const float *__restrict__ g_emb,
+    float *__restrict__ gW, float *__restrict__ gw1, int64_t B, int F, int D, int64_t N, float *__restrict__ gbias,
+    const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth) {
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  gather_fm_bwd_dense_anyD_blocks<true>(rows, emb, g_y, g_emb, gW, gw1, B, F, D, N, blk, nblk, keep, fwidth);
 }
 
 // ------------------------------------------------- next batch's table lines ----
@@ -736,25 +911,41 @@ inline bool fwd_shfl(int F, int nit) { return nit > 0 && F <= kWave; }
 
 // Chooses (LPR, NIT, SHFL), or the scalar kernel, and launches; the entry point has checked its arguments.  offsets == nullptr
 // (the ids are row numbers) is for the float4 form only: k_gather_fm_fwd_anyD reads offsets[f] unconditionally.
+// MASK: the kept-width kernels of the same (LPR, NIT, SHFL) choice, with keep / fwidth behind the common operands.
+template <bool MASK = false>
 int launch_gather_fm_fwd(const char *name, const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw,
                          const float *w1, int64_t ldw1, const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out,
-                         float *sum_out, int64_t B, int F, int D, int64_t N, int *err, void *stream) {
+                         float *sum_out, int64_t B, int F, int D, int64_t N, int *err, void *stream,
+                         const uint8_t *keep = nullptr, const int32_t *fwidth = nullptr) {
   if (B == 0) return MI_OK;
   const int grid = grid_for_waves(B);
   if (fwd_float4_ok(D, W, ldw, emb_out)) {
     const int lpr = D / 4, nit = nit_for(F, lpr);
     const bool shfl = fwd_shfl(F, nit);
-    decltype(&k_gather_fm_fwd<1, 0, false>) kernel = nullptr;
-#define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd<LPR, NIT, true> : k_gather_fm_fwd<LPR, NIT, false>
-    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+    if constexpr (MASK) {
+      decltype(&k_gather_fm_fwd_masked<1, 0, false>) kernel = nullptr;
+#define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd_masked<LPR, NIT, true> : k_gather_fm_fwd_masked<LPR, NIT, false>
+      MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
 #undef CALL
-    MI_LAUNCH(name, kernel, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1,
-              err, sum_out);
+      MI_LAUNCH(name, kernel, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1,
+                err, sum_out, keep, fwidth);
+    } else {
+      decltype(&k_gather_fm_fwd<1, 0, false>) kernel = nullptr;
+#define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd<LPR, NIT, true> : k_gather_fm_fwd<LPR, NIT, false>
+      MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+      MI_LAUNCH(name, kernel, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1,
+                err, sum_out);
+    }
   } else {
     if (!offsets) return MI_ERR_INVALID_ARG;
     if (ldw != D || ldw1 != 1) return MI_ERR_UNSUPPORTED;      // the scalar fallback reads the reference's two tensors only
-    MI_LAUNCH(name, k_gather_fm_fwd_anyD, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F,
-              D, N, err, sum_out);
+    if constexpr (MASK)
+      MI_LAUNCH(name, k_gather_fm_fwd_anyD_masked, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out,
+                B, F, D, N, err, sum_out, keep, fwidth);
+    else
+      MI_LAUNCH(name, k_gather_fm_fwd_anyD, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F,
+                D, N, err, sum_out);
   }
   return launch_status();
 }
@@ -875,6 +1066,63 @@ int mi_gather_fm_bwd_dense(const int64_t *rows, const float *emb, const float *g
   } else {
     MI_LAUNCH("gather_fm_bwd_dense", k_gather_fm_bwd_dense_anyD, grid, kBlock, stream, rows, emb,
               g_y, g_emb, gW, gw1, B, F, D, N, gbias);
+  }
+  return launch_status();
+}
+
+// ---- the kept-width forms (DeepFM on OptEmbed: a search candidate's eval lookup, the retraining table) ----
+int mi_gather_fm_masked_fwd(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1,
+                            int64_t ldw1, const float *bias, const uint8_t *keep, const int32_t *fwidth, float *emb_out,
+                            float *yfm_out, int64_t *rows_out, int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err,
+                            void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1) return MI_ERR_INVALID_ARG;
+  if (D > MI_GATHER_FM_MASKED_MAX_D) return MI_ERR_UNSUPPORTED;      // a kept width is one byte
+  if (B > 0 && (!idx || !W || !w1 || !emb_out || !yfm_out)) return MI_ERR_INVALID_ARG;
+  return launch_gather_fm_fwd<true>("gather_fm_masked_fwd", idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out, rows_out,
+                                    nullptr, B, F, D, N, err, stream, keep, fwidth);
+}
+
+int mi_gather_fm_masked_bwd_rows(const int64_t *rows, const uint8_t *keep, const int32_t *fwidth, const float *emb,
+                                 const float *g_y, const float *g_emb, float *gvals, float *g1vals, float *gbias, int64_t B,
+                                 int32_t F, int32_t D, int64_t N, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0) return MI_ERR_INVALID_ARG;
+  if (D > MI_GATHER_FM_MASKED_MAX_D) return MI_ERR_UNSUPPORTED;
+  if (B == 0) return MI_OK;
+  if (!emb || !g_y || !gvals || !g1vals || (keep && !rows)) return MI_ERR_INVALID_ARG;
+  const int grid = grid_for_waves(B) + (gbias ? 1 : 0);      // + the workgroup that only sums the bias gradient
+  const KeptWidths kept = {rows, keep, fwidth, N};
+  if (vec_ok(D) && aligned16(emb) && aligned16(gvals) && (!g_emb || aligned16(g_emb))) {
+    const int lpr = D / 4, nit = nit_for(F, lpr);
+#define CALL(LPR, NIT)                                                                                      \
+  MI_LAUNCH("gather_fm_masked_bwd_rows", (k_gather_fm_bwd_rows<LPR, NIT, false, KeptWidths>), grid, kBlock, stream, emb, \
+            g_y, g_emb, gvals, g1vals, B, F, (const int64_t *)nullptr, (int64_t)0, gbias, kept)
+    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+  } else {
+    MI_LAUNCH("gather_fm_masked_bwd_rows", k_gather_fm_bwd_rows_anyD_masked, grid, kBlock, stream, emb, g_y, g_emb, gvals,
+              g1vals, B, F, D, gbias, rows, keep, fwidth, N);
+  }
+  return launch_status();
+}
+
+int mi_gather_fm_masked_bwd_dense(const int64_t *rows, const uint8_t *keep, const int32_t *fwidth, const float *emb,
+                                  const float *g_y, const float *g_emb, float *gW, float *gw1, float *gbias, int64_t B,
+                                  int32_t F, int32_t D, int64_t N, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0) return MI_ERR_INVALID_ARG;
+  if (D > MI_GATHER_FM_MASKED_MAX_D) return MI_ERR_UNSUPPORTED;
+  if (B == 0) return MI_OK;
+  if (!rows || !emb || !g_y || !gW || !gw1) return MI_ERR_INVALID_ARG;
+  const int grid = grid_for_waves(B) + (gbias ? 1 : 0);      // + the workgroup that only sums the bias gradient
+  if (vec_ok(D) && aligned16(emb) && (!g_emb || aligned16(g_emb))) {
+    const int lpr = D / 4, nit = nit_for(F, lpr);
+#define CALL(LPR, NIT)                                                                                        \
+  MI_LAUNCH("gather_fm_masked_bwd_dense", (k_gather_fm_bwd_dense_masked<LPR, NIT>), grid, kBlock, stream, rows, \
+            emb, g_y, g_emb, gW, gw1, B, F, N, gbias, keep, fwidth)
+    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+  } else {
+    MI_LAUNCH("gather_fm_masked_bwd_dense", k_gather_fm_bwd_dense_anyD_masked, grid, kBlock, stream, rows, emb, g_y, g_emb,
+              gW, gw1, B, F, D, N, gbias, keep, fwidth);
   }
   return launch_status();
 }

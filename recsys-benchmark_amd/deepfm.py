@@ -10,6 +10,7 @@ What runs where:
       -> mi_gather_fm_fwd(_ride) forward; backward in the epilogue of the tail's first input-gradient product
          (mi_tail_dgrad_gemm_fm) when the whole forward is one autograd node (_fused_step), else
          mi_gather_fm_bwd_{rows,dense}  (vanilla table), or
+         mi_gather_fm_masked_{fwd,bwd_rows,bwd_dense}      (OptEmbed: a search candidate in eval, the retraining table), or
          IEmbedding.forward + mi_fm_fwd / mi_fm_bwd        (compressed tables)
   the MLP tail (a real GEMM): the library's own fp32-MFMA products with BatchNorm1d / ReLU / Dropout in
       their operand loads and epilogues (tail.py, csrc/tail.hip) in training, eval() and no-BatchNorm stacks alike; the
@@ -23,6 +24,7 @@ from torch import nn
 
 from . import _kernels
 from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
+from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
 from .mlp import field_offsets, hidden_stack, run_tail
 
 
@@ -112,6 +114,13 @@ class DeepFM(nn.Module):
                 x, self.offsets, emb_mod.get_weight(), self.fc.weight, self._bias,
                 sparse_W=emb_mod.sparse_grad, sparse_w1=bool(self.fc.sparse),
             )
+        # OptEmbed: a search candidate in eval, the retraining table in training and eval alike — the same launch with a
+        # kept width per looked-up row, no masked copy of the table and no [B, F] index tensors
+        mask = emb_mod.fm_mask() if isinstance(emb_mod, (DeepFMOptEmbed, RetrainOptEmbed)) else None
+        if mask is not None:
+            W, keep, fwidth, sparse_W = mask
+            return _kernels.gather_fm(x, self.offsets, W, self.fc.weight, self._bias, sparse_W=sparse_W,
+                                      sparse_w1=bool(self.fc.sparse), keep=keep, fwidth=fwidth)
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

@@ -3,8 +3,9 @@
 Same registry keys, same `get_embedding(embedding_config, field_dims, hidden_size,
 mode, field_name)` contract (config deep-copied, "name" popped and restored,
 `field_name` forwarded to pep*/cerp* classes).  Keys whose class is outside the
-hot-path scope (DeepFM's OptEmbed retraining class, the FBTT CUDA extension) raise
-NotImplementedError with the reason instead of silently substituting something.
+hot-path scope (the FBTT CUDA extension) or that cannot be built from a config alone (DeepFM's OptEmbed
+retraining table, which needs the searched masks: deepfm_opt_embed.build_retrain_deepfm) raise NotImplementedError with
+the reason instead of silently substituting something.
 """
 import copy
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -13,6 +14,8 @@ from .base import IEmbedding, VanillaEmbedding
 from .cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
 from .cf_opt_embed import OptEmbed, RetrainOptEmbed
 from .deepfm_opt_embed import OptEmbed as DeepFMOptEmbed
+from .deepfm_opt_embed import RetrainOptEmbed as DeepFMRetrainOptEmbed
+from .deepfm_opt_embed import build_retrain_deepfm, evol_search_deepfm
 from .dh_embedding import DHEmbedding
 from .pep_embedding import PepEmbeeding, RetrainPepEmbedding
 from .pruned_embedding import PrunedEmbedding
@@ -44,8 +47,10 @@ _WANTS_FIELD_NAME = {key for key, _, _, named in _REGISTRY if named}
 
 # registry keys of the reference that this build deliberately does not cover
 OUT_OF_SCOPE = {
-    "deepfm_optembed_retrain": "DeepFM's OptEmbed retraining class and its search (evol_search_deepfm); the DeepFM supernet "
-                               "is 'deepfm_optembed', the CF retraining table 'optembed_retrain'",
+    "deepfm_optembed_retrain": "a retraining table is built from the masks a search returned, not from a config: use "
+                               "deepfm_opt_embed.build_retrain_deepfm(field_dims, model_config, mask_e, mask_d), which "
+                               "attaches a deepfm_opt_embed.RetrainOptEmbed to a DeepFM (the supernet is 'deepfm_optembed', "
+                               "the CF retraining table 'optembed_retrain')",
     "tt_emb": "FBTT-Embedding CUDA extension, not in the reference tree (SURVEY.md §2.3 K3-K12); use 'tt_emb_torch'",
 }
 
@@ -81,4 +86,4 @@ def detect_special(config: Dict[str, Any]) -> Tuple[Optional[str], bool]:
 
 
 __all__ = ["IEmbedding", "VanillaEmbedding", "OptEmbed", "RetrainOptEmbed", "QRHashingEmbedding", "CerpEmbedding", "RetrainCerpEmbedding",
-           "DHEmbedding", "PrunedEmbedding", "TTRecTorch", "PepEmbeeding", "RetrainPepEmbedding", "NAME_TO_CLS", "get_embedding", "detect_special"]
+           "DHEmbedding", "PrunedEmbedding", "DeepFMOptEmbed", "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "TTRecTorch", "PepEmbeeding", "RetrainPepEmbedding", "NAME_TO_CLS", "get_embedding", "detect_special"]

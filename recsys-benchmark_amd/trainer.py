@@ -320,6 +320,44 @@ def train_epoch_cerp(dataloader, model, optimizer, device="cuda", log_step=10, p
     return dict({k: v / max(n, 1) for k, v in sums().items()}, sparsity=sparsity, num_params=num_params)
 
 
+def train_epoch_optembed_deepfm(dataloader, model, optimizers, device="cuda", log_step=10, profiler=None, clip_grad=0,
+                                alpha=0) -> Dict[str, float]:
+    """scripts/deepfm/train_deepfm_optembed.py:21-112 of the reference: a DeepFM epoch on the OptEmbed supernet, eager,
+    with a list of optimizers (the thresholds usually get their own); loss = BCEWithLogits + alpha *
+    model.embedding.get_l_s().  Returns the averaged "loss" and "loss_s" (unweighted) and the table's "sparsity" /
+    "num_params" after the epoch."""
+    if not isinstance(optimizers, (list, tuple)):
+        optimizers = [optimizers]
+    model.train()
+    model.to(device)
+    criterion = losses.BCEWithLogitsLoss()
+    sums = torch.zeros(2, dtype=torch.float32, device=device)          # loss, loss_s
+    one = losses.unit_scalar(device)
+
+    def log(idx):
+        sparsity, num_params = model.embedding.get_sparsity(get_n_params=True)
+        avg = _mean_since(sums, None, idx + 1)
+        logger.info("Idx: %d - loss: %.4g - loss_s: %.4g - sparsity: %.4g - num_params: %d", idx, avg[0], avg[1], sparsity,
+                    num_params)
+
+    def batch(inputs, labels):
+        loss_s = model.embedding.get_l_s()
+        loss = criterion(model(inputs), labels.float()) + alpha * loss_s
+        for opt in optimizers:
+            opt.zero_grad()
+        loss.backward(one)
+        if clip_grad:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad)
+        for opt in optimizers:
+            opt.step()
+        sums.add_(torch.stack([loss.detach(), torch.as_tensor(loss_s, dtype=torch.float32, device=device).detach()]))
+
+    avg = _mean_since(sums, None, _run_epoch(dataloader, device, log_step, profiler, batch, log))
+    _lib.check_index_errors()
+    sparsity, num_params = model.embedding.get_sparsity(get_n_params=True)
+    return {"loss": avg[0], "loss_s": avg[1], "sparsity": sparsity, "num_params": num_params}
+
+
 def binary_auc(y_true: torch.Tensor, y_score: torch.Tensor) -> float:
     """Area under the ROC curve as sklearn.metrics.roc_auc_score computes it for binary labels (ties share their average
     rank: the Mann-Whitney statistic), on the device in float64."""
@@ -357,12 +395,14 @@ class GraphedForward:
 
 
 @torch.no_grad()
-def validate_epoch(val_loader, model, device="cuda") -> Dict[str, float]:
+def validate_epoch(val_loader, model, device="cuda", forward: Optional[GraphedForward] = None) -> Dict[str, float]:
     """src/trainer/deepfm.py:96-139: {"auc", "log_loss"}; labels and predictions stay on the device, the forward of the
-    full-size batches is replayed as a hipGraph."""
+    full-size batches is replayed as a hipGraph.  `forward` (optional): a GraphedForward of this model to keep using —
+    the mask search scores every candidate through one (evol_search_deepfm)."""
     model.eval()
     model = model.to(device)
-    forward = GraphedForward(model)
+    if forward is None:
+        forward = GraphedForward(model)
     criterion = torch.nn.BCEWithLogitsLoss(reduction="sum")
     log_loss = torch.zeros((), dtype=torch.float64, device=device)
     y_true, y_pred = [], []

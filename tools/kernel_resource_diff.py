@@ -1,0 +1,68 @@
+"""Compare the register / scratch / LDS use of every kernel of one HIP source between two builds, from the compiler's
+`-Rpass-analysis=kernel-resource-usage` remarks — no GPU needed.  Used to show that a compile-time flag added to a
+shared walker did not leak into the instantiations that do not set it (the masked gather_fm).
+
+    git show <parent commit>:recsys-benchmark_amd/csrc/gather_fm.hip > parent_gather_fm.hip
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Irecsys-benchmark_amd/csrc \
+          -Rpass-analysis=kernel-resource-usage -c parent_gather_fm.hip -o parent.o 2> parent.txt
+    hipcc (same flags) -c recsys-benchmark_amd/csrc/gather_fm.hip -o this.o 2> this.txt
+    python tools/kernel_resource_diff.py parent.txt this.txt
+
+Kernels are matched by their DEMANGLED name (an empty template parameter pack changes the mangled one only).  Prints
+every kernel of the first build whose VGPR, SGPR, AGPR, scratch, LDS or occupancy figure moved or that is gone, then a
+count per kernel family; exit status 1 if anything moved.
+"""
+import re
+import subprocess
+import sys
+
+KEYS = ["VGPRs", "TotalSGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
+
+
+def parse(path):
+    out, cur = {}, None
+    for line in open(path):
+        m = re.search(r"remark: (.*?)\s*\[-Rpass-analysis=kernel-resource-usage\]", line)
+        if not m:
+            continue
+        text = m.group(1).strip()
+        name = re.match(r"Function Name: (\S+)", text)
+        if name:
+            cur = out.setdefault(name.group(1), {})
+            continue
+        field = re.match(r"(.+?):\s*(\S+)$", text)
+        if field and cur is not None:
+            cur[field.group(1).strip()] = field.group(2)
+    names = sorted(out)
+    plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    return {d.replace("(anonymous namespace)::", ""): out[n] for n, d in zip(names, plain)}
+
+
+def family(name):
+    return re.sub(r"[<(].*", "", re.sub(r"^void ", "", name))
+
+
+def main():
+    a, b = parse(sys.argv[1]), parse(sys.argv[2])
+    fam, moved = {}, 0
+    for name in sorted(a):
+        f = fam.setdefault(family(name), [0, 0])
+        f[0] += 1
+        if name not in b:
+            print("GONE ", name)
+        else:
+            d = [(k, a[name].get(k), b[name].get(k)) for k in KEYS if a[name].get(k) != b[name].get(k)]
+            if not d:
+                continue
+            print("MOVED", name, d)
+        f[1] += 1
+        moved += 1
+    print(f"{len(a)} kernels in the first build: {len(a) - moved} unchanged, {moved} moved or gone; "
+          f"{len(set(b) - set(a))} kernels only in the second build")
+    for f, (n, m) in sorted(fam.items()):
+        print(f"  {f}: {n} instantiations, {m} moved")
+    return 1 if moved else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
