@@ -168,6 +168,49 @@ MI_API int mi_gather_fm_masked_bwd_dense(const int64_t *rows, const uint8_t *kee
                                          float *gW, float *gw1, float *gbias,
                                          int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
 
+/* ---- the same launch with PEP's element transforms (DeepFM on PepEmbeeding / RetrainPepEmbedding) ----
+ * src/models/embeddings/pep_embedding.py:82-92 (soft-threshold the whole table, then the lookup) and :211-221
+ * (emb.weight * mask every step) without the transformed copy of the table:
+ *   soft:     emb[b,f,d] = sign(w) relu(|w| - sigmoid(s)),  w = W[row,d],  s = S[row*srs + d*scs]
+ *             (srs, scs) as in mi_xform_gather_*: (0,0) global [1], (0,1) dimension [D], (1,0) feature [N,1],
+ *             (D,1) feature_dim [N,D]; anything else is MI_ERR_INVALID_ARG.  The same device functions as
+ *             mi_xform_gather_fwd: emb has that lookup's bits.
+ *   elemmask: emb[b,f,d] = M[row,d] ? W[row,d] : +0,  M uint8[N,D] (a bool mask read as bytes, not packed into bits)
+ * y_fm over the transformed emb; the first-order term and the bias are NOT transformed.  The other arguments as
+ * mi_gather_fm_fwd_ld (out-of-range rows flagged in *err and read as zeros).
+ * Backward, row form only (dense gradients are scattered from the row values, mi_scatter_axpy_rows, or coalesced in a fixed
+ * order, mi_coalesce_rows_sorted): one launch over the saved emb, W is not read again.  rows int64[B,F] = the forward's
+ * rows_out; dE[i,d] = g_emb[i,d] + g_y[b] (S[b,d] - emb[i,d]);  g1vals[i] = g_y[b];  gbias nullable.
+ *   soft:     gvals[i,d] = dE [emb != 0];  svals = -dE sign(emb) [emb != 0] sig(s) (1 - sig(s)), laid out by the threshold:
+ *             feature_dim fp32[B*F, D]; feature fp32[B*F] (summed over d); dimension fp32[D] / global fp32[1]: the final
+ *             gradient, summed over the grid in a fixed order by the last workgroup to arrive — no float atomics.  These two
+ *             take `workspace` (mi_gather_fm_soft_bwd_workspace_elems floats, 0 for the row layouts), whose LAST word is a
+ *             ticket: armed != 0 says it is zero already (every launch leaves it zero), armed = 0 zeroes it first.
+ *   elemmask: gvals[i,d] = M[row,d] ? dE : 0 (the mask from M: a kept element may hold exactly 0).
+ * D <= 256 in the backward, else MI_ERR_UNSUPPORTED.
+ */
+MI_API int mi_gather_fm_soft_fwd(const int64_t *idx, const int64_t *offsets,
+                                 const float *W, int64_t ldw, const float *w1, int64_t ldw1, const float *bias,
+                                 const float *S, int64_t srs, int64_t scs,
+                                 float *emb_out, float *yfm_out, int64_t *rows_out,
+                                 int64_t B, int32_t F, int32_t D, int64_t N,
+                                 int32_t *err, void *stream);
+MI_API int mi_gather_fm_elemmask_fwd(const int64_t *idx, const int64_t *offsets,
+                                     const float *W, int64_t ldw, const float *w1, int64_t ldw1, const float *bias,
+                                     const uint8_t *M,
+                                     float *emb_out, float *yfm_out, int64_t *rows_out,
+                                     int64_t B, int32_t F, int32_t D, int64_t N,
+                                     int32_t *err, void *stream);
+MI_API int64_t mi_gather_fm_soft_bwd_workspace_elems(int64_t B, int32_t D, int64_t srs);
+MI_API int mi_gather_fm_soft_bwd_rows(const int64_t *rows, const float *S, int64_t srs, int64_t scs,
+                                      const float *emb, const float *g_y, const float *g_emb,
+                                      float *gvals, float *svals, float *g1vals, float *gbias, float *workspace,
+                                      int32_t armed, int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
+MI_API int mi_gather_fm_elemmask_bwd_rows(const int64_t *rows, const uint8_t *M,
+                                          const float *emb, const float *g_y, const float *g_emb,
+                                          float *gvals, float *g1vals, float *gbias,
+                                          int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
+
 /* ---- a2: plain row gather (IEmbedding.forward on a vanilla table) ----------
  * src/models/embeddings/base.py:74-75 (nn.Embedding on int64[n] ids, already
  * offset).  out fp32[n,D].
@@ -293,6 +336,12 @@ MI_API int mi_xform_gather_bwd(const int64_t *idx, const float *g_out, const flo
                                const float *S, const uint8_t *M, int64_t srs, int64_t scs,
                                float *gW, float *gS, int64_t s_numel, int64_t n, int32_t D,
                                int64_t N, int32_t xform, void *stream);
+
+/* PepEmbeeding.get_num_params() (pep_embedding.py:127-130): *count (a device int64, overwritten) = the number of
+ * elements of W fp32[N,D] with |w| - sigmoid(s) > 0, s = S[row*srs + d*scs] as above — where the soft-thresholded table
+ * is non-zero.  One read of W and S, integer adds only, no [N,D] temporary. */
+MI_API int mi_soft_count_kept(const float *W, const float *S, int64_t srs, int64_t scs, int64_t N, int32_t D,
+                              int64_t *count, void *stream);
 
 /* Quantised tables, inference only (src/models/embeddings/ptq_emb.py:24-25,85-91):
  * qtype 1: W is fp16[N,D], out = fp32(W[idx]); 2 / 3: W is int8 / int16 codes, out = (code - bias[0]) * scale[0]

@@ -103,6 +103,22 @@ def _mask_operands(keep, fwidth, N: int, F: int):
     return keep, fwidth
 
 
+XFORM_MAX_D = 256       # the row-form backward of the PEP forms (mi_gather_fm_soft_bwd_rows / _elemmask_bwd_rows)
+
+
+def _soft_strides(s: torch.Tensor, N: int, D: int):
+    """(row stride, column stride) of a PEP threshold that broadcasts over a [N, D] table: [1], [D], [N,1] or [N,D]."""
+    if s.numel() == 1:
+        return 0, 0
+    if s.dim() == 1 and s.shape[0] == D:
+        return 0, 1
+    if tuple(s.shape) == (N, 1):
+        return 1, 0
+    if tuple(s.shape) == (N, D):
+        return D, 1
+    raise ValueError(f"threshold of shape {tuple(s.shape)} does not broadcast over a [{N},{D}] table")
+
+
 class GatherFM(torch.autograd.Function):
     """emb, y_fm = gather+FM+first-order (src/models/deepfm.py:88-98) in one kernel.
 
@@ -114,13 +130,25 @@ class GatherFM(torch.autograd.Function):
     emb[b, f, d] = W[row, d] for d < min(keep[row], fwidth[f]) and +0 past it, y_fm over the masked emb, the first-order
     term unmasked; the table's gradient is exactly zero at the masked positions.  With both None every call is the
     unmasked one.
+
+    soft (fp32 [1], [D], [N,1] or [N,D], an autograd input) / elem_mask (bool or uint8 [N, D]): the PEP forms
+    (mi_gather_fm_soft_* / mi_gather_fm_elemmask_*) — emb = sign(w) relu(|w| - sigmoid(s)), or emb = mask ? w : +0;
+    y_fm over that emb, the first-order term untouched.  The backward is one row-form launch over the saved emb; dense
+    gradients (W's, and a row-shaped threshold's) are scattered from its values — in a fixed order in deterministic
+    mode —, sparse_W asks for them in COO form.  A [D] or [1] threshold's gradient leaves the launch complete.
     """
 
     @staticmethod
-    def forward(ctx, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool, keep=None, fwidth=None):
-        dev = _lib.require_gpu(idx, offsets, W, w1, bias, keep, fwidth)
+    def forward(ctx, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool, keep=None, fwidth=None, soft=None,
+                elem_mask=None):
+        dev = _lib.require_gpu(idx, offsets, W, w1, bias, keep, fwidth, soft, elem_mask)
         lib = _lib.load()
         masked = keep is not None or fwidth is not None
+        if (soft is not None) + (elem_mask is not None) + masked > 1:
+            raise ValueError("gather_fm: keep / fwidth, soft and elem_mask exclude each other")
+        xform = soft is not None or elem_mask is not None
+        if xform and W.shape[-1] > XFORM_MAX_D:
+            raise NotImplementedError(f"the soft / elem_mask gather_fm backward covers D <= {XFORM_MAX_D}, got {W.shape[-1]}")
         if masked and W.shape[-1] > MASKED_MAX_D:
             raise NotImplementedError(f"the masked gather_fm keeps one byte per width: D <= {MASKED_MAX_D}, got "
                                       f"{W.shape[-1]}")
@@ -141,7 +169,33 @@ class GatherFM(torch.autograd.Function):
         emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)
-        if masked:
+        ctx.xform = None
+        if soft is not None:
+            srs, scs = _soft_strides(soft, N, D)
+            Sc = _f32c(soft)
+            _lib.check(
+                lib.mi_gather_fm_soft_fwd(
+                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
+                    Sc.data_ptr(), srs, scs, emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
+                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+                ),
+                "mi_gather_fm_soft_fwd",
+            )
+            ctx.xform = ("soft", srs, scs, tuple(soft.shape))
+        elif elem_mask is not None:
+            if elem_mask.dtype not in (torch.bool, torch.uint8) or tuple(elem_mask.shape) != (N, D):
+                raise ValueError(f"elem_mask must be bool or uint8 [{N}, {D}], got {elem_mask.dtype} {tuple(elem_mask.shape)}")
+            Mc = elem_mask.contiguous().view(torch.uint8)      # (a bool is one byte, 0 or 1: read in place)
+            _lib.check(
+                lib.mi_gather_fm_elemmask_fwd(
+                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
+                    Mc.data_ptr(), emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
+                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+                ),
+                "mi_gather_fm_elemmask_fwd",
+            )
+            ctx.xform = ("mask", Mc)
+        elif masked:
             keep, fwidth = _mask_operands(keep, fwidth, N, F)
             _lib.check(
                 lib.mi_gather_fm_masked_fwd(
@@ -162,7 +216,8 @@ class GatherFM(torch.autograd.Function):
             )
         if sparse_W or sparse_w1 or DETERMINISTIC:
             note_field_layout(rows, offsets, N)
-        ctx.save_for_backward(emb, rows)
+        # (the threshold is an autograd input: saved, so that an in-place update before the backward raises)
+        ctx.save_for_backward(emb, rows, *((Sc,) if soft is not None else ()))
         ctx.mask = (keep, fwidth) if masked else None      # (constants of the step, not autograd inputs)
         ctx.shapes = (B, F, D, N, tuple(W.shape), tuple(w1.shape))
         ctx.sparse = (sparse_W, sparse_w1)
@@ -173,7 +228,7 @@ class GatherFM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_emb, g_y, _g_rows):
-        emb, rows = ctx.saved_tensors
+        emb, rows = ctx.saved_tensors[:2]
         B, F, D, N, Wshape, w1shape = ctx.shapes
         sparse_W, sparse_w1 = ctx.sparse
         dev = emb.device
@@ -185,6 +240,8 @@ class GatherFM(torch.autograd.Function):
         need_W, need_w1 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         gW = gw1 = None
         stream = _lib.stream_ptr(dev)
+        if ctx.xform is not None:
+            return GatherFM._xform_backward(ctx, emb, rows, g_emb, g_y, need_W, need_w1, stream)
         rows_form = (sparse_W and need_W) or (sparse_w1 and need_w1)
         dense_form = (need_W and not sparse_W) or (need_w1 and not sparse_w1)
         if DETERMINISTIC and dense_form:
@@ -237,7 +294,54 @@ class GatherFM(torch.autograd.Function):
                 gw1 = gw1d.view(w1shape)
         if gb is not None and not gb_done:          # neither table needs a gradient: nothing was launched
             gb = g_y.sum().view(1)
-        return None, None, gW, gw1, gb, None, None, None, None
+        return None, None, gW, gw1, gb, None, None, None, None, None, None
+
+    @staticmethod
+    def _xform_backward(ctx, emb, rows, g_emb, g_y, need_W, need_w1, stream):
+        """The PEP forms: one row-form launch, then the tables' gradients out of its values (_table_grads)."""
+        B, F, D, N, Wshape, w1shape = ctx.shapes
+        sparse_W, sparse_w1 = ctx.sparse
+        dev = emb.device
+        lib = _lib.load()
+        need_S = ctx.xform[0] == "soft" and ctx.needs_input_grad[9]
+        need_b = ctx.has_bias and ctx.needs_input_grad[4]
+        if not (need_W or need_w1 or need_S):
+            return (None, None, None, None, g_y.sum().view(1) if need_b else None) + (None,) * 6
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+        gvals = torch.empty((B * F, D), dtype=torch.float32, device=dev)
+        g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev)
+        gS = None
+        if ctx.xform[0] == "soft":
+            _, srs, scs, Sshape = ctx.xform
+            Sc = ctx.saved_tensors[2]
+            svals = torch.empty((B * F, D) if srs == D and scs == 1 else (B * F,) if srs else (D,) if scs else (1,),
+                                dtype=torch.float32, device=dev)
+            ws, armed = (_losses._ticket_workspace("gather_fm_soft", dev, lib.mi_gather_fm_soft_bwd_workspace_elems(B, D, srs))
+                         if srs == 0 and B > 0 else (None, True))
+            _lib.check(
+                lib.mi_gather_fm_soft_bwd_rows(rows.data_ptr(), Sc.data_ptr(), srs, scs, emb.data_ptr(), g_y.data_ptr(),
+                                               _lib.ptr(g_emb), gvals.data_ptr(), svals.data_ptr(), g1vals.data_ptr(),
+                                               _lib.ptr(gb), _lib.ptr(ws), int(armed), B, F, D, N, stream),
+                "mi_gather_fm_soft_bwd_rows",
+            )
+            if need_S:
+                if srs == 0:                  # [D] / [1]: the launch summed it
+                    gS = svals.view(Sshape)
+                else:                         # [N, D] / [N, 1]: one value row per lookup, like the table's
+                    width = D if scs else 1
+                    gS = (_coo(rows, svals.view(B * F, *Sshape[1:]), Sshape) if sparse_W
+                          else _scatter_rows(rows, svals, N, width, stream).view(Sshape))
+        else:
+            _lib.check(
+                lib.mi_gather_fm_elemmask_bwd_rows(rows.data_ptr(), ctx.xform[1].data_ptr(), emb.data_ptr(), g_y.data_ptr(),
+                                                   _lib.ptr(g_emb), gvals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb),
+                                                   B, F, D, N, stream),
+                "mi_gather_fm_elemmask_bwd_rows",
+            )
+        if gb is not None and B == 0:
+            gb.zero_()
+        gW, gw1 = _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1, stream)
+        return None, None, gW, gw1, gb, None, None, None, None, gS, None
 
 
 # Deterministic mode (recsys_benchmark_amd.use_deterministic_algorithms): dense table gradients are built by SORTING the
@@ -295,9 +399,22 @@ def _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1
     return gW, gw1
 
 
-def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False, keep=None, fwidth=None):
-    emb, yfm, _rows = GatherFM.apply(idx, offsets, W, w1, bias, sparse_W, sparse_w1, keep, fwidth)
+def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False, keep=None, fwidth=None, soft=None, elem_mask=None):
+    emb, yfm, _rows = GatherFM.apply(idx, offsets, W, w1, bias, sparse_W, sparse_w1, keep, fwidth, soft, elem_mask)
     return emb, yfm
+
+
+def soft_count_kept(W: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """Device int64 [1]: the number of non-zeros of sign(W) relu(|W| - sigmoid(s)), counted in one pass over W and s
+    (mi_soft_count_kept) — no thresholded copy of the table."""
+    dev = _lib.require_gpu(W, s)
+    Wc, Sc = _f32c(W), _f32c(s)
+    N, D = Wc.shape
+    srs, scs = _soft_strides(s, N, D)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().mi_soft_count_kept(Wc.data_ptr(), Sc.data_ptr(), srs, scs, N, D, count.data_ptr(),
+                                              _lib.stream_ptr(dev)), "mi_soft_count_kept")
+    return count
 
 
 class GatherRows(torch.autograd.Function):
@@ -1863,17 +1980,7 @@ class XformGather(torch.autograd.Function):
 
 def soft_threshold_gather(idx, W, s):
     """F.embedding(idx, sign(W)*relu(|W| - sigmoid(s))) with s broadcastable to W ([1], [D], [N,1], [N,D])."""
-    N, D = W.shape
-    if s.numel() == 1:
-        srs, scs = 0, 0
-    elif s.dim() == 1 and s.shape[0] == D:
-        srs, scs = 0, 1
-    elif tuple(s.shape) == (N, 1):
-        srs, scs = 1, 0
-    elif tuple(s.shape) == (N, D):
-        srs, scs = D, 1
-    else:
-        raise ValueError(f"threshold of shape {tuple(s.shape)} does not broadcast over a [{N},{D}] table")
+    srs, scs = _soft_strides(s, *W.shape)
     return XformGather.apply(idx, W, s, None, srs, scs, XF_SOFT)
 
 

@@ -35,6 +35,12 @@ SIGNATURES = {
     "mi_gather_fm_masked_fwd": [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
     "mi_gather_fm_masked_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
     "mi_gather_fm_masked_bwd_dense": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_fm_soft_fwd": [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_gather_fm_elemmask_fwd": [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_gather_fm_soft_bwd_workspace_elems": [_i64, _i32, _i64],
+    "mi_gather_fm_soft_bwd_rows": [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_fm_elemmask_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
+    "mi_soft_count_kept": [_p, _p, _i64, _i64, _i64, _i32, _p, _p],
     "mi_gather_rows_fwd": [_p, _p, _p, _i64, _i32, _i64, _p, _p],
     "mi_scatter_add_rows": [_p, _p, _p, _i64, _i32, _i64, _p],
     "mi_fm_fwd": [_p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
@@ -216,7 +222,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_dual_gather_bwd_rows_workspace_elems": ctypes.c_int64,
              "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64,
              "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64,
-             "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64}
+             "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64,
+             "mi_gather_fm_soft_bwd_workspace_elems": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

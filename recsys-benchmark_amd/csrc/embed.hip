@@ -655,6 +655,39 @@ __global__ __launch_bounds__(kBlock) void k_xform_gather_bwd(const int64_t *__re
   }
 }
 
+// PepEmbeeding.get_num_params() (pep_embedding.py:127-130) without soft(W): the number of elements with |w| - sig(s) > 0
+// — exactly where sign(w) relu(|w| - sig(s)) is non-zero, since |w| > sig(s) >= 0 leaves no w = 0.  One read of W and S,
+// a count per thread, one integer atomic per wave: no float is added, nothing [N, D]-sized is written.
+// VEC: four consecutive elements per thread (D % 4 == 0 keeps them in one row; W, and S where it has columns, 16-byte aligned).
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void k_soft_count_kept(XformTable t, int64_t total, int D,
+                                                            unsigned long long *__restrict__ count) {
+  constexpr int PER = VEC ? 4 : 1;
+  const int64_t steps = total / PER;      // (VEC: total = N * D is a multiple of 4)
+  unsigned long long mine = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < steps; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = i * PER, row = e / D;
+    const int d = (int)(e - row * D);
+    if constexpr (VEC) {
+      const float4 w = ld4(t.W + e);
+      float4 s;
+      if (t.scs) {
+        s = ld4(t.S + row * t.srs + d);
+      } else {
+        const float s0 = t.S[row * t.srs];
+        s = make_float4(s0, s0, s0, s0);
+      }
+      mine += (fabsf(w.x) - sigmoidf_(s.x) > 0.f) + (fabsf(w.y) - sigmoidf_(s.y) > 0.f) + (fabsf(w.z) - sigmoidf_(s.z) > 0.f) +
+              (fabsf(w.w) - sigmoidf_(s.w) > 0.f);
+    } else {
+      mine += fabsf(t.W[e]) - sigmoidf_(t.S[row * t.srs + d * t.scs]) > 0.f;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
+}
+
 // ------------------------------------------------------------- quantised tables (PTQ, inference)
 // src/models/embeddings/ptq_emb.py:24-25 (fp16 -> fp32) and :85-91 ((code - bias) * scale, int8/int16).
 // torch computes (res - bias) in the integer type promoted with the int bias tensor, then * scale
@@ -839,6 +872,23 @@ int mi_xform_gather_fwd(const int64_t *idx, const float *W, const float *S, cons
   XformTable t{W, S, M, srs, scs, N};
   MI_LAUNCH("xform_gather_fwd", k_xform_gather_fwd, grid_for_elems(n * D), kBlock, stream, idx, t, out, n, D, xform,
             err);
+  return launch_status();
+}
+
+int mi_soft_count_kept(const float *W, const float *S, int64_t srs, int64_t scs, int64_t N, int32_t D, int64_t *count,
+                       void *stream) {
+  if (N < 0 || D <= 0 || !count) return MI_ERR_INVALID_ARG;
+  if (!((srs == 0 && (scs == 0 || scs == 1)) || (srs == 1 && scs == 0) || (srs == D && scs == 1))) return MI_ERR_INVALID_ARG;
+  if (hipMemsetAsync(count, 0, sizeof(int64_t), (hipStream_t)stream) != hipSuccess) return MI_ERR_LAUNCH;
+  const int64_t total = N * D;
+  if (total == 0) return MI_OK;
+  if (!W || !S) return MI_ERR_INVALID_ARG;
+  const XformTable t = {W, S, nullptr, srs, scs, N};
+  unsigned long long *c = reinterpret_cast<unsigned long long *>(count);
+  if ((D & 3) == 0 && aligned16(W) && (scs == 0 || aligned16(S)))
+    MI_LAUNCH("soft_count_kept", k_soft_count_kept<true>, grid_for_elems(total / 4), kBlock, stream, t, total, D, c);
+  else
+    MI_LAUNCH("soft_count_kept", k_soft_count_kept<false>, grid_for_elems(total), kBlock, stream, t, total, D, c);
   return launch_status();
 }
 

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "dual_xform.hpp"
 #include "prefetch_rows.hpp"
 #include "tail_masks.hpp"
 
@@ -89,6 +90,36 @@ __device__ __forceinline__ int kept_width(KeptWidths m, int64_t i, int f, int D)
   return kept_width(m.rows, m.keep, m.fwidth, i, f, m.N, D);
 }
 
+// The element transforms of the PEP tables (mi_gather_fm_soft_* / mi_gather_fm_elemmask_*), XF of dual_xform.hpp:
+//   XF_SOFT: emb[b, f, d] = soft_(W[row, d], S[row * srs + d * scs])  (PepEmbeeding; (srs, scs) as in mi_xform_gather_*:
+//            (0,0) global, (0,1) dimension, (1,0) feature, (D,1) feature_dim)
+//   XF_MASK: emb[b, f, d] = M[row, d] ? W[row, d] : +0                 (RetrainPepEmbedding.mask, one byte per element)
+// The first-order term is not transformed.  soft_ / sigmoidf_ are the functions k_xform_gather_fwd (embed.hip) applies, so
+// emb has that lookup's bits.
+struct Xform {
+  const float *S;
+  int64_t srs, scs;
+  const uint8_t *M;
+};
+// the lane's four threshold logits of `row` (columns q*4 .. q*4+3): one float4 where the threshold has columns, one scalar
+// where it has not
+__device__ __forceinline__ float4 thr4(const Xform &x, int64_t row, int q) {
+  if (x.scs) return ld4(x.S + row * x.srs + q * 4);
+  const float s = x.S[row * x.srs];
+  return make_float4(s, s, s, s);
+}
+__device__ __forceinline__ float4 soft4(float4 w, float4 s) {
+  return make_float4(soft_(w.x, s.x), soft_(w.y, s.y), soft_(w.z, s.z), soft_(w.w, s.w));
+}
+// the lane's four mask bytes of `row` as one word (D % 4 == 0 and M 4-byte aligned: the launcher checks)
+__device__ __forceinline__ uint32_t mask4(const uint8_t *__restrict__ M, int64_t row, int D, int q) {
+  return *reinterpret_cast<const uint32_t *>(M + row * D + q * 4);
+}
+__device__ __forceinline__ float4 keep_bytes(float4 v, uint32_t m) {
+  return make_float4((m & 0xffu) ? v.x : 0.f, (m & 0xff00u) ? v.y : 0.f, (m & 0xff0000u) ? v.z : 0.f,
+                     (m & 0xff000000u) ? v.w : 0.f);
+}
+
 // ---------------------------------------------------------------- forward ----
 // SHFL (F <= 64): the sample's F ids arrive by ONE coalesced load (lane l < F takes idx[b, l] + offsets[l]) and reach
 // the row slots by shuffles — one dependent vector-memory instruction in front of the row gathers instead of NIT id
@@ -105,13 +136,15 @@ __device__ __forceinline__ int kept_width(KeptWidths m, int64_t i, int f, int D)
 // only the row id: one round trip, not two; the LPR lanes of a row slot read the same byte, one request), fwidth[f]
 // arrives like offsets[f] — in SHFL form once per wave, next to offsets[lane], and by shuffle from there.  Every row is
 // gathered whole whatever its width: the gather does not wait for the byte.  Without MASK none of this is compiled.
-template <int LPR, int NIT, bool SHFL, bool MASK = false>
+// XF (XF_SOFT / XF_MASK, never together with MASK): the row's threshold logits or mask bytes are loaded in the same step
+// as the row as well — they, too, need only the row id — and applied before the row is stored and summed.
+template <int LPR, int NIT, bool SHFL, bool MASK = false, int XF = XF_NONE>
 __device__ __forceinline__ void gather_fm_fwd_blocks(
     const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
     const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
     float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
     int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out, int blk, int nblk,
-    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr, Xform xf = {}) {
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
   const int lane = threadIdx.x & 63;
@@ -135,6 +168,8 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
       float4 v[NIT];
       float l[NIT];
       int kw[NIT];      // (MASK only) the field's width, then the lookup's kept width
+      float4 th[NIT];   // (XF_SOFT only) the row's threshold logits
+      uint32_t mb[NIT]; // (XF_MASK only) the row's mask bytes
       if constexpr (SHFL) {
         const int64_t mine = lane < F ? idx[base + lane] + myoff : 0;
         if (rows_out && lane < F) rows_out[base + lane] = mine;
@@ -161,11 +196,15 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
         v[k] = ok[k] ? ld4(W + row[k] * ldw + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         l[k] = (ok[k] && q == 0) ? w1[row[k] * ldw1] : 0.f;
         if constexpr (MASK) kw[k] = imin(kw[k], (ok[k] && keep) ? (int)keep[row[k]] : D);
+        if constexpr (XF == XF_SOFT) th[k] = ok[k] ? thr4(xf, row[k], q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (XF == XF_MASK) mb[k] = ok[k] ? mask4(xf.M, row[k], D, q) : 0u;
       }
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
         const int f = r + k * RS;
         if constexpr (MASK) v[k] = keep_prefix(v[k], q, kw[k]);
+        if constexpr (XF == XF_SOFT) v[k] = soft4(v[k], th[k]);
+        if constexpr (XF == XF_MASK) v[k] = keep_bytes(v[k], mb[k]);
         if (act[k]) {
           st4_nt(emb + (base + f) * D + q * 4, v[k]);
           if (!SHFL && rows_out && q == 0) rows_out[base + f] = row[k];
@@ -184,6 +223,8 @@ __device__ __forceinline__ void gather_fm_fwd_blocks(
           const int kb = (ok && keep) ? (int)keep[row] : D;
           v = keep_prefix(v, q, imin(kb, fwidth ? fwidth[f] : D));
         }
+        if constexpr (XF == XF_SOFT) { if (ok) v = soft4(v, thr4(xf, row, q)); }
+        if constexpr (XF == XF_MASK) v = keep_bytes(v, ok ? mask4(xf.M, row, D, q) : 0u);
         if (ok && q == 0) lin += w1[row * ldw1];
         st4(emb + (base + f) * D + q * 4, v);
         if (rows_out && q == 0) rows_out[base + f] = row;
@@ -221,6 +262,15 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_masked(
   gather_fm_fwd_blocks<LPR, NIT, SHFL, true>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, N, ldw, ldw1, err, sum_out,
                                              (int)blockIdx.x, (int)gridDim.x, keep, fwidth);
 }
+template <int LPR, int NIT, bool SHFL, int XF>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_xform(
+    const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
+    const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
+    float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
+    int64_t B, int F, int64_t N, int64_t ldw, int64_t ldw1, int *err, float *__restrict__ sum_out, Xform xf) {
+  gather_fm_fwd_blocks<LPR, NIT, SHFL, false, XF>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, N, ldw, ldw1, err,
+                                                  sum_out, (int)blockIdx.x, (int)gridDim.x, nullptr, nullptr, xf);
+}
 // The same launch carrying the MLP tail's dropout keep bits and the zero fill of its accumulation buffer in workgroups
 // past the first `ngather` (tail_masks.hpp): in DeepFM's fused step this kernel is the first of the step, every reader of
 // the bits and every adder into the buffer comes later, and the mask work (~1 us spread over the chip, all ALU) runs
@@ -252,13 +302,13 @@ __global__ __launch_bounds__(kBlock) void k_mask_job(MaskRide ride) {
 }
 
 // Any D (scalar accesses): wave per sample, lanes stride over d.
-template <bool MASK>
+template <bool MASK, int XF = XF_NONE>
 __device__ __forceinline__ void gather_fm_fwd_anyD_blocks(
     const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
     const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
     float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
     int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out,
-    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr) {
+    const uint8_t *__restrict__ keep = nullptr, const int32_t *__restrict__ fwidth = nullptr, Xform xf = {}) {
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
@@ -284,6 +334,8 @@ __device__ __forceinline__ void gather_fm_fwd_anyD_blocks(
             const int kb = (ok && keep) ? (int)keep[row] : D;
             v = d < imin(kb, fwidth ? fwidth[f] : D) ? v : 0.f;
           }
+          if constexpr (XF == XF_SOFT) { if (ok) v = soft_(v, xf.S[row * xf.srs + d * xf.scs]); }
+          if constexpr (XF == XF_MASK) v = (ok && xf.M[row * D + d]) ? v : 0.f;
           emb[(base + f) * D + d] = v;
           S += v;
           ss += v * v;
@@ -311,6 +363,15 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD_masked(
     int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out,
     const uint8_t *__restrict__ keep, const int32_t *__restrict__ fwidth) {
   gather_fm_fwd_anyD_blocks<true>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, D, N, err, sum_out, keep, fwidth);
+}
+template <int XF>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_fwd_anyD_xform(
+    const int64_t *__restrict__ idx, const int64_t *__restrict__ offsets,
+    const float *__restrict__ W, const float *__restrict__ w1, const float *__restrict__ bias,
+    float *__restrict__ emb, float *__restrict__ yfm, int64_t *__restrict__ rows_out,
+    int64_t B, int F, int D, int64_t N, int *err, float *__restrict__ sum_out, Xform xf) {
+  gather_fm_fwd_anyD_blocks<false, XF>(idx, offsets, W, w1, bias, emb, yfm, rows_out, B, F, D, N, err, sum_out, nullptr,
+                                       nullptr, xf);
 }
 
 // bias gradient = sum_b g_y[b] (the bias is added to every sample's y_fm): ONE EXTRA workgroup of a backward launch —
@@ -475,6 +536,216 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_bwd_rows_anyD_masked(
   int blk, nblk;
   if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   gather_fm_bwd_rows_anyD_blocks<true>(emb, g_y, g_emb, gvals, g1vals, B, F, D, blk, nblk, rows, keep, fwidth, N);
+}
+
+// ------------------------------------- backward, row form, PEP transforms ----
+// mi_gather_fm_soft_bwd_rows / mi_gather_fm_elemmask_bwd_rows: the walk of k_gather_fm_bwd_rows over the SAVED emb (W is
+// not read again), with dE = g_emb + g_y (S_b - e) as there, and
+//   XF_SOFT: gvals = dE [e != 0],   svals = -dE sign(e) sigma(s) (1 - sigma(s))     (sign(0) = 0 carries the [e != 0])
+//            [e != 0] IS the reference's relu derivative here: e = sign(w) u with u = relu(|w| - sigma(s)), so e is
+//            non-zero exactly when |w| - sigma(s) > 0 (then |w| > sigma(s) >= 0 and sign(w) != 0).
+//   XF_MASK: gvals = dE where M[row, d] — the mask from M, not from e: a kept element may hold exactly 0.
+// svals by the threshold's strides: (D,1) one row [D] per lookup; (1,0) one float per lookup, summed over d across the
+// row's LPR lanes; (0,1) / (0,0) every thread adds its lookups' values up per column and column_join sums the grid.
+constexpr int kJoinMaxD = 256;
+struct SoftGrad {
+  float *svals;      // [B*F, D], [B*F], [D] or [1]
+  float *part;       // (0,*) forms: nblk x D partial column sums
+  unsigned *ticket;  // (0,*) forms: zero on entry, zero again on exit
+};
+
+// Column sums over the grid without float atomics, block_join's hand-off (common.hpp) with D values per workgroup:
+// red[w][c] holds wave w's sum of column c.  Wave 0 adds the waves in order and publishes the workgroup's D sums (sc1
+// stores), waits for them (s_waitcnt vmcnt(0) covers every store the wave issued), then its lane 0 takes the ticket.  The
+// workgroup whose ticket came back last adds all workgroups' sums: thread (g, c) those of workgroups g, g + G, ... in
+// that order, then thread c the G group sums in order — a fixed tree, so reruns give the same bits.  total: the [1]
+// threshold, the D column sums added in column order.
+__device__ __forceinline__ void column_join(float (*red)[kJoinMaxD], int D, float *__restrict__ part, unsigned *ticket,
+                                            float *__restrict__ out, bool total, int blk, int nblk) {
+  __shared__ bool last;
+  __shared__ float grp[kBlock];
+  const int lane = threadIdx.x & 63;
+  __syncthreads();
+  if (threadIdx.x < kWave) {
+    for (int c = lane; c < D; c += kWave) {
+      float t = 0.f;
+      for (int j = 0; j < kWavesPerBlock; ++j) t += red[j][c];
+      __hip_atomic_store(part + (int64_t)blk * D + c, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nblk - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  const int G = kBlock / D;      // (D <= kJoinMaxD = kBlock: at least one group)
+  const int c = threadIdx.x % D, g = threadIdx.x / D;
+  float t = 0.f;
+  if (g < G)
+    for (int j = g; j < nblk; j += G) t += __hip_atomic_load(part + (int64_t)j * D + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  grp[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x < D) {
+    t = 0.f;
+    for (int j = 0; j < G; ++j) t += grp[j * D + threadIdx.x];
+    if (!total) out[threadIdx.x] = t;
+    red[0][threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (total) {
+      t = 0.f;
+      for (int j = 0; j < D; ++j) t += red[0][j];
+      out[0] = t;
+    }
+    *ticket = 0;
+  }
+}
+
+__device__ __forceinline__ float dsigmoid_(float s) {
+  const float t = sigmoidf_(s);
+  return t * (1.f - t);
+}
+
+template <int LPR, int NIT, int XF>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_xform_bwd_rows(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb, const float *__restrict__ g_y,
+    const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
+    int64_t B, int F, int64_t N, float *__restrict__ gbias, Xform xf, SoftGrad sg) {
+  constexpr int RS = kWave / LPR;
+  constexpr int D = LPR * 4;
+  constexpr int NSTEP = NIT > 0 ? NIT : 1;
+  __shared__ __align__(16) float red[XF == XF_SOFT ? kWavesPerBlock : 1][kJoinMaxD];      // (written with st4)
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  const int lane = threadIdx.x & 63;
+  const int q = lane % LPR, r = lane / LPR;
+  const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int fend = NIT > 0 ? 1 : F;      // (NIT > 0: the chunk loops below run once)
+  const bool joined = XF == XF_SOFT && xf.srs == 0;
+  float4 cs = z;      // (XF_SOFT, srs == 0) this thread's column sums of svals
+
+  for (int64_t b = wave0; b < B; b += nwaves) {
+    const int64_t base = b * F;
+    const float gy = g_y[b];
+    float4 S = z;
+    float4 e[NSTEP], ge[NSTEP];
+    for (int f0 = 0; f0 < fend; f0 += NSTEP * RS) {
+      load_chunk<LPR, NSTEP>(emb, NIT > 0 ? g_emb : nullptr, base, f0 + r, F, q, e, ge);
+#pragma unroll
+      for (int k = 0; k < NSTEP; ++k) acc4(S, e[k]);
+    }
+    S = slot_sum<LPR>(S);
+    for (int f0 = 0; f0 < fend; f0 += NSTEP * RS) {
+      if constexpr (NIT == 0) load_chunk<LPR, NSTEP>(emb, g_emb, base, f0 + r, F, q, e, ge);
+#pragma unroll
+      for (int k = 0; k < NSTEP; ++k) {
+        const int f = f0 + r + k * RS;
+        const bool act = f < F;
+        const int64_t i = base + f;
+        const int64_t row = act ? rows[i] : -1;
+        const bool ok = (uint64_t)row < (uint64_t)N;      // (a row the forward flagged: emb is zero, its gradients too)
+        const float4 dE = fm_grad_row(ge[k], gy, S, e[k]);
+        float4 o4 = z;
+        if constexpr (XF == XF_MASK) {
+          o4 = keep_bytes(dE, ok ? mask4(xf.M, row, D, q) : 0u);
+        } else {
+          const float4 ev = e[k];
+          o4 = make_float4(ev.x != 0.f ? dE.x : 0.f, ev.y != 0.f ? dE.y : 0.f, ev.z != 0.f ? dE.z : 0.f,
+                           ev.w != 0.f ? dE.w : 0.f);
+          float4 sv = z;
+          if (ok) {
+            const float4 s4 = thr4(xf, row, q);
+            sv = make_float4(-o4.x * signf_(ev.x) * dsigmoid_(s4.x), -o4.y * signf_(ev.y) * dsigmoid_(s4.y),
+                             -o4.z * signf_(ev.z) * dsigmoid_(s4.z), -o4.w * signf_(ev.w) * dsigmoid_(s4.w));
+          }
+          if (joined) {
+            acc4(cs, sv);
+          } else if (xf.scs) {
+            if (act) st4(sg.svals + i * D + q * 4, sv);
+          } else {
+            float t = (sv.x + sv.y) + (sv.z + sv.w);
+#pragma unroll
+            for (int m = 1; m < LPR; m <<= 1) t += __shfl_xor(t, m);
+            if (act && q == 0) sg.svals[i] = t;
+          }
+        }
+        if (act) store_grad_row<LPR, false>(gvals, g1vals, nullptr, 0, i, q, o4, gy);
+      }
+    }
+  }
+  if constexpr (XF == XF_SOFT) {
+    if (joined) {      // (uniform over the grid: every workgroup but the bias one arrives here)
+      cs = slot_sum<LPR>(cs);
+      if (lane < LPR) st4(&red[threadIdx.x >> 6][lane * 4], cs);
+      column_join(red, D, sg.part, sg.ticket, sg.svals, xf.scs == 0, blk, nblk);
+    }
+  }
+}
+
+// any D <= kJoinMaxD (scalar accesses): wave per sample, lanes stride over d
+template <int XF>
+__global__ __launch_bounds__(kBlock) void k_gather_fm_xform_bwd_rows_anyD(
+    const int64_t *__restrict__ rows, const float *__restrict__ emb, const float *__restrict__ g_y,
+    const float *__restrict__ g_emb, float *__restrict__ gvals, float *__restrict__ g1vals,
+    int64_t B, int F, int D, int64_t N, float *__restrict__ gbias, Xform xf, SoftGrad sg) {
+  __shared__ __align__(16) float red[XF == XF_SOFT ? kWavesPerBlock : 1][kJoinMaxD];      // (written with st4)
+  int blk, nblk;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
+  const bool joined = XF == XF_SOFT && xf.srs == 0;
+  float cs[kJoinMaxD / kWave] = {0.f, 0.f, 0.f, 0.f};      // column lane + 64 j
+  for (int64_t b = wave0; b < B; b += nwaves) {
+    const int64_t base = b * F;
+    const float gy = g_y[b];
+    for (int f = lane; f < F; f += kWave) g1vals[base + f] = gy;
+#pragma unroll
+    for (int j = 0; j < kJoinMaxD / kWave; ++j) {
+      const int d = lane + j * kWave;
+      if (d >= D) continue;
+      float S = 0.f;
+      for (int f = 0; f < F; ++f) S += emb[(base + f) * D + d];
+      for (int f = 0; f < F; ++f) {
+        const int64_t o = (base + f) * D + d;
+        const int64_t row = rows[base + f];
+        const bool ok = (uint64_t)row < (uint64_t)N;
+        const float ev = emb[o];
+        const float dE = (g_emb ? g_emb[o] : 0.f) + gy * (S - ev);
+        if constexpr (XF == XF_MASK) {
+          gvals[o] = (ok && xf.M[row * D + d]) ? dE : 0.f;
+        } else {
+          const float g = ev != 0.f ? dE : 0.f;
+          gvals[o] = g;
+          const float sv = ok ? -g * signf_(ev) * dsigmoid_(xf.S[row * xf.srs + d * xf.scs]) : 0.f;
+          if (joined) cs[j] += sv;
+          else if (xf.scs) sg.svals[o] = sv;
+        }
+      }
+    }
+    if (XF == XF_SOFT && !joined && xf.scs == 0) {      // feature: one value per lookup, its columns summed over the wave
+      for (int f = 0; f < F; ++f) {
+        const int64_t row = rows[base + f];
+        const bool ok = (uint64_t)row < (uint64_t)N;
+        const float ds = ok ? dsigmoid_(xf.S[row * xf.srs]) : 0.f;
+        float t = 0.f;
+        for (int d = lane; d < D; d += kWave) {
+          const int64_t o = (base + f) * D + d;
+          t += -gvals[o] * signf_(emb[o]) * ds;      // (gvals[o]: this lane's own store above)
+        }
+        t = wave_sum(t);
+        if (lane == 0) sg.svals[base + f] = t;
+      }
+    }
+  }
+  if constexpr (XF == XF_SOFT) {
+    if (joined) {
+      for (int j = 0; j < kJoinMaxD / kWave; ++j) red[threadIdx.x >> 6][lane + j * kWave] = cs[j];
+      column_join(red, D, sg.part, sg.ticket, sg.svals, xf.scs == 0, blk, nblk);
+    }
+  }
 }
 
 // ------------------------------------------- backward, summed per slot ----
@@ -912,17 +1183,31 @@ inline bool fwd_shfl(int F, int nit) { return nit > 0 && F <= kWave; }
 // Chooses (LPR, NIT, SHFL), or the scalar kernel, and launches; the entry point has checked its arguments.  offsets == nullptr
 // (the ids are row numbers) is for the float4 form only: k_gather_fm_fwd_anyD reads offsets[f] unconditionally.
 // MASK: the kept-width kernels of the same (LPR, NIT, SHFL) choice, with keep / fwidth behind the common operands.
-template <bool MASK = false>
+// XF: the PEP transforms, xf their operand; a threshold with columns (or a mask) the float4 loads cannot take sends the
+// call to the scalar kernel.
+inline bool xform_float4_ok(int XF, const Xform &xf) {
+  if (XF == XF_SOFT) return xf.scs == 0 || (aligned16(xf.S) && (xf.srs & 3) == 0);
+  if (XF == XF_MASK) return (reinterpret_cast<uintptr_t>(xf.M) & 3u) == 0;
+  return true;
+}
+template <bool MASK = false, int XF = XF_NONE>
 int launch_gather_fm_fwd(const char *name, const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw,
                          const float *w1, int64_t ldw1, const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out,
                          float *sum_out, int64_t B, int F, int D, int64_t N, int *err, void *stream,
-                         const uint8_t *keep = nullptr, const int32_t *fwidth = nullptr) {
+                         const uint8_t *keep = nullptr, const int32_t *fwidth = nullptr, Xform xf = {}) {
   if (B == 0) return MI_OK;
   const int grid = grid_for_waves(B);
-  if (fwd_float4_ok(D, W, ldw, emb_out)) {
+  if (fwd_float4_ok(D, W, ldw, emb_out) && xform_float4_ok(XF, xf)) {
     const int lpr = D / 4, nit = nit_for(F, lpr);
     const bool shfl = fwd_shfl(F, nit);
-    if constexpr (MASK) {
+    if constexpr (XF != XF_NONE) {
+      decltype(&k_gather_fm_fwd_xform<1, 0, false, XF>) kernel = nullptr;
+#define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd_xform<LPR, NIT, true, XF> : k_gather_fm_fwd_xform<LPR, NIT, false, XF>
+      MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+      MI_LAUNCH(name, kernel, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out, B, F, N, ldw, ldw1,
+                err, sum_out, xf);
+    } else if constexpr (MASK) {
       decltype(&k_gather_fm_fwd_masked<1, 0, false>) kernel = nullptr;
 #define CALL(LPR, NIT) kernel = shfl ? k_gather_fm_fwd_masked<LPR, NIT, true> : k_gather_fm_fwd_masked<LPR, NIT, false>
       MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
@@ -940,7 +1225,10 @@ int launch_gather_fm_fwd(const char *name, const int64_t *idx, const int64_t *of
   } else {
     if (!offsets) return MI_ERR_INVALID_ARG;
     if (ldw != D || ldw1 != 1) return MI_ERR_UNSUPPORTED;      // the scalar fallback reads the reference's two tensors only
-    if constexpr (MASK)
+    if constexpr (XF != XF_NONE)
+      MI_LAUNCH(name, k_gather_fm_fwd_anyD_xform<XF>, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out,
+                rows_out, B, F, D, N, err, sum_out, xf);
+    else if constexpr (MASK)
       MI_LAUNCH(name, k_gather_fm_fwd_anyD_masked, grid, kBlock, stream, idx, offsets, W, w1, bias, emb_out, yfm_out, rows_out,
                 B, F, D, N, err, sum_out, keep, fwidth);
     else
@@ -960,6 +1248,30 @@ int gather_fm_fwd_sum(const int64_t *idx, const int64_t *offsets, const float *W
                               D, N, err, stream);
 }
 
+// the four threshold layouts of mi_xform_gather_*
+inline bool soft_strides_ok(int64_t srs, int64_t scs, int D) {
+  return (srs == 0 && (scs == 0 || scs == 1)) || (srs == 1 && scs == 0) || (srs == D && scs == 1);
+}
+
+template <int XF>
+int gather_fm_xform_bwd_rows(const char *name, const int64_t *rows, const float *emb, const float *g_y, const float *g_emb,
+                             float *gvals, float *g1vals, float *gbias, int64_t B, int F, int D, int64_t N, Xform xf,
+                             SoftGrad sg, void *stream) {
+  const int grid = grid_for_waves(B) + (gbias ? 1 : 0);      // + the workgroup that only sums the bias gradient
+  if (vec_ok(D) && all_aligned16(emb, gvals, g_emb) && xform_float4_ok(XF, xf) &&
+      (XF != XF_SOFT || xf.srs == 0 || xf.scs == 0 || aligned16(sg.svals))) {
+    const int lpr = D / 4, nit = nit_for(F, lpr);
+#define CALL(LPR, NIT)                                                                                              \
+  MI_LAUNCH(name, (k_gather_fm_xform_bwd_rows<LPR, NIT, XF>), grid, kBlock, stream, rows, emb, g_y, g_emb, gvals, g1vals, B, \
+            F, N, gbias, xf, sg)
+    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
+#undef CALL
+  } else {
+    MI_LAUNCH(name, k_gather_fm_xform_bwd_rows_anyD<XF>, grid, kBlock, stream, rows, emb, g_y, g_emb, gvals, g1vals, B, F, D,
+              N, gbias, xf, sg);
+  }
+  return launch_status();
+}
 }  // namespace
 
 extern "C" {
@@ -1125,6 +1437,67 @@ int mi_gather_fm_masked_bwd_dense(const int64_t *rows, const uint8_t *keep, cons
               gW, gw1, B, F, D, N, gbias, keep, fwidth);
   }
   return launch_status();
+}
+
+// ---- the PEP forms (DeepFM on PepEmbeeding: the threshold search; on RetrainPepEmbedding: the retraining table) ----
+int mi_gather_fm_soft_fwd(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1,
+                          int64_t ldw1, const float *bias, const float *S, int64_t srs, int64_t scs, float *emb_out,
+                          float *yfm_out, int64_t *rows_out, int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err,
+                          void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1 || !soft_strides_ok(srs, scs, D)) return MI_ERR_INVALID_ARG;
+  if (B > 0 && (!idx || !W || !w1 || !S || !emb_out || !yfm_out)) return MI_ERR_INVALID_ARG;
+  const Xform xf = {S, srs, scs, nullptr};
+  return launch_gather_fm_fwd<false, XF_SOFT>("gather_fm_soft_fwd", idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out,
+                                              rows_out, nullptr, B, F, D, N, err, stream, nullptr, nullptr, xf);
+}
+
+int mi_gather_fm_elemmask_fwd(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1,
+                              int64_t ldw1, const float *bias, const uint8_t *M, float *emb_out, float *yfm_out,
+                              int64_t *rows_out, int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw < D || ldw1 < 1) return MI_ERR_INVALID_ARG;
+  if (B > 0 && (!idx || !W || !w1 || !M || !emb_out || !yfm_out)) return MI_ERR_INVALID_ARG;
+  const Xform xf = {nullptr, 0, 0, M};
+  return launch_gather_fm_fwd<false, XF_MASK>("gather_fm_elemmask_fwd", idx, offsets, W, ldw, w1, ldw1, bias, emb_out, yfm_out,
+                                              rows_out, nullptr, B, F, D, N, err, stream, nullptr, nullptr, xf);
+}
+
+int64_t mi_gather_fm_soft_bwd_workspace_elems(int64_t B, int32_t D, int64_t srs) {
+  if (B <= 0 || D <= 0 || srs != 0) return 0;
+  return (int64_t)grid_for_waves(B) * D + 1;      // the workgroups' column sums, then the ticket
+}
+
+int mi_gather_fm_soft_bwd_rows(const int64_t *rows, const float *S, int64_t srs, int64_t scs, const float *emb,
+                               const float *g_y, const float *g_emb, float *gvals, float *svals, float *g1vals, float *gbias,
+                               float *workspace, int32_t armed, int64_t B, int32_t F, int32_t D, int64_t N, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || !soft_strides_ok(srs, scs, D)) return MI_ERR_INVALID_ARG;
+  if (D > kJoinMaxD) return MI_ERR_UNSUPPORTED;
+  if (B == 0 || F == 0) {      // no lookup: the summed forms still owe their zeros
+    if (srs == 0 && svals && hipMemsetAsync(svals, 0, sizeof(float) * (scs ? D : 1), (hipStream_t)stream) != hipSuccess)
+      return MI_ERR_LAUNCH;
+    if (B == 0) return MI_OK;
+  }
+  if (!rows || !S || !emb || !g_y || !gvals || !svals || !g1vals || (srs == 0 && !workspace)) return MI_ERR_INVALID_ARG;
+  const Xform xf = {S, srs, scs, nullptr};
+  SoftGrad sg = {svals, nullptr, nullptr};
+  if (srs == 0) {
+    sg.part = workspace;
+    sg.ticket = reinterpret_cast<unsigned *>(workspace + (int64_t)grid_for_waves(B) * D);
+    if (!armed && hipMemsetAsync(sg.ticket, 0, sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return MI_ERR_LAUNCH;
+  }
+  return gather_fm_xform_bwd_rows<XF_SOFT>("gather_fm_soft_bwd_rows", rows, emb, g_y, g_emb, gvals, g1vals, gbias, B, F, D, N,
+                                           xf, sg, stream);
+}
+
+int mi_gather_fm_elemmask_bwd_rows(const int64_t *rows, const uint8_t *M, const float *emb, const float *g_y,
+                                   const float *g_emb, float *gvals, float *g1vals, float *gbias, int64_t B, int32_t F,
+                                   int32_t D, int64_t N, void *stream) {
+  if (B < 0 || F < 0 || D <= 0 || N < 0) return MI_ERR_INVALID_ARG;
+  if (D > kJoinMaxD) return MI_ERR_UNSUPPORTED;
+  if (B == 0) return MI_OK;
+  if (!rows || !M || !emb || !g_y || !gvals || !g1vals) return MI_ERR_INVALID_ARG;
+  const Xform xf = {nullptr, 0, 0, M};
+  return gather_fm_xform_bwd_rows<XF_MASK>("gather_fm_elemmask_bwd_rows", rows, emb, g_y, g_emb, gvals, g1vals, gbias, B, F, D,
+                                           N, xf, SoftGrad{}, stream);
 }
 
 int mi_prefetch_rows(const int64_t *idx, const int64_t *offsets, const float *W, int64_t ldw, const float *w1, int64_t ldw1,

@@ -11,6 +11,7 @@ What runs where:
          (mi_tail_dgrad_gemm_fm) when the whole forward is one autograd node (_fused_step), else
          mi_gather_fm_bwd_{rows,dense}  (vanilla table), or
          mi_gather_fm_masked_{fwd,bwd_rows,bwd_dense}      (OptEmbed: a search candidate in eval, the retraining table), or
+         mi_gather_fm_{soft,elemmask}_{fwd,bwd_rows}       (PEP: the threshold search, the retraining table), or
          IEmbedding.forward + mi_fm_fwd / mi_fm_bwd        (compressed tables)
   the MLP tail (a real GEMM): the library's own fp32-MFMA products with BatchNorm1d / ReLU / Dropout in
       their operand loads and epilogues (tail.py, csrc/tail.hip) in training, eval() and no-BatchNorm stacks alike; the
@@ -25,6 +26,7 @@ from torch import nn
 from . import _kernels
 from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
+from .embeddings.pep_embedding import PepEmbeeding, RetrainPepEmbedding
 from .mlp import field_offsets, hidden_stack, run_tail
 
 
@@ -121,6 +123,12 @@ class DeepFM(nn.Module):
             W, keep, fwidth, sparse_W = mask
             return _kernels.gather_fm(x, self.offsets, W, self.fc.weight, self._bias, sparse_W=sparse_W,
                                       sparse_w1=bool(self.fc.sparse), keep=keep, fwidth=fwidth)
+        # PEP: the threshold search and the retraining table — the same launch with the soft threshold, or the element
+        # mask, applied to the looked-up rows
+        xform = emb_mod.fm_xform() if isinstance(emb_mod, (PepEmbeeding, RetrainPepEmbedding)) else None
+        if xform is not None:
+            return _kernels.gather_fm(x, self.offsets, xform.pop("W"), self.fc.weight, self._bias,
+                                      sparse_w1=bool(self.fc.sparse), **xform)
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

@@ -5,6 +5,8 @@ Same constructors, parameters (`emb.weight`, `s`; `mask` for the retrain variant
 types, checkpoint side files and `train_callback`.  The reference soft-thresholds the WHOLE table
 on every forward and then gathers; here the threshold (broadcast per type) is applied on the fly
 inside the gather (mi_xform_gather_fwd/bwd), so traffic is proportional to the looked-up rows.
+DeepFM asks the tables for `fm_xform()` and runs the threshold / the mask inside its fused gather + FM launch
+(mi_gather_fm_soft_* / mi_gather_fm_elemmask_*).
 """
 import os
 from typing import List, Optional, Union
@@ -97,7 +99,16 @@ class PepEmbeeding(IEmbedding):   # (sic: the reference's class name)
     def get_weight(self):
         return _kernels.soft_threshold_gather(self._all_ids(), self.emb.weight, self.s)
 
+    def fm_xform(self):
+        """DeepFM's fused lookup on this table: the operands of _kernels.gather_fm(..., soft=s), or None for a bag mode
+        (DeepFM then goes through forward())."""
+        if self._mode is not None:
+            return None
+        return dict(W=self.emb.weight, soft=self.s, sparse_W=False)
+
     def get_num_params(self) -> int:
+        if self.emb.weight.is_cuda:       # counted in one pass over the table and the thresholds, no soft(W) copy
+            return int(_kernels.soft_count_kept(self.emb.weight.detach(), self.s.detach()).item())
         return torch.count_nonzero(_soft(self.emb.weight, self.s)).item()
 
     def get_sparsity(self, get_n_params=False):
@@ -148,6 +159,13 @@ class RetrainPepEmbedding(IEmbedding):
     def get_weight(self):
         ids = torch.arange(self.emb.num_embeddings, device=self.emb.weight.device)
         return _kernels.masked_gather(ids, self.emb.weight, self.mask)
+
+    def fm_xform(self):
+        """DeepFM's fused lookup on this table: the operands of _kernels.gather_fm(..., elem_mask=mask) — sparse=True asks
+        for the table's gradient in row form —, or None for a bag mode."""
+        if self._mode is not None:
+            return None
+        return dict(W=self.emb.weight, elem_mask=self.mask, sparse_W=bool(self._sparse))
 
     def get_num_params(self):
         return self._nnz

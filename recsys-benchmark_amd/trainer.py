@@ -320,6 +320,32 @@ def train_epoch_cerp(dataloader, model, optimizer, device="cuda", log_step=10, p
     return dict({k: v / max(n, 1) for k, v in sums().items()}, sparsity=sparsity, num_params=num_params)
 
 
+def train_epoch_pep_deepfm(dataloader, model, optimizer, device="cuda", log_step=10, profiler=None, clip_grad=0,
+                           step: Optional[GraphedTrainStep] = None) -> Dict[str, float]:
+    """scripts/deepfm/train_deepfm_pep.py:23-80 of the reference: `train_epoch` on a PEP table; at every logging step the
+    table's sparsity is read and logged and `model.embedding.train_callback()` writes the milestone files
+    {checkpoint_weight_dir}/{sparsity}.pth it has passed.  Returns the reference's averaged "loss" plus the table's
+    "sparsity" / "num_params" after the epoch.  Pass the same `step` to successive epochs to keep one captured graph."""
+    model.train()
+    model.to(device)
+    if step is None:
+        step = GraphedTrainStep(model, optimizer, clip_grad=clip_grad)
+    first = float(step.loss_sum) if step.loss_sum is not None else 0.0
+
+    def log(idx):
+        with torch.no_grad():
+            sparsity, num_params = model.embedding.get_sparsity(True)
+        logger.info("Idx: %d - params: %d - sparsity: %.2g - loss: %.4g", idx, num_params, sparsity,
+                    (float(step.loss_sum) - first) / (idx + 1))
+        model.embedding.train_callback()
+
+    n = _run_epoch(dataloader, device, log_step, profiler, step, log)
+    _lib.check_index_errors()
+    with torch.no_grad():
+        sparsity, num_params = model.embedding.get_sparsity(True)
+    return {"loss": ((float(step.loss_sum) - first) / n) if n else 0.0, "sparsity": sparsity, "num_params": num_params}
+
+
 def train_epoch_optembed_deepfm(dataloader, model, optimizers, device="cuda", log_step=10, profiler=None, clip_grad=0,
                                 alpha=0) -> Dict[str, float]:
     """scripts/deepfm/train_deepfm_optembed.py:21-112 of the reference: a DeepFM epoch on the OptEmbed supernet, eager,
