@@ -1377,6 +1377,43 @@ MI_API int mi_ndcg_recall_rows(const int64_t *pred, int64_t ld, const int64_t *u
                                const int64_t *crow, const int64_t *col, int64_t U, int64_t nnz, const double *weight,
                                const double *ideal, double *ndcg, double *recall, int *err, void *stream);
 
+/* ---- CTR validation metric (src/trainer/deepfm.py:96-139 `validate_epoch`: sklearn's roc_auc_score and log_loss over
+ * the whole validation set) ---------------------------------------------------------------------------------------------
+ * mi_binary_auc: the area under the ROC curve of score fp32[n] against label uint8[n] as roc_auc_score computes it for
+ *   binary labels — the Mann-Whitney statistic, equal scores sharing their average rank — as an integer:
+ *     S = sum over the groups g of equal score of pos_g * (2 * neg_below_g + neg_g),   AUC = S / (2 P N).
+ *   key(score) = a monotone map of the float32 bits with -0.0 folded onto +0.0 (sklearn ties them); +-inf are the largest
+ *   and smallest ordinary keys; NaN is outside the order.  The negatives' keys are sorted by a stable radix sort (four
+ *   8-bit digits, least significant first; a positive travels as the key 0xffffffff, so the sorted negatives are the
+ *   first N words), then every positive adds its lower- and its upper-bound position among them.  Integer adds only up to
+ *   the one division: the record does not depend on the order of arrival and is the same bit for bit on every run.
+ *   Nothing is read back, nothing is allocated: 4 * 3 + 2 launches and one memset node on `stream`.
+ *   result: a device record of 48 bytes, 8-byte aligned —
+ *     uint64 S | int64 P (labels == 1) | int64 N (labels == 0) | int64 NaN scores | int64 labels outside {0, 1} | double auc.
+ *     auc = S / (2 P N) computed on the device; NaN when a score is NaN (S then says nothing), or P == 0, or N == 0.
+ *     A label outside {0, 1} is counted and belongs to neither class.
+ *   workspace: mi_binary_auc_workspace_bytes(n) bytes (about 9 n; 0 for n == 0, NULL is then fine), 16-byte aligned; no
+ *     state between calls and nothing in it needs zeroing (the record is zeroed by the memset node).
+ *   n <= 2^31 - 1, else MI_ERR_UNSUPPORTED (S < 2^63 follows); n == 0: MI_OK, counts zero, auc NaN.
+ * mi_ctr_metric_append: one launch per validation batch.  logits fp32[b] are copied to score_buf[at, at + b) (fp32[cap]),
+ *   the labels (int64[b] or fp32[b] by label_kind) to label_buf[at, at + b) (uint8[cap]) as 1, 0, or 2 for any other value,
+ *   and *loss_sum (a device double) grows by the batch's BCE-with-logits sum: each term
+ *   max(x, 0) - x * y + log1p(exp(-|x|)) in float64 from the float32 logit, summed in float64 in a fixed order (per-thread
+ *   strides, a fixed tree per workgroup, the workgroups' partials joined in index order by the last one to arrive):
+ *   reruns give the same bits.  The sigmoid is NOT applied: the caller ranks torch.sigmoid of the whole buffer, whose
+ *   float32 rounding decides the ties.
+ *   workspace: mi_ctr_metric_append_workspace_bytes() bytes, 8-byte aligned, ZERO before its first use; every launch
+ *     leaves it ready for the next (the arrival ticket is re-armed).  Launches that share one must run one after another.
+ *   at + b > cap (or a negative size, or a label_kind that is neither): MI_ERR_INVALID_ARG.  b == 0: MI_OK, no launch.   */
+#define MI_CTR_LABEL_INT64 0
+#define MI_CTR_LABEL_FLOAT32 1
+MI_API int64_t mi_binary_auc_workspace_bytes(int64_t n);
+MI_API int mi_binary_auc(const float *score, const uint8_t *label, int64_t n, void *workspace, void *result, void *stream);
+MI_API int64_t mi_ctr_metric_append_workspace_bytes(void);
+MI_API int mi_ctr_metric_append(const float *logits, const void *labels, int32_t label_kind, int64_t b, int64_t at,
+                                float *score_buf, uint8_t *label_buf, int64_t cap, double *loss_sum, void *workspace,
+                                void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.

@@ -6,6 +6,7 @@ C-ABI HIP library libmi355x_recsys.so (include/mi355x_recsys.h).  See DESIGN.md.
 from . import _lib
 from ._lib import MI355XLibraryError, check_index_errors
 from .cf_data import (DeviceCFGraphDataset, DeviceCFLoader, DeviceCFTestDataset, DeviceCFTestLoader, DeviceTruth)
+from .ctr_metric import CTRMetric
 from .deepfm import DeepFM
 from .embeddings import IEmbedding, NAME_TO_CLS, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import RetrainOptEmbed as DeepFMRetrainOptEmbed, build_retrain_deepfm, evol_search_deepfm
@@ -52,6 +53,6 @@ __all__ = [
     "LightGCN", "SingleLightGCN", "HCCFModelCore", "get_ctr_model", "get_graph_model", "load_ctr_model", "load_graph_model",
     "save_cf_emb_checkpoint", "save_ctr_checkpoint", "MI355XLibraryError", "check_index_errors", "use_deterministic_algorithms",
     "BCEWithLogitsLoss", "NeuMF", "ModelFlag", "prune", "prune_table", "to_pruned_tables", "evaluate_pruned", "search_min_item",
-    "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm",
+    "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "CTRMetric",
     "DeviceCFGraphDataset", "DeviceCFLoader", "DeviceCFTestDataset", "DeviceCFTestLoader", "DeviceTruth",
 ]

@@ -2429,3 +2429,73 @@ def ndcg_recall_rows(pred: torch.Tensor, users: torch.Tensor, crow: torch.Tensor
                                                ideal.data_ptr(), ndcg.data_ptr(), recall.data_ptr(),
                                                _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)), "mi_ndcg_recall_rows")
     return ndcg, recall
+
+
+# ---- CTR validation metric (csrc/ctr_metric.hip) -------------------------------------------------------------------------
+AUC_RECORD_WORDS = 6        # mi_binary_auc's record as int64 words: S | P | N | NaN scores | labels outside {0, 1} | auc (double)
+_auc_workspaces = {}
+
+
+def _auc_workspace(dev, n: int) -> torch.Tensor:
+    """mi_binary_auc's workspace, kept per device and size class (n rounded up to a power of two).  Launches that share one
+    must run one after the other (everything on one stream does); nothing in it is state."""
+    size = 1 << max(int(n) - 1, 0).bit_length()
+    nbytes = int(_lib.load().mi_binary_auc_workspace_bytes(min(size, 2**31 - 1)))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)      # a capture's memory belongs to its graph's pool
+    key = (torch.device(dev).index, size)
+    ws = _auc_workspaces.get(key)
+    if ws is None:
+        ws = _auc_workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def binary_auc_device(score: torch.Tensor, label: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mi_binary_auc of score float32 [n] against label uint8 [n] (both contiguous): the record as int64 [6] on the device
+    (`auc_record` decodes a host copy).  out: int64 [6] to write into.  No sync, no read-back."""
+    dev = _lib.require_gpu(score, label)
+    n = score.numel()
+    if score.dtype != torch.float32 or label.dtype != torch.uint8 or label.numel() != n:
+        raise ValueError(f"score float32 [n] and label uint8 [n] expected; got {score.dtype} {tuple(score.shape)}, "
+                         f"{label.dtype} {tuple(label.shape)}")
+    if not (score.is_contiguous() and label.is_contiguous()):
+        raise ValueError("score and label must be contiguous")
+    if out is None:
+        out = torch.empty(AUC_RECORD_WORDS, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.numel() != AUC_RECORD_WORDS or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous int64 [6] on the scores' device")
+    ws = _auc_workspace(dev, n) if n else None
+    _lib.check(_lib.load().mi_binary_auc(score.data_ptr(), label.data_ptr(), n, _lib.ptr(ws), out.data_ptr(),
+                                         _lib.stream_ptr(dev)), "mi_binary_auc")
+    return out
+
+
+def auc_record(words: torch.Tensor) -> dict:
+    """A host copy of mi_binary_auc's record (int64 [>= 6]) as {"S", "P", "N", "nan", "bad", "auc"}."""
+    words = words.cpu()
+    S, P, N, n_nan, n_bad = (int(v) for v in words[:5])
+    return {"S": S, "P": P, "N": N, "nan": n_nan, "bad": n_bad, "auc": float(words[5:6].view(torch.float64))}
+
+
+def ctr_metric_workspace(dev) -> torch.Tensor:
+    """A zeroed workspace of mi_ctr_metric_append (its launches re-arm it); one per accumulator."""
+    return torch.zeros(int(_lib.load().mi_ctr_metric_append_workspace_bytes()), dtype=torch.uint8, device=dev)
+
+
+def ctr_metric_append(logits: torch.Tensor, labels: torch.Tensor, at: int, score_buf: torch.Tensor, label_buf: torch.Tensor,
+                      loss_sum: torch.Tensor, ws: torch.Tensor) -> None:
+    """mi_ctr_metric_append: logits float32 [b] and labels (int64 or float32 [b]) into score_buf / label_buf at `at`, the
+    batch's BCE-with-logits sum onto loss_sum (float64 [1]).  One launch, no sync."""
+    dev = _lib.require_gpu(logits, labels, score_buf, label_buf, loss_sum, ws)
+    b = logits.numel()
+    if logits.dtype != torch.float32 or labels.dtype not in (torch.int64, torch.float32) or labels.numel() != b:
+        raise ValueError(f"logits float32 [b] and labels int64 / float32 [b] expected; got {logits.dtype} "
+                         f"{tuple(logits.shape)}, {labels.dtype} {tuple(labels.shape)}")
+    if score_buf.dtype != torch.float32 or label_buf.dtype != torch.uint8 or label_buf.numel() != score_buf.numel() \
+            or loss_sum.dtype != torch.float64:
+        raise ValueError("score_buf float32 [cap], label_buf uint8 [cap] and loss_sum float64 [1] expected")
+    logits, labels = logits.contiguous(), labels.contiguous()
+    _lib.check(_lib.load().mi_ctr_metric_append(logits.data_ptr(), labels.data_ptr(), 0 if labels.dtype == torch.int64 else 1,
+                                                b, int(at), score_buf.data_ptr(), label_buf.data_ptr(), score_buf.numel(),
+                                                loss_sum.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),
+               "mi_ctr_metric_append")

@@ -205,6 +205,10 @@ SIGNATURES = {
     "mi_cf_sample_triples": [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i32, _i64, _i32, _p, _i64, _i64, _i64, _i64, _p, _p,
                              _p, _p, _p],
     "mi_ndcg_recall_rows": [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p],
+    "mi_binary_auc_workspace_bytes": [_i64],
+    "mi_binary_auc": [_p, _p, _i64, _p, _p, _p],
+    "mi_ctr_metric_append_workspace_bytes": [],
+    "mi_ctr_metric_append": [_p, _p, _i32, _i64, _i64, _p, _p, _i64, _p, _p, _p],
     "mi_comm_available": [],
     "mi_comm_unique_id": [ctypes.c_char_p],
     "mi_comm_init": [ctypes.c_char_p, _i32, _i32, ctypes.POINTER(ctypes.c_void_p)],
@@ -223,7 +227,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_dual_table_bwd_workspace_elems": ctypes.c_int64, "mi_reg_prune_rows_workspace_elems": ctypes.c_int64,
              "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64,
              "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64,
-             "mi_gather_fm_soft_bwd_workspace_elems": ctypes.c_int64}
+             "mi_gather_fm_soft_bwd_workspace_elems": ctypes.c_int64, "mi_binary_auc_workspace_bytes": ctypes.c_int64,
+             "mi_ctr_metric_append_workspace_bytes": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

@@ -78,6 +78,35 @@ __device__ __forceinline__ void st4_nt(float *p, float4 v) {
   __builtin_nontemporal_store(x, reinterpret_cast<f32x4_t *>(p));
 }
 
+// ---- integer scans over a wave / the 256-thread workgroup (mag_prune.hip, ctr_metric.hip) ---------------------------
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    uint32_t o = __shfl_up(v, d);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// exclusive scan of one value per thread over the 256-thread workgroup; *total = the sum.  `sm` holds 4 words.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sm, uint32_t *total) {
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  uint32_t inc = wave_incl_scan(v);
+  __syncthreads();                       // sm may still be read from an earlier call
+  if (lane == kWave - 1) sm[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0, t = 0;
+#pragma unroll
+  for (int w = 0; w < kWavesPerBlock; ++w) {
+    uint32_t s = sm[w];
+    if (w < wave) base += s;
+    t += s;
+  }
+  *total = t;
+  return base + inc - v;
+}
+
 // "last workgroup sums the partials" without agent-scope fences (on gfx950 a __threadfence() is an L2 write-back +
 // invalidate per workgroup: the loss kernels took 13 us with it).  ONE lane per workgroup publishes: the partials travel
 // as device-scope (sc1, write-through) stores, an explicit `s_waitcnt vmcnt(0)` holds the lane until those stores have

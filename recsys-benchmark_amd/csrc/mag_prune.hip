@@ -54,34 +54,6 @@ __device__ __forceinline__ bool is_protected(const uint2 *cut, uint32_t r, uint3
   return key > q.x || (key == q.x && c <= q.y);
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & (kWave - 1);
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    uint32_t o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive scan of one value per thread over the 256-thread workgroup; *total = the sum.  `sm` holds 4 words.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sm, uint32_t *total) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  uint32_t inc = wave_incl_scan(v);
-  __syncthreads();                       // sm may still be read from an earlier call
-  if (lane == kWave - 1) sm[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, t = 0;
-#pragma unroll
-  for (int w = 0; w < kWavesPerBlock; ++w) {
-    uint32_t s = sm[w];
-    if (w < wave) base += s;
-    t += s;
-  }
-  *total = t;
-  return base + inc - v;
-}
-
 // The bucket of `hist` (BINS bins) that holds the krem-th smallest element (1-based) and the rank inside it:
 // res[0] = bucket, res[1] = krem - (elements below the bucket), res[2] = hist[bucket].  krem == 0 gives (0, 0, hist[0]).
 // Every thread of the workgroup calls it; the result is in res[] (LDS, 3 words) after the call.

@@ -509,13 +509,13 @@ def _mutate(top: List[Candidate], n_mutate: int, p_mutate: float, hidden_size: i
     return out
 
 
-def _validate_candidate(model, candidate: Candidate, val_loader, forward=None) -> float:
+def _validate_candidate(model, candidate: Candidate, val_loader, forward=None, metric=None) -> float:
     """AUC of the model under the candidate (deepfm_opt_embed.py:388-410): set_candidate, then one validation pass."""
     from ..trainer import validate_epoch
 
     model.eval()
     model.embedding.set_candidate(candidate.save_mask)
-    return validate_epoch(val_loader, model, device=model.embedding._weight.device, forward=forward)["auc"]
+    return validate_epoch(val_loader, model, device=model.embedding._weight.device, forward=forward, metric=metric)["auc"]
 
 
 def evol_search_deepfm(model, n_generations: int, population: int, n_crossover: int, n_mutate: int, p_mutate: float, k: int,
@@ -528,12 +528,13 @@ def evol_search_deepfm(model, n_generations: int, population: int, n_crossover: 
     Returns (mask, best AUC); `history`, if given, receives the best AUC after each generation.
 
     A candidate costs set_candidate (a few bytes per field, or one byte per row) plus one validation pass through the
-    masked gather_fm; ONE GraphedForward serves all candidates, their widths living in persistent buffers.  The model
-    stays on its device (the reference moves it to "cuda"); the candidates are drawn and kept where the table is.
+    masked gather_fm; ONE GraphedForward and ONE CTRMetric (its buffers allocated once) serve all candidates, their widths
+    living in persistent buffers.  The model stays on its device (the reference moves it to "cuda"); the candidates are
+    drawn and kept where the table is.
 
     Deliberate deviation: every redraw loop is bounded at MAX_REDRAWS = 10 000 tries and then raises RuntimeError
     naming the target; the reference loops forever on a target its draws cannot reach."""
-    from ..trainer import GraphedForward
+    from ..trainer import CTRMetric, GraphedForward
 
     emb = model.embedding
     assert isinstance(emb, OptEmbed)
@@ -543,11 +544,13 @@ def evol_search_deepfm(model, n_generations: int, population: int, n_crossover: 
     d_target = d_target_sparsity(target_sparsity, sub_mask, emb._num_item)
     candidates = [_generate_candidate(emb, target_sparsity, d_target, method) for _ in range(population)]
     forward = GraphedForward(model)
+    val_dataset = getattr(val_dataloader, "dataset", None)
+    metric = CTRMetric(emb._weight.device, capacity=len(val_dataset) if hasattr(val_dataset, "__len__") else None)
     top: List[Candidate] = []
     top_values = None
     try:
         for gen in range(n_generations):
-            metrics = torch.tensor([_validate_candidate(model, c, val_dataloader, forward) for c in candidates],
+            metrics = torch.tensor([_validate_candidate(model, c, val_dataloader, forward, metric) for c in candidates],
                                    dtype=torch.float64)
             top_values = metrics if top_values is None else torch.cat((top_values, metrics))
             top.extend(candidates)

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, losses
 from .cf_data import DeviceTruth
+from .ctr_metric import CTRMetric, _binary_auc_torch, binary_auc  # noqa: F401  (binary_auc's home was here)
 from .lightgcn import get_sparsity_and_param, score_topk, train_items_csr
 
 logger = logging.getLogger("recsys_benchmark_amd.trainer")
@@ -384,21 +385,6 @@ def train_epoch_optembed_deepfm(dataloader, model, optimizers, device="cuda", lo
     return {"loss": avg[0], "loss_s": avg[1], "sparsity": sparsity, "num_params": num_params}
 
 
-def binary_auc(y_true: torch.Tensor, y_score: torch.Tensor) -> float:
-    """Area under the ROC curve as sklearn.metrics.roc_auc_score computes it for binary labels (ties share their average
-    rank: the Mann-Whitney statistic), on the device in float64."""
-    y_true = y_true.reshape(-1).to(torch.float64)
-    uniq, inverse, counts = torch.unique(y_score.reshape(-1), sorted=True, return_inverse=True, return_counts=True)
-    ends = torch.cumsum(counts, 0).to(torch.float64)
-    avg_rank = ends - (counts.to(torch.float64) - 1.0) / 2.0          # 1-based average rank of each distinct score
-    n_pos = y_true.sum()
-    n_neg = y_true.numel() - n_pos
-    if float(n_pos) == 0.0 or float(n_neg) == 0.0:
-        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
-    rank_sum = (avg_rank[inverse] * y_true).sum()
-    return float((rank_sum - n_pos * (n_pos + 1.0) / 2.0) / (n_pos * n_neg))
-
-
 class GraphedForward:
     """model(x) under no_grad with the forward of each input shape seen twice replayed as a hipGraph (the first call of a
     shape runs eagerly).  The returned tensor is the graph's static output: consume it before the next call."""
@@ -421,26 +407,26 @@ class GraphedForward:
 
 
 @torch.no_grad()
-def validate_epoch(val_loader, model, device="cuda", forward: Optional[GraphedForward] = None) -> Dict[str, float]:
-    """src/trainer/deepfm.py:96-139: {"auc", "log_loss"}; labels and predictions stay on the device, the forward of the
-    full-size batches is replayed as a hipGraph.  `forward` (optional): a GraphedForward of this model to keep using —
-    the mask search scores every candidate through one (evol_search_deepfm)."""
+def validate_epoch(val_loader, model, device="cuda", forward: Optional[GraphedForward] = None,
+                   metric: Optional[CTRMetric] = None) -> Dict[str, float]:
+    """src/trainer/deepfm.py:96-139: {"auc", "log_loss"}; labels and logits stay on the device (one append launch per
+    batch, ctr_metric.CTRMetric), the forward of the full-size batches is replayed as a hipGraph.  `forward` (optional): a
+    GraphedForward of this model to keep using; `metric` (optional): a CTRMetric on `device` to keep using (it is reset
+    here) — the mask search scores every candidate through one of each (evol_search_deepfm)."""
     model.eval()
     model = model.to(device)
     if forward is None:
         forward = GraphedForward(model)
-    criterion = torch.nn.BCEWithLogitsLoss(reduction="sum")
-    log_loss = torch.zeros((), dtype=torch.float64, device=device)
-    y_true, y_pred = [], []
+    if metric is None:
+        dataset = getattr(val_loader, "dataset", None)
+        metric = CTRMetric(device, capacity=len(dataset) if hasattr(dataset, "__len__") else None)
+    else:
+        metric.reset()
     for inputs, labels in val_loader:
         inputs, labels = inputs.to(device), labels.to(device)
-        outputs = forward(inputs)
-        log_loss += criterion(outputs, labels.float())
-        y_true.append(labels.reshape(-1))
-        y_pred.append(torch.sigmoid(outputs).reshape(-1))
-    y_true, y_pred = torch.cat(y_true), torch.cat(y_pred)
+        metric.add(forward(inputs), labels)
     _lib.check_index_errors()
-    return {"auc": binary_auc(y_true, y_pred), "log_loss": float(log_loss) / y_pred.numel()}
+    return metric.compute()
 
 
 # --------------------------------------------------------------------------------------------------------------------
