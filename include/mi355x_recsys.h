@@ -211,6 +211,78 @@ MI_API int mi_gather_fm_elemmask_bwd_rows(const int64_t *rows, const uint8_t *M,
                                           float *gvals, float *g1vals, float *gbias,
                                           int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
 
+/* ---- the same launch over the two-table compositional embeddings (DeepFM on QR hashing, CERP, CERP retrain) ----
+ * src/models/embeddings/qr_embedding.py:84-109, cerp_embedding.py:160-175 and :329-367 under src/models/deepfm.py:88-98.
+ * mi_gather_fm_dual_fwd: for idx int64[B,F], offsets int64[F] (nullable: the ids are row numbers),
+ *     row        = idx[b,f] + offsets[f]
+ *     emb[b,f,:] = T1'[row % mod1] (op) T2'[row / div2]       T1 fp32[n1,De], T2 fp32[n2,De]
+ *     y_fm[b]    = 0.5 (|sum_f e|^2 - sum_f |e|^2) + sum_f w1[row * ldw1] + bias[0]      (bias nullable)
+ *   op 0 mult / 1 add; T' = T (xform 0), sign(T) relu(|T| - sigmoid(S)) (xform 1, S1 / S2 fp32 shaped like the tables) or
+ *   M ? T : +0 (xform 2, M1 / M2 uint8 shaped like the tables).  Served: (mult, none), (add, none), (add, soft),
+ *   (add, mask); every other pair (op 2 cat among them) is MI_ERR_UNSUPPORTED and the caller keeps mi_dual_gather_fwd +
+ *   mi_fm_fwd.  The element transforms are mi_dual_gather_fwd's device functions: emb has that lookup's bits, signed
+ *   zeros included.  rows_out int64[B,F] (nullable) = row; rows_bwd int64[B,F] (nullable) = row where the lookup was served, -1
+ *   where it was flagged: the ids for mi_dual_gather_bwd_fields / _bwd_rows, which check table bounds only.  A row outside [0, N) (N = rows of w1), or one the tables do not
+ *   cover (row % mod1 >= n1, row / div2 >= n2), reads as zeros everywhere and ORs MI_IDX_OUT_OF_RANGE into *err.
+ *   De <= MI_GATHER_FM_DUAL_MAX_D; De = 4 * 2^k <= 256 with 16-byte aligned operands runs float4 kernels, any other De
+ *   the scalar ones.
+ * mi_gather_fm_dual_bwd_rows: the row-form backward from the saved emb and rows (= rows_out), no float atomics.  With
+ *   dE[i,:] = g_emb[i,:] + g_y[b] (S_b - emb[i,:]), i = b F + f, S_b = sum_f emb[b,f,:] (g_emb nullable):
+ *     keys1[i] = row % mod1,  keys2[i] = row / div2   (int64; 0 for a row the forward flagged, whose value rows are zeros)
+ *     add : c1[i,:] = dE [M1[keys1,:]],  c2[i,:] = dE [M2[keys2,:]]  — the masks only when M1 / M2 are given (values masked
+ *           per lookup: the COO gradients of the retrain table); without them c1 == c2 and c2 may be NULL
+ *     mult: c1[i,:] = dE * T2[keys2,:],  c2[i,:] = dE * T1[keys1,:]   (c2 required)
+ *     g1vals[i] = g_y[b];  gbias[0] = sum_b g_y[b] in a fixed order (nullable)
+ *   field_off int64[F] (nullable; the forward's offsets), for a caller that sums in the order of mi_sort_field_rows: a row
+ *   outside [field_off[f], field_off[f+1]) (the last field ends at N) counts as flagged too — what that sort drops —, and a
+ *   flagged lookup of field f gets keys2 = the largest table-2 row of field f (value rows still zero), so that keys2 taken
+ *   through the sort's permutation is monotone.
+ * mi_gather_fm_dual_finish: the transform's derivative, once per table element AFTER the sums (A1 fp32[n1,De], A2 fp32[n2,De],
+ *   in place; either may be NULL and is then skipped):
+ *     mask: A = M ? A : 0
+ *     soft: kept = |T| - sigmoid(S) > 0;  gS = -sign(T) sig(S) (1 - sig(S)) kept A;  A = kept A
+ *   kept comes from the table and its threshold, never from looked-up values: a kept element that holds exactly 0 keeps its
+ *   gradient, a pruned or masked one gets exactly 0; sig (1 - sig) is formed from the fp32 sigmoid (exactly 0 at s = +-150).
+ *   xform 0 launches nothing.
+ */
+#define MI_GATHER_FM_DUAL_MAX_D 1024
+MI_API int mi_gather_fm_dual_fwd(const int64_t *idx, const int64_t *offsets,
+                                 const float *T1, const float *T2, const float *S1, const float *S2,
+                                 const uint8_t *M1, const uint8_t *M2,
+                                 const float *w1, int64_t ldw1, const float *bias,
+                                 float *emb_out, float *yfm_out, int64_t *rows_out, int64_t *rows_bwd,
+                                 int64_t B, int32_t F, int32_t De, int64_t N,
+                                 int64_t n1, int64_t n2, int64_t mod1, int64_t div2, int32_t op, int32_t xform,
+                                 int32_t *err, void *stream);
+MI_API int mi_gather_fm_dual_bwd_rows(const int64_t *rows, const int64_t *field_off, const float *emb, const float *g_y, const float *g_emb,
+                                      const float *T1, const float *T2, const uint8_t *M1, const uint8_t *M2,
+                                      float *c1, float *c2, int64_t *keys1, int64_t *keys2,
+                                      float *g1vals, float *gbias,
+                                      int64_t B, int32_t F, int32_t De, int64_t N,
+                                      int64_t n1, int64_t n2, int64_t mod1, int64_t div2, int32_t op, void *stream);
+MI_API int mi_gather_fm_dual_finish(float *A1, float *A2, const float *T1, const float *T2,
+                                    const float *S1, const float *S2, const uint8_t *M1, const uint8_t *M2,
+                                    float *gS1, float *gS2, int64_t n1, int64_t n2, int32_t De, int32_t xform,
+                                    void *stream);
+
+/* ---- CERP's whole-table prune loss (DeepFM's search step) ----
+ * src/models/embeddings/cerp_embedding.py get_prune_loss: -tanh((soft(P,Sp) + soft(Q,Sq)) K).norm(2)**2 over four
+ * fp32 tables of n = bucket * D elements each (contiguous, equal shapes).
+ * mi_cerp_prune_loss_fwd: out[0] = -sum tanh(K (soft(P,Sp) + soft(Q,Sq)))^2, one launch, one read of each table, no
+ *   [bucket, D] temporary; the workgroups' partial sums are added in a fixed order by the last workgroup to take a ticket
+ *   (the same bits on every run).  workspace: mi_cerp_prune_loss_workspace_elems(n) floats whose LAST word is the ticket;
+ *   armed != 0 says it is zero already (every launch leaves it zero), armed = 0 zeroes it first.
+ * mi_cerp_prune_loss_bwd: with x = soft(P,Sp) + soft(Q,Sq), t = tanh(K x), g = -2 K t (1 - t^2) grad_out[0]:
+ *     gP = kept_p g,  gSp = -sign(P) sig(Sp) (1 - sig(Sp)) kept_p g,  kept_p = |P| - sig(Sp) > 0   (gQ, gSq alike)
+ *   every element of the four outputs written once with a plain store: no zero fill, no atomics.
+ */
+MI_API int64_t mi_cerp_prune_loss_workspace_elems(int64_t n);
+MI_API int mi_cerp_prune_loss_fwd(const float *P, const float *Sp, const float *Q, const float *Sq, int64_t n,
+                                  float k_tanh, float *workspace, int32_t armed, float *out, void *stream);
+MI_API int mi_cerp_prune_loss_bwd(const float *P, const float *Sp, const float *Q, const float *Sq, int64_t n,
+                                  float k_tanh, const float *grad_out, float *gP, float *gSp, float *gQ, float *gSq,
+                                  void *stream);
+
 /* ---- a2: plain row gather (IEmbedding.forward on a vanilla table) ----------
  * src/models/embeddings/base.py:74-75 (nn.Embedding on int64[n] ids, already
  * offset).  out fp32[n,D].

@@ -404,14 +404,17 @@ def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False, keep=N
     return emb, yfm
 
 
-def soft_count_kept(W: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+def soft_count_kept(W: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Device int64 [1]: the number of non-zeros of sign(W) relu(|W| - sigmoid(s)), counted in one pass over W and s
-    (mi_soft_count_kept) — no thresholded copy of the table."""
-    dev = _lib.require_gpu(W, s)
+    (mi_soft_count_kept) — no thresholded copy of the table.  out (optional): the int64 [1] to write, e.g. one element of
+    a tensor that collects several tables' counts for one host read."""
+    dev = _lib.require_gpu(W, s, out)
     Wc, Sc = _f32c(W), _f32c(s)
     N, D = Wc.shape
     srs, scs = _soft_strides(s, N, D)
-    count = torch.empty(1, dtype=torch.int64, device=dev)
+    if out is not None and (out.dtype != torch.int64 or out.numel() != 1):
+        raise ValueError(f"out must be int64 [1], got {out.dtype} {tuple(out.shape)}")
+    count = torch.empty(1, dtype=torch.int64, device=dev) if out is None else out
     _lib.check(_lib.load().mi_soft_count_kept(Wc.data_ptr(), Sc.data_ptr(), srs, scs, N, D, count.data_ptr(),
                                               _lib.stream_ptr(dev)), "mi_soft_count_kept")
     return count
@@ -757,6 +760,298 @@ def dual_table(T1, T2, N, mod1, div2, op="add", S1=None, S2=None, M1=None, M2=No
     the order of the float additions only).  Check `dual_table_supported` first."""
     xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
     return DualTable.apply(T1, T2, S1, S2, M1, M2, int(N), int(mod1), int(div2), OPS[op], xform)
+
+
+# --------------------------------------------------------------------------------------
+# DeepFM on the two-table family: lookup + FM + first-order in one launch (csrc/gather_fm_dual.hip)
+DUAL_FM_MAX_D = 1024      # MI_GATHER_FM_DUAL_MAX_D
+
+
+def _sum_sorted(keys_sorted, perm, vals, nrows: int, D: int) -> torch.Tensor:
+    """[nrows, D] sums of vals[perm[i]] per keys_sorted[i], added in a fixed order (mi_coalesce_rows_sorted)."""
+    n = keys_sorted.numel()
+    out = torch.zeros((nrows, D), dtype=torch.float32, device=vals.device)
+    acc = torch.empty((n, D), dtype=torch.float32, device=vals.device)
+    _lib.check(_lib.load().mi_coalesce_rows_sorted(keys_sorted.data_ptr(), perm.data_ptr(), vals.data_ptr(), out.data_ptr(),
+                                                   acc.data_ptr(), n, D, nrows, _lib.stream_ptr(vals.device)),
+               "mi_coalesce_rows_sorted")
+    return out
+
+
+class GatherFMDual(torch.autograd.Function):
+    """emb, y_fm of DeepFM over a two-table compositional embedding in one launch (mi_gather_fm_dual_fwd):
+    emb[b, f] = T1'[row % mod1] (op) T2'[row // div2], row = idx[b, f] + offsets[f]; y_fm over that emb plus the
+    first-order bag over `row`.  (op, transform) as the models produce them: (mult, none) and (add, none) for QR,
+    (add, soft: S1 / S2) for CERP, (add, mask: M1 / M2) for CERP retrain.
+
+    Backward.  Deterministic mode, and every COO gradient other than QR's: mi_gather_fm_dual_bwd_rows writes a value row
+    per lookup and table plus the table-row keys; dense gradients are those rows summed per key in a fixed order
+    (table 2's keys are monotone in `row`, so the per-field sort of the rows orders them; table 1 takes a stable sort
+    of its keys) and the transform's derivative is applied once per table element (mi_gather_fm_dual_finish) — no float
+    atomics.  Default mode otherwise: dE from mi_gather_fm_bwd_rows goes to the atomic kernels of the separate lookup
+    (mi_dual_gather_bwd_fields / _bwd_rows): the launches it ran before, minus one add.  The two forms have not been
+    timed against each other ("Not measured")."""
+
+    @staticmethod
+    def forward(ctx, idx, offsets, T1, T2, w1, bias, S1, S2, M1, M2, mod1: int, div2: int, op: int, sparse1: bool,
+                sparse2: bool, sparse_w1: bool, fields):
+        dev = _lib.require_gpu(idx, offsets, T1, T2, w1, bias, S1, S2, M1, M2)
+        lib = _lib.load()
+        if (S1 is None) != (S2 is None) or (M1 is None) != (M2 is None):
+            raise ValueError("gather_fm_dual: the thresholds S1 / S2 (and the masks M1 / M2) come in pairs")
+        if S1 is not None and M1 is not None:
+            raise ValueError("gather_fm_dual: soft (S1 / S2) and mask (M1 / M2) exclude each other")
+        if op == OPS["cat"]:
+            raise NotImplementedError('gather_fm_dual: "cat" changes the field count; it keeps dual_gather + fm_first_order')
+        xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
+        if op == OPS["mult"] and xform != XF_NONE:
+            raise NotImplementedError("gather_fm_dual: mult goes with untransformed tables only")
+        if T1.dim() != 2 or T2.dim() != 2 or T1.shape[1] != T2.shape[1]:
+            raise ValueError(f"gather_fm_dual: both tables must share the row width, got {tuple(T1.shape)} and {tuple(T2.shape)}")
+        for name, t, table in (("S1", S1, T1), ("S2", S2, T2), ("M1", M1, T1), ("M2", M2, T2)):
+            if t is not None and tuple(t.shape) != tuple(table.shape):
+                raise ValueError(f"gather_fm_dual: {name} must be shaped like its table {tuple(table.shape)}, got {tuple(t.shape)}")
+        for name, m in (("M1", M1), ("M2", M2)):
+            if m is not None and m.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"gather_fm_dual: {name} must be bool or uint8, got {m.dtype}")
+        if xform == XF_SOFT and (sparse1 or sparse2):
+            raise ValueError("gather_fm_dual: a soft-thresholded table has no row-form gradient")
+        De = int(T1.shape[1])
+        if De > DUAL_FM_MAX_D:
+            raise NotImplementedError(f"gather_fm_dual covers De <= {DUAL_FM_MAX_D}, got {De}")
+        idx = _i64c(idx)
+        offsets = _i64c(offsets.reshape(-1))
+        if idx.dim() != 2 or idx.shape[1] != offsets.numel():
+            raise ValueError(f"idx must be [B, {offsets.numel()}], got {tuple(idx.shape)}")
+        T1c, T2c = _f32c(T1), _f32c(T2)
+        S1c = None if S1 is None else _f32c(S1)
+        S2c = None if S2 is None else _f32c(S2)
+        M1c = None if M1 is None else M1.contiguous().view(torch.uint8)      # (a bool is one byte, 0 or 1: read in place)
+        M2c = None if M2 is None else M2.contiguous().view(torch.uint8)
+        w1c, ldw1 = _row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
+        B, F = idx.shape
+        N = int(w1c.shape[0])
+        if w1c.numel() != N and ldw1 == 1:
+            raise ValueError("first-order table must have one weight per embedding row")
+        emb = torch.empty((B, F, De), dtype=torch.float32, device=dev)
+        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
+        rows = torch.empty((B, F), dtype=torch.int64, device=dev)
+        # the default-mode backward hands the row ids to kernels that check table bounds only: they get the ids with -1
+        # where this launch flagged the lookup (a row past N may still map inside both tables)
+        qr_rows = sparse2 and not sparse1 and xform == XF_NONE
+        atomic_bwd = not DETERMINISTIC and (qr_rows or not (sparse1 or sparse2))
+        rows_bwd = torch.empty_like(rows) if atomic_bwd and any(ctx.needs_input_grad[i] for i in (2, 3, 6, 7)) else None
+        _lib.check(
+            lib.mi_gather_fm_dual_fwd(
+                idx.data_ptr(), offsets.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
+                _lib.ptr(M1c), _lib.ptr(M2c), w1c.data_ptr(), ldw1, _lib.ptr(bias), emb.data_ptr(), yfm.data_ptr(),
+                rows.data_ptr(), _lib.ptr(rows_bwd), B, F, De, N, T1c.shape[0], T2c.shape[0], int(mod1), int(div2), op, xform,
+                _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+            ),
+            "mi_gather_fm_dual_fwd",
+        )
+        if sparse1 or sparse2 or sparse_w1 or DETERMINISTIC:
+            note_field_layout(rows, offsets, N)
+        # (tables and thresholds are autograd inputs: saved, so that an in-place update before the backward raises)
+        ctx.save_for_backward(emb, rows, T1c, T2c, *((S1c, S2c) if xform == XF_SOFT else ()))
+        ctx.masks = (M1c, M2c)      # (constants of the step, not autograd inputs)
+        ctx.rows_bwd, ctx.offsets = rows_bwd, offsets
+        ctx.meta = (B, F, De, N, int(mod1), int(div2), op, xform, tuple(T1.shape), tuple(T2.shape), tuple(w1.shape))
+        ctx.sparse = (bool(sparse1), bool(sparse2), bool(sparse_w1))
+        ctx.fields = fields if (fields is not None and fields[3] == F) else None
+        ctx.has_bias = bias is not None
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(rows)
+        return emb, yfm, rows
+
+    @staticmethod
+    def backward(ctx, g_emb, g_y, _g_rows):
+        emb, rows, T1c, T2c = ctx.saved_tensors[:4]
+        B, F, De, N, mod1, div2, op, xform, T1shape, T2shape, w1shape = ctx.meta
+        S1c, S2c = ctx.saved_tensors[4:6] if xform == XF_SOFT else (None, None)
+        M1c, M2c = ctx.masks
+        sparse1, sparse2, sparse_w1 = ctx.sparse
+        dev = emb.device
+        lib = _lib.load()
+        stream = _lib.stream_ptr(dev)
+        need_T1, need_T2, need_w1 = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        need_b = ctx.has_bias and ctx.needs_input_grad[5]
+        need_S = xform == XF_SOFT and (ctx.needs_input_grad[6] or ctx.needs_input_grad[7])
+        n1, n2 = T1c.shape[0], T2c.shape[0]
+        n = B * F
+
+        def done(gT1=None, gT2=None, gw1=None, gb=None, gS1=None, gS2=None):
+            return (None, None, gT1, gT2, gw1, gb, gS1, gS2) + (None,) * 9
+
+        if g_emb is None and g_y is None:
+            return done()
+        if n == 0:      # no lookup: zero gradients in every shape
+            def zero(shape, sparse, need):
+                if not need:
+                    return None
+                if sparse:
+                    return _coo(torch.empty((0,), dtype=torch.int64, device=dev),
+                                torch.empty((0,) + tuple(shape[1:]), dtype=torch.float32, device=dev), shape)
+                return torch.zeros(shape, dtype=torch.float32, device=dev)
+            return done(zero(T1shape, sparse1, need_T1), zero(T2shape, sparse2, need_T2), zero(w1shape, sparse_w1, need_w1),
+                        torch.zeros((1,), dtype=torch.float32, device=dev) if need_b else None,
+                        torch.zeros_like(S1c) if need_S else None, torch.zeros_like(S2c) if need_S else None)
+        if g_y is None:
+            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
+        g_y = _f32c(g_y)
+        g_emb = None if g_emb is None else _f32c(g_emb)
+        if not (need_T1 or need_T2 or need_w1 or need_S):
+            return done(gb=g_y.sum().view(1) if need_b else None)
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+        g1vals = torch.empty((n,), dtype=torch.float32, device=dev)
+        gT1 = gT2 = gS1 = gS2 = None
+        qr_rows = sparse2 and not sparse1 and xform == XF_NONE      # QR(sparse=True): emb2 as COO, emb1 dense
+        own = DETERMINISTIC or ((sparse1 or sparse2) and not qr_rows)
+        order = None      # (sorted rows, permutation) of the per-field sort, shared by table 2 and the first-order table
+        if not own:
+            # ---- default mode: dE, then the separate lookup's backward kernels (float atomics)
+            dE = torch.empty((n, De), dtype=torch.float32, device=dev)
+            ids = ctx.rows_bwd      # (None when the mode changed between the forward and here)
+            if ids is None:
+                ids = torch.where((rows >= 0) & (rows < N), rows, torch.full_like(rows, -1))
+            _lib.check(lib.mi_gather_fm_bwd_rows(emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb), dE.data_ptr(),
+                                                 g1vals.data_ptr(), _lib.ptr(gb), B, F, De, stream), "mi_gather_fm_bwd_rows")
+            if need_T1 or need_T2 or need_S:
+                if qr_rows:
+                    ws = _dual_rows_workspace(dev, De, n1)
+                    written = ws is not None and lib.mi_dual_gather_bwd_rows_overwrites(De, n1) != 0
+                    gT1 = torch.empty_like(T1c) if written else torch.zeros_like(T1c)
+                    g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
+                    rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
+                    _lib.check(lib.mi_dual_gather_bwd_rows(ids.data_ptr(), dE.data_ptr(), T1c.data_ptr(), T2c.data_ptr(),
+                                                           gT1.data_ptr(), g2vals.data_ptr(), rows2.data_ptr(), n, F, De, n1, n2,
+                                                           mod1, div2, op, _lib.ptr(ws), stream), "mi_dual_gather_bwd_rows")
+                    gT2 = _coo(rows2, g2vals, T2shape)
+                else:
+                    gT1, gT2 = torch.zeros_like(T1c), torch.zeros_like(T2c)
+                    gS1 = torch.zeros_like(S1c) if xform == XF_SOFT else None
+                    gS2 = torch.zeros_like(S2c) if xform == XF_SOFT else None
+                    small, row0, flags = ctx.fields[:3] if ctx.fields is not None else (None, None, None)
+                    _lib.check(
+                        lib.mi_dual_gather_bwd_fields(
+                            ids.data_ptr(), dE.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
+                            _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1), _lib.ptr(gS2),
+                            n, F, De, n1, n2, mod1, div2, op, xform, _lib.ptr(small),
+                            small.numel() if small is not None else 0, _lib.ptr(row0), _lib.ptr(flags), stream),
+                        "mi_dual_gather_bwd_fields",
+                    )
+                    gT1, gT2 = gT1.view(T1shape), gT2.view(T2shape)
+        else:
+            # ---- row values and keys, then fixed-order sums per table row: no float atomics
+            mask_vals = xform == XF_MASK and (sparse1 or sparse2)
+            c1 = torch.empty((n, De), dtype=torch.float32, device=dev)
+            c2 = torch.empty((n, De), dtype=torch.float32, device=dev) if (op == OPS["mult"] or mask_vals) else None
+            keys1 = torch.empty((n,), dtype=torch.int64, device=dev)
+            keys2 = torch.empty((n,), dtype=torch.int64, device=dev)
+            # sums taken in the order of the per-field sort (table 2, the first-order table): that sort moves an id outside
+            # its own field behind the field and the sums drop it, so the row kernel is told the fields, zeroes such a
+            # lookup for every table and gives every flagged lookup a table-2 key that keeps the sorted keys monotone
+            field_off = None
+            if DETERMINISTIC and (((need_T2 or need_S) and not sparse2) or (need_w1 and not sparse_w1)):
+                order = sort_field_rows(rows.view(-1), N)
+                field_off = ctx.offsets if order is not None else None
+            _lib.check(
+                lib.mi_gather_fm_dual_bwd_rows(
+                    rows.data_ptr(), _lib.ptr(field_off), emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb), T1c.data_ptr(), T2c.data_ptr(),
+                    _lib.ptr(M1c) if mask_vals else None, _lib.ptr(M2c) if mask_vals else None, c1.data_ptr(), _lib.ptr(c2),
+                    keys1.data_ptr(), keys2.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb), B, F, De, N, n1, n2, mod1, div2, op,
+                    stream),
+                "mi_gather_fm_dual_bwd_rows",
+            )
+            v2 = c1 if c2 is None else c2
+            A1 = A2 = None
+            if need_T1 or need_S:
+                if sparse1:
+                    gT1 = _coo(keys1, c1, T1shape)
+                elif DETERMINISTIC:
+                    ks, perm = torch.sort(keys1, stable=True)
+                    A1 = _sum_sorted(ks, perm, c1, n1, De)
+                else:
+                    A1 = _scatter_rows(keys1, c1, n1, De, stream)
+            if need_T2 or need_S:
+                if sparse2:
+                    gT2 = _coo(keys2, v2, T2shape)
+                elif DETERMINISTIC:
+                    if order is not None:
+                        # r2 is monotone in the row id: the per-field order of the rows is a stable order by r2, and the
+                        # keys the row kernel wrote are monotone through its permutation (field_off above): one gather
+                        perm = order[1]
+                        ks = keys2.index_select(0, perm)
+                    else:
+                        ks, perm = torch.sort(keys2, stable=True)
+                    A2 = _sum_sorted(ks, perm, v2, n2, De)
+                else:
+                    A2 = _scatter_rows(keys2, v2, n2, De, stream)
+            if xform != XF_NONE and (A1 is not None or A2 is not None):
+                gS1 = torch.empty_like(S1c) if (xform == XF_SOFT and A1 is not None) else None
+                gS2 = torch.empty_like(S2c) if (xform == XF_SOFT and A2 is not None) else None
+                _lib.check(lib.mi_gather_fm_dual_finish(_lib.ptr(A1), _lib.ptr(A2), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c),
+                                                        _lib.ptr(S2c), _lib.ptr(M1c), _lib.ptr(M2c), _lib.ptr(gS1), _lib.ptr(gS2),
+                                                        n1, n2, De, xform, stream), "mi_gather_fm_dual_finish")
+            if A1 is not None:
+                gT1 = A1.view(T1shape)
+            if A2 is not None:
+                gT2 = A2.view(T2shape)
+        gw1 = None
+        if need_w1:
+            if sparse_w1:
+                gw1 = _coo(rows, g1vals.view((-1,) + (1,) * (len(w1shape) - 1)), w1shape)
+            elif DETERMINISTIC and order is not None:
+                gw1 = _sum_sorted(order[0], order[1], g1vals, N, 1).view(w1shape)
+            else:
+                gw1 = _scatter_rows(rows, g1vals, N, 1, stream).view(w1shape)
+        return done(gT1 if need_T1 else None, gT2 if need_T2 else None, gw1, gb, gS1 if need_S else None,
+                    gS2 if need_S else None)
+
+
+def gather_fm_dual(idx, offsets, T1, T2, w1, bias, mod1, div2, op="add", S1=None, S2=None, M1=None, M2=None, sparse1=False,
+                   sparse2=False, sparse_w1=False, fields=None):
+    """(emb, y_fm) of DeepFM over a QR / CERP / CERP-retrain table in one launch; see GatherFMDual.  fields (optional):
+    small_field_hint(...), for the default mode's dense backward."""
+    emb, yfm, _rows = GatherFMDual.apply(idx, offsets, T1, T2, w1, bias, S1, S2, M1, M2, int(mod1), int(div2), OPS[op],
+                                         bool(sparse1), bool(sparse2), bool(sparse_w1), fields)
+    return emb, yfm
+
+
+class CerpPruneLoss(torch.autograd.Function):
+    """-sum tanh(K (soft(P, Sp) + soft(Q, Sq)))^2 over CERP's four [bucket, D] tables (mi_cerp_prune_loss_fwd / _bwd):
+    one launch each way, no [bucket, D] temporary, the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, P, Sp, Q, Sq, K: float):
+        dev = _lib.require_gpu(P, Sp, Q, Sq)
+        lib = _lib.load()
+        P, Sp, Q, Sq = _f32c(P), _f32c(Sp), _f32c(Q), _f32c(Sq)
+        if not (P.shape == Sp.shape == Q.shape == Sq.shape) or P.numel() == 0:
+            raise ValueError("cerp_prune_loss: the four tables must share one non-empty shape")
+        n = P.numel()
+        ws, armed = _losses._ticket_workspace("cerp_prune_loss", dev, lib.mi_cerp_prune_loss_workspace_elems(n))
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.check(lib.mi_cerp_prune_loss_fwd(P.data_ptr(), Sp.data_ptr(), Q.data_ptr(), Sq.data_ptr(), n, float(K),
+                                              ws.data_ptr(), int(armed), out.data_ptr(), _lib.stream_ptr(dev)),
+                   "mi_cerp_prune_loss_fwd")
+        ctx.save_for_backward(P, Sp, Q, Sq)
+        ctx.K = float(K)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        P, Sp, Q, Sq = ctx.saved_tensors
+        g = _f32c(g).view(1)
+        grads = [torch.empty_like(t) for t in (P, Sp, Q, Sq)]      # every element written by the kernel: no zero fill
+        _lib.check(_lib.load().mi_cerp_prune_loss_bwd(P.data_ptr(), Sp.data_ptr(), Q.data_ptr(), Sq.data_ptr(), P.numel(),
+                                                      ctx.K, g.data_ptr(), *(t.data_ptr() for t in grads),
+                                                      _lib.stream_ptr(P.device)), "mi_cerp_prune_loss_bwd")
+        return (*grads, None)
+
+
+def cerp_prune_loss(P, Sp, Q, Sq, K: float = 100) -> torch.Tensor:
+    return CerpPruneLoss.apply(P, Sp, Q, Sq, float(K))
 
 
 def csr_rows(values, crow, col, ids, D: int, N: int) -> torch.Tensor:

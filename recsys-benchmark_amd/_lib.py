@@ -40,6 +40,14 @@ SIGNATURES = {
     "mi_gather_fm_soft_bwd_workspace_elems": [_i64, _i32, _i64],
     "mi_gather_fm_soft_bwd_rows": [_p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p],
     "mi_gather_fm_elemmask_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_fm_dual_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64, _i64, _i64,
+                              _i64, _i32, _i32, _p, _p],
+    "mi_gather_fm_dual_bwd_rows": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _i64, _i64,
+                                   _i64, _i64, _i32, _p],
+    "mi_gather_fm_dual_finish": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p],
+    "mi_cerp_prune_loss_workspace_elems": [_i64],
+    "mi_cerp_prune_loss_fwd": [_p, _p, _p, _p, _i64, ctypes.c_float, _p, _i32, _p, _p],
+    "mi_cerp_prune_loss_bwd": [_p, _p, _p, _p, _i64, ctypes.c_float, _p, _p, _p, _p, _p, _p],
     "mi_soft_count_kept": [_p, _p, _i64, _i64, _i64, _i32, _p, _p],
     "mi_gather_rows_fwd": [_p, _p, _p, _i64, _i32, _i64, _p, _p],
     "mi_scatter_add_rows": [_p, _p, _p, _i64, _i32, _i64, _p],
@@ -228,7 +236,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_mag_prune_workspace_bytes": ctypes.c_int64, "mi_mag_csr_workspace_bytes": ctypes.c_int64,
              "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64,
              "mi_gather_fm_soft_bwd_workspace_elems": ctypes.c_int64, "mi_binary_auc_workspace_bytes": ctypes.c_int64,
-             "mi_ctr_metric_append_workspace_bytes": ctypes.c_int64}
+             "mi_ctr_metric_append_workspace_bytes": ctypes.c_int64,
+             "mi_cerp_prune_loss_workspace_elems": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

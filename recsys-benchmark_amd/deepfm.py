@@ -12,6 +12,7 @@ What runs where:
          mi_gather_fm_bwd_{rows,dense}  (vanilla table), or
          mi_gather_fm_masked_{fwd,bwd_rows,bwd_dense}      (OptEmbed: a search candidate in eval, the retraining table), or
          mi_gather_fm_{soft,elemmask}_{fwd,bwd_rows}       (PEP: the threshold search, the retraining table), or
+         mi_gather_fm_dual_{fwd,bwd_rows,finish}           (QR add / mult, CERP, CERP retrain), or
          IEmbedding.forward + mi_fm_fwd / mi_fm_bwd        (compressed tables)
   the MLP tail (a real GEMM): the library's own fp32-MFMA products with BatchNorm1d / ReLU / Dropout in
       their operand loads and epilogues (tail.py, csrc/tail.hip) in training, eval() and no-BatchNorm stacks alike; the
@@ -26,7 +27,9 @@ from torch import nn
 from . import _kernels
 from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
+from .embeddings.cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
 from .embeddings.pep_embedding import PepEmbeeding, RetrainPepEmbedding
+from .embeddings.qr_embedding import QRHashingEmbedding
 from .mlp import field_offsets, hidden_stack, run_tail
 
 
@@ -129,6 +132,12 @@ class DeepFM(nn.Module):
         if xform is not None:
             return _kernels.gather_fm(x, self.offsets, xform.pop("W"), self.fc.weight, self._bias,
                                       sparse_w1=bool(self.fc.sparse), **xform)
+        # QR / CERP / CERP retrain: the two row gathers, their transform and the combine inside the same launch
+        # (mi_gather_fm_dual_*); "cat", bag modes and CPU tables keep the path below
+        dual = emb_mod.fm_dual() if isinstance(emb_mod, (QRHashingEmbedding, CerpEmbedding, RetrainCerpEmbedding)) else None
+        if dual is not None:
+            return _kernels.gather_fm_dual(x, self.offsets, w1=self.fc.weight, bias=self._bias,
+                                           sparse_w1=bool(self.fc.sparse), **dual)
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

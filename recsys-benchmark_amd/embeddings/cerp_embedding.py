@@ -105,6 +105,19 @@ class CerpEmbedding(IEmbedding):
         # over the summed rows in the reference as well (cerp_embedding.py:160-175)
         return _kernels.bag_reduce(emb, self._mode)
 
+    def fm_dual(self):
+        """The operands of DeepFM's fused lookup + FM launch (_kernels.gather_fm_dual), or None when this table keeps
+        the separate lookup: a bag mode, CPU or non-fp32 tables, a width past the kernels' limit."""
+        if (self._mode is not None or not self.p_weight.is_cuda or self.p_weight.dtype != torch.float32
+                or self._hidden_size > _kernels.DUAL_FM_MAX_D):
+            return None
+        return dict(T1=self.p_weight, T2=self.q_weight, mod1=self._bucket_size, div2=self.q_entity_per_row, op="add",
+                    S1=self.p_threshold, S2=self.q_threshold)
+
+    def _on_kernels(self) -> bool:
+        tables = (self.p_weight, self.q_weight, self.p_threshold, self.q_threshold)
+        return all(t.is_cuda and t.dtype == torch.float32 and t.shape == self.p_weight.shape for t in tables)
+
     def get_sparsity(self, get_n_params=False):
         total_params = self._num_item * self._hidden_size
         n_params = self.get_num_params()
@@ -123,6 +136,12 @@ class CerpEmbedding(IEmbedding):
         return self(all_idxes)
 
     def get_num_params(self):
+        if self._on_kernels():      # two counting passes over the raw tables (no pruned copies), one host read
+            counts = torch.empty(2, dtype=torch.int64, device=self.p_weight.device)
+            with torch.no_grad():
+                _kernels.soft_count_kept(self.p_weight, self.p_threshold, out=counts[0:1])
+                _kernels.soft_count_kept(self.q_weight, self.q_threshold, out=counts[1:2])
+            return sum(counts.tolist())
         self.apply_pruning()
         n_params = 0
         for w in [self.sparse_p_weight, self.sparse_q_weight]:
@@ -133,6 +152,8 @@ class CerpEmbedding(IEmbedding):
         # same value as the reference's (cerp_embedding.py get_prune_loss); the pruned tables are NOT stashed on the module
         # here: a tensor with autograd history that outlives a hipGraph capture on a module attribute crashes torch's
         # capture_end, and this loss is part of the captured training step (trainer.train_epoch_cerp)
+        if self._on_kernels():      # one launch each way over the four tables (mi_cerp_prune_loss_*), no [bucket, D] temporary
+            return _kernels.cerp_prune_loss(self.p_weight, self.p_threshold, self.q_weight, self.q_threshold, K)
         q, p = self._pruned_tables()
         return -torch.tanh((p + q) * K).norm(2) ** 2
 
@@ -222,6 +243,15 @@ class RetrainCerpEmbedding(IEmbedding):
                 op="add", M1=self.p_mask, M2=self.q_mask,
             )
         return _kernels.bag_reduce(emb, self._mode)
+
+    def fm_dual(self):
+        """The operands of DeepFM's fused lookup + FM launch (_kernels.gather_fm_dual), or None when this table keeps
+        the separate lookup: a bag mode, CPU or non-fp32 tables, a width past the kernels' limit."""
+        if (self._mode is not None or not self.p_weight.is_cuda or self.p_weight.dtype != torch.float32
+                or self._hidden_size > _kernels.DUAL_FM_MAX_D):
+            return None
+        return dict(T1=self.p_weight, T2=self.q_weight, mod1=self._bucket_size, div2=self.q_entity_per_row, op="add",
+                    M1=self.p_mask, M2=self.q_mask, sparse1=self._sparse, sparse2=self._sparse)
 
     def get_num_params(self):
         return (torch.count_nonzero(self.q_mask) + torch.count_nonzero(self.p_mask)).item()

@@ -102,6 +102,25 @@ class QRHashingEmbedding(IEmbedding):
             return bag1 * bag2
         return bag1 + bag2 if self._operation == "add" else torch.cat([bag1, bag2], dim=1)
 
+    def _field_hint(self, device):
+        if self._field_dims is None:
+            return None
+        if self._hint is None or self._hint[0] != device:
+            self._hint = (device, _kernels.small_field_hint(self._field_dims, self._divider, device))
+        return self._hint[1]
+
+    def fm_dual(self):
+        """The operands of DeepFM's fused lookup + FM launch (_kernels.gather_fm_dual), or None when this table keeps
+        the separate lookup: a bag mode, "cat" (it changes the field count), CPU or non-fp32 tables, a width past the
+        kernels' limit."""
+        w1, w2 = self._tables()
+        if (self._mode is not None or self._operation == "cat" or not w1.is_cuda or w1.dtype != torch.float32
+                or w1.shape[1] > _kernels.DUAL_FM_MAX_D):
+            return None
+        d = self._divider
+        return dict(T1=w1, T2=w2, mod1=d, div2=d, op=self._operation, sparse2=self._sparse2,
+                    fields=self._field_hint(w1.device))
+
     def takes_offsets(self, tensor: torch.Tensor) -> bool:
         """Whether forward(tensor, offsets=...) folds the addition into the lookup kernel (float4 rows, [B, F] ids on the GPU)."""
         De = self.emb1.weight.shape[1]
