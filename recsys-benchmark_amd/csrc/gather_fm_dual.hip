@@ -10,6 +10,9 @@
 // rows, and their threshold logits or mask bytes, need only the row id: all of a step's loads (up to 4 NIT float4 per
 // lane for the soft form) are issued before the first use.  HBM / L2 latency-bound copy work: no LDS.  The element
 // transforms are dual_xform.hpp's, so emb has the bits of mi_dual_gather_fwd.
+// What the two files share lives in gather_fm_walk.hpp: the float4 helpers, the bias-gradient workgroup, fm_grad_row
+// and the (LPR, NIT) dispatch.  The forward walks below stay bodies of their own: run by a shared float4 walk, y_fm
+// moved in the last bit (see the header).
 //
 // Backward: no float atomics anywhere in this file.  The row kernel writes one value row per lookup and table
 // (c1, c2) and the table-row keys (r1, r2); the caller sums the rows per key in a fixed order (mi_coalesce_rows_sorted)
@@ -17,6 +20,7 @@
 // k_dual_finish applies it once per table element after the sum.
 #include "common.hpp"
 #include "dual_xform.hpp"
+#include "gather_fm_walk.hpp"
 
 namespace {
 using namespace mi;
@@ -49,17 +53,6 @@ __device__ __forceinline__ bool split_row(int64_t row, int64_t N, const DualFm &
 }
 
 __device__ __forceinline__ float4 combine(int op, float4 a, float4 b) { return op == OP_MULT ? mul4(a, b) : add4(a, b); }
-
-__device__ __forceinline__ float4 apply4(float4 w, float4 s) {
-  return make_float4(soft_(w.x, s.x), soft_(w.y, s.y), soft_(w.z, s.z), soft_(w.w, s.w));
-}
-__device__ __forceinline__ uint32_t bytes4(const uint8_t *__restrict__ M, int64_t o) {
-  return *reinterpret_cast<const uint32_t *>(M + o);
-}
-__device__ __forceinline__ float4 keep4(float4 v, uint32_t m) {
-  return make_float4((m & 0xffu) ? v.x : 0.f, (m & 0xff00u) ? v.y : 0.f, (m & 0xff0000u) ? v.z : 0.f,
-                     (m & 0xff000000u) ? v.w : 0.f);
-}
 
 // ---------------------------------------------------------------- forward ----
 // rows_bwd (nullable, [B, F]): the row again where the lookup was served and -1 where it was flagged — the ids a backward
@@ -116,8 +109,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_fwd(
           tc[k] = ok[k] ? ld4(t.S2 + o2) : z;
         }
         if constexpr (XF == XF_MASK) {
-          ma[k] = ok[k] ? bytes4(t.M1, o1) : 0u;
-          mc[k] = ok[k] ? bytes4(t.M2, o2) : 0u;
+          ma[k] = ok[k] ? mask4(t.M1, o1) : 0u;
+          mc[k] = ok[k] ? mask4(t.M2, o2) : 0u;
         }
       }
 #pragma unroll
@@ -125,13 +118,13 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_fwd(
         const int f = r + k * RS;
         if constexpr (XF == XF_SOFT) {
           if (ok[k]) {      // (a flagged lookup is +0 whatever soft_(0, 0) would give)
-            a[k] = apply4(a[k], ta[k]);
-            c[k] = apply4(c[k], tc[k]);
+            a[k] = soft4(a[k], ta[k]);
+            c[k] = soft4(c[k], tc[k]);
           }
         }
         if constexpr (XF == XF_MASK) {
-          a[k] = keep4(a[k], ma[k]);
-          c[k] = keep4(c[k], mc[k]);
+          a[k] = keep_bytes(a[k], ma[k]);
+          c[k] = keep_bytes(c[k], mc[k]);
         }
         const float4 v = ok[k] ? combine(t.op, a[k], c[k]) : z;
         if (act[k]) st4_nt(emb + (base + f) * D + q * 4, v);
@@ -218,28 +211,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_fwd_anyD(
 }
 
 // ----------------------------------------------------- backward, row form ----
-// sum_b g_y[b] in a fixed order by ONE extra workgroup (workgroup 0) of the launch: no atomics, no launch of its own
-__device__ __forceinline__ bool bias_grad_workgroup(const float *__restrict__ g_y, int64_t B, float *__restrict__ gbias, int &blk,
-                                                    int &nblk) {
-  blk = blockIdx.x;
-  nblk = gridDim.x;
-  if (!gbias) return false;
-  nblk = gridDim.x - 1;
-  blk = (int)blockIdx.x - 1;
-  if (blockIdx.x != 0) return false;
-  __shared__ float part[kWavesPerBlock];
-  float s = 0.f;
-  for (int64_t b = threadIdx.x; b < B; b += kBlock) s += g_y[b];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tt = 0.f;
-    for (int j = 0; j < kWavesPerBlock; ++j) tt += part[j];
-    gbias[0] = tt;
-  }
-  return true;
-}
+// (the bias gradient: bias_grad_block, gather_fm_walk.hpp — ONE extra workgroup of the launch)
 
 // What the row kernels write for lookup i = b F + f (dE = g_emb + g_y (S_b - e), S_b = sum_f e[b, f, :]):
 //   keys1[i] = r1, keys2[i] = r2 (0 for a lookup the forward flagged; its value rows are zeros)
@@ -281,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_bwd_rows(
   constexpr int RS = kWave / LPR;
   constexpr int D = LPR * 4;
   int blk, nblk;
-  if (bias_grad_workgroup(g_y, B, gbias, blk, nblk)) return;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   const int lane = threadIdx.x & 63;
   const int q = lane % LPR, r = lane / LPR;
   const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
@@ -298,8 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_bwd_rows(
       int64_t r1, r2;
       const bool ok = lookup_keys(o, t, f, F, N, rows[i], r1, r2);
       const float4 e = ld4(emb + eo), ge = g_emb ? ld4(g_emb + eo) : z;
-      const float4 dE = make_float4(ge.x + gy * (S.x - e.x), ge.y + gy * (S.y - e.y), ge.z + gy * (S.z - e.z),
-                                    ge.w + gy * (S.w - e.w));
+      const float4 dE = fm_grad_row(ge, gy, S, e);
       float4 c1 = z, c2 = z;
       if (ok) {
         const int64_t o1 = r1 * D + q * 4, o2 = r2 * D + q * 4;
@@ -307,8 +278,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_bwd_rows(
           c1 = mul4(dE, ld4(t.T2 + o2));
           c2 = mul4(dE, ld4(t.T1 + o1));
         } else if (o.mask_vals) {
-          c1 = keep4(dE, bytes4(t.M1, o1));
-          c2 = keep4(dE, bytes4(t.M2, o2));
+          c1 = keep_bytes(dE, mask4(t.M1, o1));
+          c2 = keep_bytes(dE, mask4(t.M2, o2));
         } else {
           c1 = c2 = dE;
         }
@@ -328,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_fm_dual_bwd_rows_anyD(
     const int64_t *__restrict__ rows, const float *__restrict__ emb, const float *__restrict__ g_y,
     const float *__restrict__ g_emb, DualFm t, DualRowsOut o, int64_t B, int F, int D, int64_t N, float *__restrict__ gbias) {
   int blk, nblk;
-  if (bias_grad_workgroup(g_y, B, gbias, blk, nblk)) return;
+  if (bias_grad_block(g_y, B, gbias, blk, nblk)) return;
   const int lane = threadIdx.x & 63;
   const int64_t wave0 = (int64_t)blk * kWavesPerBlock + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)nblk * kWavesPerBlock;
@@ -476,12 +447,6 @@ __global__ __launch_bounds__(kBlock) void k_cerp_prune_loss_bwd(PruneTables a, c
   }
 }
 
-// ------------------------------------------------------------- dispatch ------
-inline int nit_for(int F, int LPR) {      // unrolled steps that cover F rows, 0 = the generic loop (also every F > 64)
-  const int RS = kWave / LPR;
-  const int n = (F + RS - 1) / RS;
-  return (F <= kWave && n <= 4) ? n : 0;
-}
 
 // the (op, xform) pairs the models produce: (mult, none) and (add, none) QR, (add, soft) CERP, (add, mask) CERP retrain
 inline bool served(int op, int xform) {
@@ -503,25 +468,6 @@ inline bool tables_float4_ok(const DualFm &t, int xform) {
          (xform != XF_MASK || ((((uintptr_t)t.M1 | (uintptr_t)t.M2) & 3) == 0));
 }
 
-#define MI_DUAL_NIT(LPR, nit, XF, CALL) \
-  switch (nit) {                        \
-    case 1: CALL(LPR, 1, XF); break;    \
-    case 2: CALL(LPR, 2, XF); break;    \
-    case 3: CALL(LPR, 3, XF); break;    \
-    case 4: CALL(LPR, 4, XF); break;    \
-    default: CALL(LPR, 0, XF); break;   \
-  }
-#define MI_DUAL_LPR_NIT(lpr, nit, XF, CALL)              \
-  switch (lpr) {                                         \
-    case 1: MI_DUAL_NIT(1, nit, XF, CALL); break;        \
-    case 2: MI_DUAL_NIT(2, nit, XF, CALL); break;        \
-    case 4: MI_DUAL_NIT(4, nit, XF, CALL); break;        \
-    case 8: MI_DUAL_NIT(8, nit, XF, CALL); break;        \
-    case 16: MI_DUAL_NIT(16, nit, XF, CALL); break;      \
-    case 32: MI_DUAL_NIT(32, nit, XF, CALL); break;      \
-    case 64: MI_DUAL_NIT(64, nit, XF, CALL); break;      \
-    default: return MI_ERR_UNSUPPORTED;                  \
-  }
 
 inline int grid_for_elems(int64_t n) {
   int64_t g = (n + kBlock - 1) / kBlock;
@@ -549,14 +495,16 @@ int mi_gather_fm_dual_fwd(const int64_t *idx, const int64_t *offsets, const floa
   if (!idx || !w1 || !emb_out || !yfm_out) return MI_ERR_INVALID_ARG;
   const int grid = grid_for_waves(B);
   if (vec_ok(De) && tables_float4_ok(t, xform) && aligned16(emb_out)) {
-    const int lpr = De / 4, nit = nit_for(F, lpr);
-#define CALL(LPR, NIT, XF)                                                                                          \
-  MI_LAUNCH("gather_fm_dual_fwd", (k_gather_fm_dual_fwd<LPR, NIT, XF>), grid, kBlock, stream, idx, offsets, t, w1, ldw1, bias, \
-            emb_out, yfm_out, rows_out, rows_bwd, B, F, N, err)
-    if (xform == XF_NONE) { MI_DUAL_LPR_NIT(lpr, nit, XF_NONE, CALL) }
-    else if (xform == XF_SOFT) { MI_DUAL_LPR_NIT(lpr, nit, XF_SOFT, CALL) }
-    else { MI_DUAL_LPR_NIT(lpr, nit, XF_MASK, CALL) }
+    const int lpr = De / 4, nit = F <= kWave ? nit_for(F, lpr) : 0;      // (unrolled only in shuffle form)
+    decltype(&k_gather_fm_dual_fwd<1, 0, XF_NONE>) kernel = nullptr;
+#define CALL(LPR, NIT)                                                     \
+  kernel = xform == XF_NONE   ? k_gather_fm_dual_fwd<LPR, NIT, XF_NONE>   \
+           : xform == XF_SOFT ? k_gather_fm_dual_fwd<LPR, NIT, XF_SOFT>   \
+                              : k_gather_fm_dual_fwd<LPR, NIT, XF_MASK>
+    MI_DISPATCH_LPR_NIT(lpr, nit, CALL)
 #undef CALL
+    MI_LAUNCH("gather_fm_dual_fwd", kernel, grid, kBlock, stream, idx, offsets, t, w1, ldw1, bias, emb_out, yfm_out,
+              rows_out, rows_bwd, B, F, N, err);
   } else {
     MI_LAUNCH("gather_fm_dual_fwd", k_gather_fm_dual_fwd_anyD, grid, kBlock, stream, idx, offsets, t, xform, w1, ldw1, bias,
               emb_out, yfm_out, rows_out, rows_bwd, B, F, De, N, err);

@@ -271,6 +271,24 @@ def test_cerp_gather_fm_dual_against_the_lookup_and_float64(F, D, B, kind, geo):
     _check_case(c)
 
 
+def test_bias_gradient_at_a_batch_that_runs_every_loop_of_its_workgroup():
+    """The row backward's bias workgroup (bias_grad_block, csrc/gather_fm_walk.hpp: 256 threads, float4 loads) has three
+    loops, and BATCHES stops at 1030, below the first.  B = 5123 = 4*256*4 + 256*4 + 3: one trip of the four-deep loop, one
+    of the single float4 loop, and a scalar tail of 3."""
+    c = _case(3, 4, 5123, "add", None)
+    pkg.use_deterministic_algorithms(True)
+    try:
+        r = _run(c)
+        _grads_equal(r, _run(c))
+    finally:
+        pkg.use_deterministic_algorithms(False)
+    _lib.check_index_errors()
+    gy = c["gy"].double()
+    assert_within_terms(r["gb"], gy.sum().view(1), gy.abs().sum().view(1), 8, "bias gradient at B = 5123")
+    _dense_checks(c, r, _reference64(c, r["emb"]), "deterministic, B = 5123")
+    _first_order_checks(c, r, False)
+
+
 @pytest.mark.parametrize("kind,geo", [("mult", 3), ("add", None), ("soft", 7), ("mask", 7)])
 def test_one_forward_launch_and_no_atomic_kernel_in_deterministic_mode(kind, geo):
     c = _case(26, 16, 37, kind, geo)
