@@ -38,14 +38,32 @@ __global__ __launch_bounds__(kBlock) void k_tail_dropmask(MaskJob j, const int64
 }
 
 // The consumers' accumulators as a [64][kTilePitch] tile in LDS: lane (r, g) of wave w holds rows 16 w + r, columns
-// 16 s + 4 g .. + 3 of sub-tile s.
+// 16 s + 4 g .. + 3 of full sub-tile s; of the four-column group (columns 16 nfull .. + 3, tail_gemm.hpp's exact cover) it
+// holds the partial sum over k-class g: the four classes are added across g (fixed order: deterministic) and one lane
+// group writes the float4.  Columns beyond the cover (>= cols_valid then) are NOT written: every epilogue guards its reads
+// of the tile with c < cols_valid.
 constexpr int kTilePitch = BNT + 4;
-__device__ __forceinline__ void acc_to_lds(const floatx4 (&acc)[NSUB], float *T, int wave, int lane) {
+__device__ __forceinline__ void acc_to_lds(const floatx4 (&acc)[NSUB], const floatx4 (&accg)[NGRP], Cover cv, float *T, int wave,
+                                           int lane) {
   if (wave < 4) {
     const int r = lane & 15, g = lane >> 4;
-    float *row = T + (wave * 16 + r) * kTilePitch + 4 * g;
+    float *row = T + (wave * 16 + r) * kTilePitch;
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s) st4(row + 16 * s, make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]));
+    for (int s = 0; s < NSUB; ++s)
+      if (s < cv.nfull) st4(row + 16 * s + 4 * g, make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]));
+#pragma unroll
+    for (int q = 0; q < NGRP; ++q) {
+      if (q < cv.rem) {
+        float v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          v[c] = accg[q][c];
+          v[c] += __shfl_xor(v[c], 16);
+          v[c] += __shfl_xor(v[c], 32);
+        }
+        if (g == q) st4(row + 16 * cv.nfull + 4 * q, make_float4(v[0], v[1], v[2], v[3]));
+      }
+    }
   }
 }
 
@@ -359,9 +377,14 @@ __global__ __launch_bounds__(kThreads) void k_tail_fwd(FwdArgs a) {
   const int m0 = mt * BM, n0 = nt * a.ncols;
   const int rows_valid = min(BM, a.M - m0), cols_valid = min(a.ncols, a.N - n0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  floatx4 acc[NSUB];
+  floatx4 acc[NSUB], accg[NGRP];
 #pragma unroll
   for (int s = 0; s < NSUB; ++s) acc[s] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q) accg[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+  // the exact column cover for the 112-column form on the register-staged loop; the small-batch form and the LDS-DMA loop
+  // keep all their sub-tiles
+  Cover cv{NSUB, 0};
 
   const LoadAct act = make_act(a.x);
   const LoadPlain xp{a.x.Z, a.x.ld};
@@ -372,21 +395,25 @@ __global__ __launch_bounds__(kThreads) void k_tail_fwd(FwdArgs a) {
     const LoadActL actl{a.x.Z, a.x.ld, c, c + kCstPitch, c + 2 * kCstPitch, act.drop};
     float *cst = lds + kLdsFloats;
     const bool writer = tile == 0;
-    main_loop<true, true>(acc, lds, 0, a.K, KcOperand<64, Tee<LoadActL>>{Tee<LoadActL>{actl, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K}, opC,
-                          make_pre([&]() { bn_merge_fwd<kThreads - kProd>(a.bn, a.M, a.K, cst, writer, (int)threadIdx.x); }));
+    cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.K, KcOperand<64, Tee<LoadActL>>{Tee<LoadActL>{actl, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K}, opC,
+                    make_pre([&]() { bn_merge_fwd<kThreads - kProd>(a.bn, a.M, a.K, cst, writer, (int)threadIdx.x); }));
   } else if constexpr (DMA && ACT)      // the weights by LDS-DMA (two loader waves), the activation through two producer waves
     main_loop_dma(acc, lds, 0, a.K, KcOperand<64, Tee<LoadAct>, 128>{Tee<LoadAct>{act, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K},
                   a.W, a.ldw, n0, cols_valid);
   else if constexpr (DMA)
     main_loop_dma(acc, lds, 0, a.K, KcOperand<64, LoadPlain, 128>{xp, m0, rows_valid, a.K}, a.W, a.ldw, n0, cols_valid);
-  else if constexpr (ACT)
-    main_loop<true, true, NS>(acc, lds, 0, a.K, KcOperand<64, Tee<LoadAct>>{Tee<LoadAct>{act, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K}, opC);
-  else main_loop<true, true, NS>(acc, lds, 0, a.K, KcOperand<64, LoadPlain>{xp, m0, rows_valid, a.K}, opC);
+  else if constexpr (NS != NSUB) {
+    if constexpr (ACT)
+      main_loop<true, true, NS>(acc, lds, 0, a.K, KcOperand<64, Tee<LoadAct>>{Tee<LoadAct>{act, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K}, opC);
+    else main_loop<true, true, NS>(acc, lds, 0, a.K, KcOperand<64, LoadPlain>{xp, m0, rows_valid, a.K}, opC);
+  } else if constexpr (ACT)
+    cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.K, KcOperand<64, Tee<LoadAct>>{Tee<LoadAct>{act, nt == 0 ? a.a_out : nullptr, a.x.ld}, m0, rows_valid, a.K}, opC);
+  else cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.K, KcOperand<64, LoadPlain>{xp, m0, rows_valid, a.K}, opC);
 
   // ---- epilogue.  A lane holds z[m0 + 16 wave + r][n0 + 16 s + 4 g + v] (waves 0-3); the tile goes through LDS once so
   // that ALL 8 waves store whole 448-byte row segments and the column statistics are plain column walks.
   float *T = lds;                                        // [64][kTilePitch]
-  acc_to_lds(acc, T, wave, lane);
+  acc_to_lds(acc, accg, cv, T, wave, lane);
   __syncthreads();
   const int t = threadIdx.x;
   if (a.head_w) {      // thread (row = t / 8, part = t % 8): float4 chunks part, part + 8, part + 16, part + 24 of the row's tile
@@ -1034,9 +1061,12 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
   const int m0 = mt * BM, k0 = nt * a.ncols;
   const int rows_valid = min(BM, a.M - m0), cols_valid = min(a.ncols, a.K - k0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  floatx4 acc[NSUB];
+  floatx4 acc[NSUB], accg[NGRP];
 #pragma unroll
   for (int s = 0; s < NSUB; ++s) acc[s] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q) accg[q] = floatx4{0.f, 0.f, 0.f, 0.f};
+  Cover cv{NSUB, 0};
 
   const LoadDz dzl = make_dz(a.dz);
   const LoadPlain dyp{a.dz.DY, a.dz.ld};
@@ -1047,15 +1077,15 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
     const LoadDzL dzm{a.dz.DY, a.dz.Z, a.dz.ld, c, c + kCstPitch, c + 2 * kCstPitch, c + 3 * kCstPitch};
     float *cst = lds + kLdsFloats;
     const bool writer = tile == 0, wwriter = tile == min(1, mt_total * a.ntn - 1);
-    main_loop<true, true>(acc, lds, 0, a.N, KcOperand<64, Tee<LoadDzL>>{Tee<LoadDzL>{dzm, nt == 0 ? a.dz_out : nullptr, a.dz.ld}, m0, rows_valid, a.N}, opC,
-                          make_pre([&]() { bn_merge_bwd<kThreads - kProd>(a.bn, a.M, a.N, cst, writer, wwriter, (int)threadIdx.x); }));
+    cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.N, KcOperand<64, Tee<LoadDzL>>{Tee<LoadDzL>{dzm, nt == 0 ? a.dz_out : nullptr, a.dz.ld}, m0, rows_valid, a.N}, opC,
+                    make_pre([&]() { bn_merge_bwd<kThreads - kProd>(a.bn, a.M, a.N, cst, writer, wwriter, (int)threadIdx.x); }));
   } else if constexpr (DZ)
-    main_loop<true, true>(acc, lds, 0, a.N, KcOperand<64, Tee<LoadDz>>{Tee<LoadDz>{dzl, nt == 0 ? a.dz_out : nullptr, a.dz.ld}, m0, rows_valid, a.N}, opC);
-  else main_loop<true, true>(acc, lds, 0, a.N, KcOperand<64, LoadPlain>{dyp, m0, rows_valid, a.N}, opC);
+    cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.N, KcOperand<64, Tee<LoadDz>>{Tee<LoadDz>{dzl, nt == 0 ? a.dz_out : nullptr, a.dz.ld}, m0, rows_valid, a.N}, opC);
+  else cv = main_loop_cover(acc, accg, cols_valid, lds, 0, a.N, KcOperand<64, LoadPlain>{dyp, m0, rows_valid, a.N}, opC);
 
   // ---- epilogue through LDS (see k_tail_fwd): all 8 waves, whole row segments
   float *T = lds;
-  acc_to_lds(acc, T, wave, lane);
+  acc_to_lds(acc, accg, cv, T, wave, lane);
   __syncthreads();
   const int t = threadIdx.x;
   if constexpr (FM) {

@@ -6,8 +6,11 @@
 //
 // Shape-driven tiling.  The tail's products are M = 4096 by N,K in {400, 416}: 64 x 64 tiles give 448 workgroups = 1.75
 // waves over the 256 CUs (what the library GEMM and round 1's generic kernel pay for).  Here a workgroup owns 64 rows of
-// R (4 row blocks of 16) by ONE QUARTER of the columns (100 or 104, computed as 7 sub-tiles of 16 with the surplus
-// masked): exactly 64 x 4 = 256 workgroups, one per CU; 8 waves, two per SIMD, 28 accumulator registers per lane.
+// R (4 row blocks of 16) by ONE QUARTER of the columns (100 or 104): exactly 64 x 4 = 256 workgroups, one per CU; 8 waves,
+// two per SIMD.  104 columns are 7 sub-tiles of 16 with the surplus masked (28 accumulator registers per lane); 100 columns
+// are covered EXACTLY, 6 sub-tiles on v_mfma_f32_16x16x4_f32 plus one group of 4 on v_mfma_f32_4x4x1_16b_f32 (see "EXACT
+// COLUMN COVER" below).  The all-zero upper half of the partial reduction slice (400 = 12 x 32 + 16) costs the consumers
+// no fragment reads and no MFMAs.
 //
 // MFMA roles are swapped (A := Cc fragment, B := R fragment) so that a lane ends up with 4 CONSECUTIVE columns of one
 // output row: the epilogue stores float4 and the column reductions (BatchNorm statistics, dgamma / dbeta) are 16-lane
@@ -620,23 +623,66 @@ __device__ __forceinline__ float4 oc_frag(const float *T, int col, int h, int g)
   return make_float4(p[0], p[S], p[2 * S], p[3 * S]);
 }
 
-// Fragment registers of one half-slice (16 reduction indices) for a consumer wave: its 16 rows of R and the 7 sub-tiles
-// of Cc.
-// NS <= NSUB: the sub-tiles a kernel actually needs (a 64-column range needs 4 of the 7: the others would be MFMAs on
+// Fragment registers of one half-slice (16 reduction indices) for a consumer wave: its 16 rows of R, NF full sub-tiles of
+// Cc and NG (0 or 1) four-column groups (the exact column cover, below).
+// NF <= NSUB: the sub-tiles a kernel actually needs (a 64-column range needs 4 of the 7: the others would be MFMAs on
 // columns that are masked anyway).
-template <int NS>
+constexpr int NGRP = 1;           // four-column groups per tile (see cover_of)
+template <int NF, int NG = 0>
 struct Frags {
-  float4 b, a[NS];
+  float4 b, a[NF > 0 ? NF : 1], q[NG > 0 ? NG : 1];
 };
-template <bool R_KC, bool C_KC, int NS>
-__device__ __forceinline__ void read_frags(Frags<NS> &f, const float *Rt, const float *Ct, int wave, int lane, int h) {
+template <bool R_KC, bool C_KC, int NF, int NG = 0>
+__device__ __forceinline__ void read_frags(Frags<NF, NG> &f, const float *Rt, const float *Ct, int wave, int lane, int h) {
+  static_assert(NG == 0 || C_KC, "four-column groups read KC tiles");
   const int r = lane & 15, g = lane >> 4;
   f.b = R_KC ? kc_frag(Rt, wave * 16 + r, h, g) : oc_frag<SR_OC>(Rt, wave * 16 + r, h, g);
 #pragma unroll
-  for (int s = 0; s < NS; ++s) f.a[s] = C_KC ? kc_frag(Ct, s * 16 + r, h, g) : oc_frag<SC_OC>(Ct, s * 16 + r, h, g);
+  for (int s = 0; s < NF; ++s) f.a[s] = C_KC ? kc_frag(Ct, s * 16 + r, h, g) : oc_frag<SC_OC>(Ct, s * 16 + r, h, g);
+#pragma unroll
+  for (int q = 0; q < NG; ++q) f.q[q] = kc_frag(Ct, NF * 16 + 4 * q + (lane & 3), h, g);      // 16 distinct addresses: broadcast
 }
-// 4 NS MFMAs, j-major: consecutive ones hit different accumulators (a dependent v_mfma_f32_16x16x4_f32 needs 40 cycles, an
+// EXACT COLUMN COVER.  A column tile of cols_valid = 16 nfull + 4 columns (the headline's 100) used to pay a whole seventh
+// sub-tile — a 32-cycle v_mfma_f32_16x16x4_f32 per k-step — for 4 valid columns.  v_mfma_f32_4x4x1_16b_f32 computes 16
+// independent 4x4x1 blocks; tools/probe_mfma.hip measured 8.4 cycles back to back on independent accumulators, 9.4 on one,
+// and checked the lane maps element by element (profiles/tail_cover_mfma_probe.txt).  With A := 4 columns, B := 4 rows,
+// block b = lane / 4 is row group b % 4 and k-class b / 4: lane (r, g) supplies row r and reduction index 16h + 4g + j
+// exactly as for the 16x16x4 form, so the R fragment is shared and the C fragment of the group is the b128 of row
+// base + (lane & 3).  Four instructions (j = 0..3) cover a half slice for 16 rows x 4 columns; lane (r, g) ends up with
+// row r, the group's 4 columns and the partial sum over k-class g (summed across g in the epilogue).
+// ONE group only.  The probe's consumer-only streams per half slice: 28 full 896 cycles, 24 + 4 groups 833, 24 + 8 848,
+// 24 + 12 876 — the gain shrinks with every further group.  A build that also ran left-overs of 8 and 12 columns as two and
+// three groups (21 loop instances, 188 VGPRs in every product kernel) measured 0.2249 ms per step where this one measures
+// 0.2219 (parent 0.2260, profiles/tail_cover_ab.txt); the cause was not isolated, so such tiles (the 104-column product)
+// keep the full sub-tile.
+template <int J>
+__device__ __forceinline__ float comp(const float4 &v) {
+  if constexpr (J == 0) return v.x;
+  else if constexpr (J == 1) return v.y;
+  else if constexpr (J == 2) return v.z;
+  else return v.w;
+}
+template <int J, int NF, int NG>
+__device__ __forceinline__ void mma_step(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], const Frags<NF, NG> &f) {
+#pragma unroll
+  for (int s = 0; s < NF; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(comp<J>(f.a[s]), comp<J>(f.b), acc[s], 0, 0, 0);
+  if constexpr (NG > 0) {
+    // the group goes BEHIND the full sub-tiles of its k-step (a dependent 4x4x1 then has NF MFMAs between itself and its
+    // predecessor); without the fence hipcc chains a half slice's four group instructions at its end, s_nop between them
+#pragma unroll
+    for (int q = 0; q < NG; ++q) accg[q] = __builtin_amdgcn_mfma_f32_4x4x1f32(comp<J>(f.q[q]), comp<J>(f.b), accg[q], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// 4 (NF + NG) MFMAs, j-major: consecutive ones hit different accumulators (a dependent v_mfma_f32_16x16x4_f32 needs 40 cycles, an
 // independent one issues every 32).
+template <int NF, int NG>
+__device__ __forceinline__ void mma_half(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], const Frags<NF, NG> &f) {
+  mma_step<0>(acc, accg, f);
+  mma_step<1>(acc, accg, f);
+  mma_step<2>(acc, accg, f);
+  mma_step<3>(acc, accg, f);
+}
 template <int NS>
 __device__ __forceinline__ void mma_half(floatx4 (&acc)[NSUB], const Frags<NS> &f) {
 #pragma unroll
@@ -647,6 +693,15 @@ __device__ __forceinline__ void mma_half(floatx4 (&acc)[NSUB], const Frags<NS> &
   for (int s = 0; s < NS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[s].z, f.b.z, acc[s], 0, 0, 0);
 #pragma unroll
   for (int s = 0; s < NS; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[s].w, f.b.w, acc[s], 0, 0, 0);
+}
+// The cover of a column tile (workgroup-uniform): nfull sub-tiles + one group when exactly 4 columns are left over, else
+// all NSUB sub-tiles with the surplus masked — the path and the bits from before the exact cover.  A reduction shorter
+// than one slice (main_loop's unpipelined `lone` step) keeps whole sub-tiles too.
+struct Cover {
+  int nfull, rem;
+};
+__device__ __forceinline__ Cover cover_of(int cols_valid, int red_len) {
+  return (cols_valid & 15) == 4 && red_len >= BK ? Cover{cols_valid >> 4, 1} : Cover{NSUB, 0};
 }
 
 constexpr int kStageFloats = 64 * BK + BNT * BK > 32 * SR_OC + 32 * SC_OC ? 64 * BK + BNT * BK : 32 * SR_OC + 32 * SC_OC;
@@ -693,9 +748,52 @@ struct Pre {
 template <class F>
 __device__ __forceinline__ Pre<F> make_pre(F f) { return Pre<F>{f}; }
 
-template <bool R_KC, bool C_KC, int NS = NSUB, class OR, class OC, class PRE = NoPre>
-__device__ __forceinline__ void main_loop(floatx4 (&acc)[NSUB], float *lds, int red_begin, int red_end, const OR &opR,
-                                          const OC &opC, const PRE &pre = PRE{}) {
+// The consumers' phases: NF full sub-tiles + NG four-column groups per wave (static accumulator indices; main_loop_impl
+// picks the instance with a uniform branch outside the slice loop).  dead_half: the partial slice — index 0 — ends inside
+// its first half, so its second half is all zeros by construction: no fragment reads and no MFMAs for it.
+template <bool R_KC, bool C_KC, int NF, int NG>
+__device__ __forceinline__ void consume(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], float *lds, int nst, bool dead_half, int wave,
+                                        int lane) {
+  constexpr int rOff = R_KC ? kROffKC : kROffOC, cOff = C_KC ? kCOffKC : kCOffOC;
+  auto slot = [&](int i) { return lds + (i % kRing) * kStageFloats; };
+  Frags<NF, NG> f0, f1;
+  read_frags<R_KC, C_KC, NF, NG>(f0, slot(0) + rOff, slot(0) + cOff, wave, lane, 0);
+  int i = 0;
+  if (dead_half) {
+    __builtin_amdgcn_sched_barrier(0);
+    mma_half(acc, accg, f0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (1 < nst) read_frags<R_KC, C_KC, NF, NG>(f0, slot(1) + rOff, slot(1) + cOff, wave, lane, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    consumer_barrier();
+    i = 1;
+  }
+  for (; i < nst; ++i) {
+    const float *T = slot(i), *Tn = slot(i + 1);
+    read_frags<R_KC, C_KC, NF, NG>(f1, T + rOff, T + cOff, wave, lane, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma_half(acc, accg, f0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (i + 1 < nst) read_frags<R_KC, C_KC, NF, NG>(f0, Tn + rOff, Tn + cOff, wave, lane, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    mma_half(acc, accg, f1);
+    __builtin_amdgcn_sched_barrier(0);
+    consumer_barrier();
+  }
+}
+// nfull = 0..6 full sub-tiles + the group: every tile width 16 nfull + 4, no fallback among them.
+template <int NF>
+__device__ __forceinline__ void consume_cover(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], float *lds, int nst, bool dead_half,
+                                              int wave, int lane, int nfull) {
+  if constexpr (NF < NSUB) {
+    if (nfull == NF) consume<true, true, NF, 1>(acc, accg, lds, nst, dead_half, wave, lane);
+    else consume_cover<NF + 1>(acc, accg, lds, nst, dead_half, wave, lane, nfull);
+  }
+}
+
+template <bool R_KC, bool C_KC, int NS, bool COVER, class OR, class OC, class PRE>
+__device__ __forceinline__ void main_loop_impl(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], Cover cv, float *lds, int red_begin,
+                                               int red_end, const OR &opR, const OC &opC, const PRE &pre) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int rOff = R_KC ? kROffKC : kROffOC, cOff = C_KC ? kCOffKC : kCOffOC;
   const int nst = (red_end - red_begin + BK - 1) / BK;
@@ -706,6 +804,7 @@ __device__ __forceinline__ void main_loop(floatx4 (&acc)[NSUB], float *lds, int 
   // which only the *_any forms may read: `lone` routes every access through them (tiny reductions only).
   const bool partial = (red_end - red_begin) % BK != 0;
   const bool lone = partial && nst == 1;
+  const bool dead_half = partial && (red_end - red_begin) % BK <= BK / 2;      // the partial slice's upper 16 indices are zeros
   auto at = [&](int i) {
     const int ii = i < nst ? i : nst - 1;
     return red_begin + (partial ? (ii == 0 ? nst - 1 : ii - 1) : ii) * BK;
@@ -731,9 +830,11 @@ __device__ __forceinline__ void main_loop(floatx4 (&acc)[NSUB], float *lds, int 
       consumer_barrier();
       Frags<NS> f0, f1;
       read_frags<R_KC, C_KC, NS>(f0, slot(0) + rOff, slot(0) + cOff, wave, lane, 0);
-      read_frags<R_KC, C_KC, NS>(f1, slot(0) + rOff, slot(0) + cOff, wave, lane, 1);
       mma_half(acc, f0);
-      mma_half(acc, f1);
+      if (!dead_half) {
+        read_frags<R_KC, C_KC, NS>(f1, slot(0) + rOff, slot(0) + cOff, wave, lane, 1);
+        mma_half(acc, f1);
+      }
     }
     __syncthreads();
     return;
@@ -799,28 +900,32 @@ __device__ __forceinline__ void main_loop(floatx4 (&acc)[NSUB], float *lds, int 
     }
   } else {
     // ---------------------------------------------------------------------------------------------- consumers
-    Frags<NS> f0, f1;
     if constexpr (PRE::kActive) {
       pre();
       producer_barrier();              // (lgkmcnt(0): the constants are in LDS) pairs with the producers' extra barrier
     }
     __builtin_amdgcn_s_setprio(3);     // the matrix pipe's wave wins the issue arbitration against the producer beside it
     consumer_barrier();
-    read_frags<R_KC, C_KC, NS>(f0, slot(0) + rOff, slot(0) + cOff, wave, lane, 0);
-    for (int i = 0; i < nst; ++i) {
-      const float *T = slot(i), *Tn = slot(i + 1);
-      read_frags<R_KC, C_KC, NS>(f1, T + rOff, T + cOff, wave, lane, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma_half(acc, f0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (i + 1 < nst) read_frags<R_KC, C_KC, NS>(f0, Tn + rOff, Tn + cOff, wave, lane, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma_half(acc, f1);
-      __builtin_amdgcn_sched_barrier(0);
-      consumer_barrier();
-    }
+    if (COVER && cv.rem != 0) {
+      if constexpr (COVER) consume_cover<0>(acc, accg, lds, nst, dead_half, wave, lane, cv.nfull);
+    } else consume<R_KC, C_KC, NS, 0>(acc, accg, lds, nst, dead_half, wave, lane);
   }
   __syncthreads();     // (full fence) every wave has passed 1 + nst ring barriers; the ring is free from here on
+}
+template <bool R_KC, bool C_KC, int NS = NSUB, class OR, class OC, class PRE = NoPre>
+__device__ __forceinline__ void main_loop(floatx4 (&acc)[NSUB], float *lds, int red_begin, int red_end, const OR &opR,
+                                          const OC &opC, const PRE &pre = PRE{}) {
+  floatx4 none[NGRP];      // never touched: NS full sub-tiles, no groups
+  main_loop_impl<R_KC, C_KC, NS, false>(acc, none, Cover{NS, 0}, lds, red_begin, red_end, opR, opC, pre);
+}
+// ... with the exact column cover of a cols_valid-wide tile (KC tiles); returns the cover it ran, which says where the sums
+// are: acc[0 .. nfull) and, with rem = 1, accg[0] (see acc_to_lds in tail.hip)
+template <class OR, class OC, class PRE = NoPre>
+__device__ __forceinline__ Cover main_loop_cover(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], int cols_valid, float *lds, int red_begin,
+                                                 int red_end, const OR &opR, const OC &opC, const PRE &pre = PRE{}) {
+  const Cover cv = cover_of(cols_valid, red_end - red_begin);
+  main_loop_impl<true, true, NSUB, true>(acc, accg, cv, lds, red_begin, red_end, opR, opC, pre);
+  return cv;
 }
 
 

@@ -9,11 +9,14 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # kernel statistics: IN-GRAPH launches only (no eager per-kernel pass, no gather-only graphs, no extra legs), so that a
 # kernel's average is its average inside the replayed step
-for cfg in c2 c3 c5; do
+# CFGS="c2" limits the configurations, SKIP_PMC=1 leaves the memory-counter passes out (kernel statistics only)
+CFGS=${CFGS:-c2 c3 c5}
+for cfg in $CFGS; do
   extra=""; [ $cfg = c2 ] && extra="--no-eager-leg --no-gather-leg --no-train-step --no-sweep"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$cfg -- python3 $R/bench.py --full --config $cfg --steps 200 --warmup 20 --no-cpu-baseline $extra > $OUT/stats_$cfg.json 2> $OUT/stats_$cfg.err || exit 1
 done
-for cfg in c2 c3 c5; do
+[ -n "$SKIP_PMC" ] && CFGS=""
+for cfg in $CFGS; do
   for pmc in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
     tag=$(echo $pmc | tr ' ' '+')
     timeout -k 10 300 rocprofv3 --pmc $pmc --kernel-trace --output-format csv -d $OUT/pmc_${cfg}_$tag -- python3 $R/bench.py --full --config $cfg --steps 5 --warmup 2 --windows 0 --no-cpu-baseline --no-graph --no-gather-leg --no-train-step --no-sweep --no-eager-leg > $OUT/pmc_${cfg}_$tag.json 2> $OUT/pmc_${cfg}_$tag.err || echo "pmc $cfg $tag failed"
