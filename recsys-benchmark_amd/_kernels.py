@@ -623,10 +623,8 @@ class DualGather(torch.autograd.Function):
             # table 2 (the quotient table: ~N / divider rows) gets its gradient in ROW form: one value row per lookup, no
             # atomics into scattered rows and no [n2, De] zero-fill; table 1 (divider rows) stays dense
             ws = _dual_rows_workspace(dev, De, T1c.shape[0])
-            # (with the workspace the last workgroup WRITES table 1's gradient: no zero fill)
-            written = ws is not None and _lib.load().mi_dual_gather_bwd_rows_overwrites(De, T1c.shape[0]) != 0
-            gT1 = torch.empty_like(T1c) if written else torch.zeros_like(T1c)
             g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
+            gT1 = _dual_rows_grad1(ws, De, T1c, g, T2c, g2vals)
             rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
             _lib.check(_lib.load().mi_dual_gather_bwd_rows(idxc.data_ptr(), g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), gT1.data_ptr(),
                                                            g2vals.data_ptr(), rows2.data_ptr(), n, F, De, T1c.shape[0], T2c.shape[0],
@@ -659,6 +657,17 @@ def _dual_rows_workspace(dev, De: int, n1: int):
         ne = int(_lib.load().mi_dual_gather_bwd_rows_workspace_elems(De, n1))
         _DUAL_WS[key] = torch.zeros((ne,), dtype=torch.float32, device=dev) if ne else None
     return _DUAL_WS[key]
+
+
+def _dual_rows_grad1(ws, De: int, T1c, g, T2c, g2vals):
+    """The buffer mi_dual_gather_bwd_rows gets for table 1's dense gradient.  With the workspace the last workgroup of the
+    float4 kernel WRITES it (no zero fill) — but the library takes that kernel only when the shape qualifies
+    (mi_dual_gather_bwd_rows_overwrites) AND g, T1, T2 and g2vals are 16-byte aligned, and otherwise falls back to the
+    kernel that ADDS into it.  A contiguous view need not be aligned (the slice of a flat gradient that cat's backward
+    hands over is not), so the choice made here asks for everything the dispatch of csrc/embed.hip asks for."""
+    written = (ws is not None and _lib.load().mi_dual_gather_bwd_rows_overwrites(De, T1c.shape[0]) != 0
+               and all(t.data_ptr() % 16 == 0 for t in (g, T1c, T2c, g2vals)))
+    return torch.empty_like(T1c) if written else torch.zeros_like(T1c)
 
 
 SMALL_FIELD_ROWS = 16     # kSmallRows of csrc/embed.hip
@@ -919,9 +928,8 @@ class GatherFMDual(torch.autograd.Function):
             if need_T1 or need_T2 or need_S:
                 if qr_rows:
                     ws = _dual_rows_workspace(dev, De, n1)
-                    written = ws is not None and lib.mi_dual_gather_bwd_rows_overwrites(De, n1) != 0
-                    gT1 = torch.empty_like(T1c) if written else torch.zeros_like(T1c)
                     g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
+                    gT1 = _dual_rows_grad1(ws, De, T1c, dE, T2c, g2vals)
                     rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
                     _lib.check(lib.mi_dual_gather_bwd_rows(ids.data_ptr(), dE.data_ptr(), T1c.data_ptr(), T2c.data_ptr(),
                                                            gT1.data_ptr(), g2vals.data_ptr(), rows2.data_ptr(), n, F, De, n1, n2,
@@ -2456,7 +2464,9 @@ class SlotFM(torch.autograd.Function):
         gb = torch.empty((1,), dtype=torch.float32, device=dev) if want_gb else None
         if ctx.needs_input_grad[0]:
             gbuf = torch.empty((rows, D + 4), dtype=torch.float32, device=dev)
-            # the kernel zeroes rows [0, S) itself; the dump row's gradient is never read
+            # the kernel zeroes rows [0, S) itself and never stores to the dump row: that row (what the all-to-all does not
+            # ship, but part of the gradient autograd hands on) is zeroed here
+            gbuf[rows - 1].zero_()
             _lib.check(
                 lib.mi_slot_fm_bwd(slot.data_ptr(), emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb),
                                    gbuf.data_ptr(), _lib.ptr(gb), rows - 1, B, F, D, _lib.stream_ptr(dev)),
