@@ -706,6 +706,7 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bwd(ActDesc x, const float
         kb[u] = drop.fetch(m, c);
       }
     }
+    loads_landed();      // the trip's loads (and the constants) waited for once: no wait between its DY stores
 #pragma unroll
     for (int u = 0; u < kHeadRows; ++u) {
       const int m = m4 + u;
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bwd(ActDesc x, const float
       st4(sw + c, s_ga);
     }
     if (threadIdx.x == 0) sw[N] = s_g;
-    __syncthreads();
+    lds_barrier();       // orders sp / sw only: the DY stores stay in flight under the atomics
     const int rr = blockIdx.x % reps;
     float *o = part + (int64_t)rr * N * 2;
     for (int i = threadIdx.x; i < 2 * N; i += kBlock) atomicAdd(o + i, sp[i]);
@@ -784,7 +785,9 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
   __shared__ __attribute__((aligned(16))) float cst[MERGE != 0 ? 3 * kCstPitch : 4];
   __shared__ __attribute__((aligned(16))) float red[kWavesPerBlock][kHeadLossRed];
   if (bump && blockIdx.x == 0 && threadIdx.x == 0) bump[0] += 1;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // (the wave's index as a SCALAR: the row loop and the split of the roles at the end are then branches of the whole wave, and
+  //  what the loss chain leaves pending is not carried into the column-sum waves' path as a wait in front of their atomics)
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wave0 = blockIdx.x * kWavesPerBlock + wv, nw = gridDim.x * kWavesPerBlock;
   const Drop drop = make_drop(x.keep, x.p, x.ld);
   const float bv = b ? b[0] : 0.f;
@@ -825,6 +828,9 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
       }
     }
     first = false;
+    // every global load of this trip (rows, labels, constants) has landed: waited for once, where every lane passes, so
+    // that no register below needs a vmcnt wait while the trip's stores are outstanding
+    loads_landed();
     if (m0 >= M) break;
     // the four rows' dots first, then ONE butterfly over the four sums side by side (a row at a time is four dependent chains
     // of six lane exchanges, ~1 us of a kernel that is all latency), then the rows' remaining arithmetic
@@ -860,6 +866,9 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
 #pragma unroll
       for (int u = 0; u < 4; ++u) sa[u] += __shfl_xor(sa[u], msk);
     }
+    // the rows' arithmetic first (their column sums ride along in row order), then the trip's stores (out, g and DY of up to four rows) as ONE group
+    float4 d0[4], d1[4];
+    float xo[4], go[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int m = m0 + u * nw;
@@ -874,14 +883,14 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
       const float gm = gsc * (1.f / (1.f + expf(-xl)) - yv[u]);
       s_loss += fmaxf(xl, 0.f) - xl * yv[u] + log1pf(expf(-fabsf(xl)));
       s_g += gm;
-      if (lane == 0) { out[m] = xl; gout[m] = gm; }
+      xo[u] = xl; go[u] = gm;
       if (v0) {
         float4 d;
         d.x = pre0.x > 0.f ? gm * w0.x * kk0.x : 0.f;
         d.y = pre0.y > 0.f ? gm * w0.y * kk0.y : 0.f;
         d.z = pre0.z > 0.f ? gm * w0.z * kk0.z : 0.f;
         d.w = pre0.w > 0.f ? gm * w0.w * kk0.w : 0.f;
-        st4(DY + (int64_t)m * x.ld + c0, d);
+        d0[u] = d;
         dy0.x += d.x; dy0.y += d.y; dy0.z += d.z; dy0.w += d.w;
         dz0.x += d.x * zc0.x; dz0.y += d.y * zc0.y; dz0.z += d.z * zc0.z; dz0.w += d.w * zc0.w;
         ga0.x += gm * fmaxf(pre0.x, 0.f) * kk0.x; ga0.y += gm * fmaxf(pre0.y, 0.f) * kk0.y;
@@ -893,12 +902,20 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
         d.y = pre1.y > 0.f ? gm * w1.y * kk1.y : 0.f;
         d.z = pre1.z > 0.f ? gm * w1.z * kk1.z : 0.f;
         d.w = pre1.w > 0.f ? gm * w1.w * kk1.w : 0.f;
-        st4(DY + (int64_t)m * x.ld + c1, d);
+        d1[u] = d;
         dy1.x += d.x; dy1.y += d.y; dy1.z += d.z; dy1.w += d.w;
         dz1.x += d.x * zc1.x; dz1.y += d.y * zc1.y; dz1.z += d.z * zc1.z; dz1.w += d.w * zc1.w;
         ga1.x += gm * fmaxf(pre1.x, 0.f) * kk1.x; ga1.y += gm * fmaxf(pre1.y, 0.f) * kk1.y;
         ga1.z += gm * fmaxf(pre1.z, 0.f) * kk1.z; ga1.w += gm * fmaxf(pre1.w, 0.f) * kk1.w;
       }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int m = m0 + u * nw;
+      if (m >= M) break;
+      if (lane == 0) { out[m] = xo[u]; gout[m] = go[u]; }
+      if (v0) st4(DY + (int64_t)m * x.ld + c0, d0[u]);
+      if (v1) st4(DY + (int64_t)m * x.ld + c1, d1[u]);
     }
   }
   // the four waves' sums meet in LDS: [0, 2 * 512) (sum dy, sum dy (z - mu)) interleaved per column, [1024, 1536) the
@@ -915,7 +932,9 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
     st4(rp + 2 * kHeadLossCols + c1, ga1);
   }
   if (lane == 0) { rp[3 * kHeadLossCols] = s_g; rp[3 * kHeadLossCols + 1] = s_loss; }
-  __syncthreads();
+  // orders `red` only: the DY stores stay in flight under the column-sum atomics and the loss chain (nothing below reads
+  // out / gout / DY; the loss chain's own fences wait as they must, and the kernel's end waits for every store)
+  lds_barrier();
   const int rr = blockIdx.x % reps;
   // the last wave takes the loss (a chain of dependent round trips: add, fence, ticket), the other three the column sums
   // (fire and forget): the two run side by side instead of one after the other
@@ -928,18 +947,23 @@ __global__ __launch_bounds__(kBlock) void k_tail_head_bce(ActDesc x, const float
       const int j = i < N ? 2 * kHeadLossCols + i : 3 * kHeadLossCols;
       atomicAdd(q + i, (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]));
     }
-  } else if (lane == 0) {
-    const int j = 3 * kHeadLossCols + 1;
-    const float lp = ((red[0][j] + red[1][j]) + (red[2][j] + red[3][j])) * inv_m;
-    atomicAdd(loss_ws + 4 + rr, lp);
-    __threadfence();
-    const uint32_t mine = ((uint32_t)gridDim.x - (uint32_t)rr + (uint32_t)reps - 1u) / (uint32_t)reps;   // workgroups of this replica
-    const uint32_t old = atomicAdd(reinterpret_cast<uint32_t *>(loss_ws + 4 + reps) + rr, 1u);
-    if (old == mine - 1u) {
+  } else {
+    if (lane == 0) {
+      const int j = 3 * kHeadLossCols + 1;
+      const float lp = ((red[0][j] + red[1][j]) + (red[2][j] + red[3][j])) * inv_m;
+      atomicAdd(loss_ws + 4 + rr, lp);
       __threadfence();
-      const float v = __hip_atomic_load(loss_ws + 4 + rr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      atomicAdd(loss_ws, v);
+      const uint32_t mine = ((uint32_t)gridDim.x - (uint32_t)rr + (uint32_t)reps - 1u) / (uint32_t)reps;   // workgroups of this replica
+      const uint32_t old = atomicAdd(reinterpret_cast<uint32_t *>(loss_ws + 4 + reps) + rr, 1u);
+      if (old == mine - 1u) {
+        __threadfence();
+        const float v = __hip_atomic_load(loss_ws + 4 + rr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        atomicAdd(loss_ws, v);
+      }
     }
+    // (the chain's wave is done; said here so that what it leaves pending is not carried, where the two paths join in the
+    //  compiled code, into the column-sum waves' as a vmcnt(0) in front of their atomics)
+    loads_landed();
   }
 }
 
@@ -1086,7 +1110,9 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
   // ---- epilogue through LDS (see k_tail_fwd): all 8 waves, whole row segments
   float *T = lds;
   acc_to_lds(acc, accg, cv, T, wave, lane);
-  __syncthreads();
+  // (FM: orders T only — no wave reads another wave's global stores in this kernel)
+  if constexpr (FM) lds_barrier();
+  else __syncthreads();
   const int t = threadIdx.x;
   if constexpr (FM) {
     static_assert(!MID, "the FM epilogue belongs to the product whose output is the tail's input gradient");
@@ -1094,7 +1120,7 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
     // arithmetic: one round trip for the epilogue
     float4 e[4], sm[4], da[4];
     float gy[4];
-    int64_t sl[4] = {0, 0, 0, 0};
+    int64_t sl[4];      // (read only with fm_slot; not zeroed: a zero written beside the load on the other path costs a wait between the loads)
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1107,6 +1133,16 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
       da[k] = ld4(T + (ok[k] ? row : 0) * kTilePitch + (ok[k] ? c : 0));
       if (a.fm_slot) sl[k] = a.fm_slot[(int64_t)m * (a.K / a.fm_D) + kc / a.fm_D];
     }
+    // the first-order values of this row tile (gy[m] for every field) belong to the same round trip: the first
+    // 4 * kThreads of them are loaded here, stored behind the rows
+    const bool g1w = a.fm_g1 && nt == 0;
+    const int F = a.K / a.fm_D, ng1 = rows_valid * F;
+    float g1v[4];
+    if (g1w) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g1v[k] = a.fm_gy[m0 + min(t + k * kThreads, ng1 - 1) / F];
+    }
+    loads_landed();      // every load above has landed: the stores below go out back to back
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int i = t + k * kThreads, row = i / 28, c = (i % 28) * 4;
@@ -1126,9 +1162,13 @@ __global__ __launch_bounds__(kThreads) void k_tail_dgrad(DgradArgs a) {
         }
       }
     }
-    if (a.fm_g1 && nt == 0) {      // the first-order table's gradient values of this row tile: gy[m] for every field
-      const int F = a.K / a.fm_D;
-      for (int i = t; i < rows_valid * F; i += kThreads) a.fm_g1[(int64_t)m0 * F + i] = a.fm_gy[m0 + i / F];
+    if (g1w) {      // the first-order table's gradient values of this row tile
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = t + k * kThreads;
+        if (i < ng1) a.fm_g1[(int64_t)m0 * F + i] = g1v[k];
+      }
+      for (int i = t + 4 * kThreads; i < ng1; i += kThreads) a.fm_g1[(int64_t)m0 * F + i] = a.fm_gy[m0 + i / F];      // (F > 32)
     }
   } else if constexpr (!MID) {
 #pragma unroll

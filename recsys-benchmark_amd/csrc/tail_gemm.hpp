@@ -722,6 +722,29 @@ __device__ __forceinline__ void producer_barrier() {
 }
 __device__ __forceinline__ void consumer_barrier() { __builtin_amdgcn_s_barrier(); }
 
+// Waits and barriers of the epilogues.  Loads and stores share ONE in-order vmcnt on gfx9, and a store stays counted until it
+// is acknowledged.  Back-to-back plain stores get counted waits (vmcnt(2), (2), (2) for three loads stored in turn), but where
+// the stores sit under a lane-divergent `if` the compiler's count for a later use of an OLDER load comes out tighter than the
+// load needs (0 at most joins), and a value loaded behind a store always waits vmcnt(0).  Such a wait is a wait for the
+// acknowledgement of the wave's OWN stores: a group of stores with them in between pays one round trip per store, and so
+// does whatever follows (column-sum atomics behind a barrier).
+//   loads_landed(): vmcnt(0), lgkmcnt / expcnt untouched.  Called in control flow that every lane of the wave walks, after the
+//     last global load of an epilogue (or of a loop trip) and before its first store: from there on no load is pending on
+//     any path, no register needs a vmcnt wait again, and the stores go out back to back.
+//   lds_barrier(): a barrier that orders LDS traffic only (lgkmcnt(0) + s_barrier, like producer_barrier; the fences keep
+//     the compiler from moving an LDS access across it and are "local": they emit no vmcnt wait).  The wave's global stores
+//     stay in flight across it.  Only for barriers after which no wave reads what another wave stored to GLOBAL memory
+//     before it; the end of the kernel still waits for every store.
+// (profiles/epilogue_waits.txt: which epilogues gained from them and which did not.)
+__device__ __forceinline__ void loads_landed() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0); expcnt(7), lgkmcnt(15): untouched
+}
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // The main loop over the BK slices [red_begin, red_end), one barrier per slice, roles split by wave:
 //   waves 4-7 (producers): in phase i they transform slice i+3 (fetched during phase i-3) and write it to LDS slot
 //     (i+3) % 4, then issue the global loads of slice i+6 into the register stage that just became free (three register
