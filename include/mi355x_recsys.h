@@ -439,6 +439,43 @@ MI_API int mi_qat_gather_bwd(const int64_t *idx, const float *W, const float *sc
                              const float *prob, const int64_t *seed, int64_t salt, const float *g,
                              float *dW, float *dscale, int64_t n, int32_t D, int64_t N, void *stream);
 
+/* ---- DeepFM on the quantised tables: lookup + dequantisation / rounding + FM + first order, ONE launch ----
+ * row = idx[b,f] + offsets[f] (offsets nullable); emb fp32[B,F,D]; yfm[b] = the FM second-order term of emb[b] + the
+ * first-order bag sum_f w1[row * ldw1] + bias[0] (bias nullable).  A row outside [0, N) reads as a zero row and ORs
+ * MI_IDX_OUT_OF_RANGE into *err.  D = 4 * 2^k <= 256 with the table's base aligned to four codes and emb to 16 bytes runs
+ * the kernels that load a lane's four codes as one word, anything else the scalar ones: the same bits.
+ * mi_gather_fm_quant_fwd (inference; PTQEmb_Int / PTQEmb_Fp16): Wq, qtype, scale and zero as W, qtype, scale and bias of
+ *   mi_gather_rows_quant, and emb has that entry point's bits over idx + offsets.
+ * mi_gather_fm_qat_fwd (QAT_EmbInt, training and evaluation): W, scale, n_bits, prob, seed and salt as mi_qat_gather_fwd;
+ *   the draw of emb element (b F + f) D + d is prob[that index] or the generator's at that index, so emb has the bits of
+ *   mi_qat_gather_fwd over idx + offsets.  rows_out int64[B,F], nullable: idx + offsets.
+ * mi_gather_fm_qat_bwd_rows: the row-form backward from the saved emb, no float atomics.  For lookup i = b F + f:
+ *   gvals[i,:] = g_emb[i,:] + g_y[b] (S_b - emb[i,:]), S_b = sum_f emb[b,f,:] (straight through the rounding; g_emb nullable),
+ *   g1vals[i] = g_y[b], gbias[0] = sum_b g_y[b] (nullable).
+ *   W and dscale both given (else both NULL: the table is not read): dscale[0] = sum gvals * m over the lookups inside [0, N),
+ *   m = q_max where W[row]/scale >= q_max, q_min where <= q_min, else rintf(emb / scale) - W[row]/scale (the code the forward
+ *   rounded to, recovered from emb); rows = rows_out.  The sum is joined over the grid in a fixed order by the last workgroup
+ *   to arrive and is complete when the launch ends.  It takes `workspace` (mi_gather_fm_qat_bwd_workspace_elems floats), whose
+ *   LAST word is a ticket: armed != 0 says it is zero already (every launch leaves it zero), armed = 0 zeroes it first.
+ *   D <= MI_GATHER_FM_QAT_BWD_MAX_D, and n_bits <= 21 when dscale is wanted (the code is recovered from emb exactly up to
+ *   there), else MI_ERR_UNSUPPORTED.
+ */
+#define MI_GATHER_FM_QAT_BWD_MAX_D 256
+MI_API int mi_gather_fm_quant_fwd(const int64_t *idx, const int64_t *offsets, const void *Wq, int32_t qtype,
+                                  const float *scale, const void *zero, const float *w1, int64_t ldw1,
+                                  const float *bias, float *emb_out, float *yfm_out,
+                                  int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, void *stream);
+MI_API int mi_gather_fm_qat_fwd(const int64_t *idx, const int64_t *offsets, const float *W, const float *scale,
+                                int32_t n_bits, const float *prob, const int64_t *seed, int64_t salt,
+                                const float *w1, int64_t ldw1, const float *bias, float *emb_out, float *yfm_out,
+                                int64_t *rows_out, int64_t B, int32_t F, int32_t D, int64_t N,
+                                int32_t *err, void *stream);
+MI_API int64_t mi_gather_fm_qat_bwd_workspace_elems(int64_t B);
+MI_API int mi_gather_fm_qat_bwd_rows(const int64_t *rows, const float *W, const float *scale, int32_t n_bits,
+                                     const float *emb, const float *g_y, const float *g_emb,
+                                     float *gvals, float *g1vals, float *gbias, float *dscale, float *workspace,
+                                     int32_t armed, int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
+
 /* ---- §8f rank 4 (fourth flavour): OptEmbed supernet lookup ---------------------------------------
  * OptEmbed.forward / get_weight (src/models/embeddings/deepfm_opt_embed.py:150-243) with _MaskEmbeddingModule
  * and BinaryStep (optembed_utils.py:10-112):

@@ -138,6 +138,10 @@ SIGNATURES = {
     "mi_lse_diag_bwd": [_p, _i64, _i32, ctypes.c_float, _p, _p, _p, _p, _i32, _p],
     "mi_qat_gather_fwd": [_p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _i32, _i64, _p, _p],
     "mi_qat_gather_bwd": [_p, _p, _p, _i32, _p, _p, _i64, _p, _p, _p, _i64, _i32, _i64, _p],
+    "mi_gather_fm_quant_fwd": [_p, _p, _p, _i32, _p, _p, _p, _i64, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_gather_fm_qat_fwd": [_p, _p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_gather_fm_qat_bwd_workspace_elems": [_i64],
+    "mi_gather_fm_qat_bwd_rows": [_p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p],
     "mi_optembed_fwd": [_p, _p, _p, _p, _i32, _p, _i32, _p, _i64, _i32, _i64, _p, _p],
     "mi_optembed_bwd": [_p, _p, _p, _p, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _i64, _p],
     "mi_optembed_cf_fwd": [_p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _i32, _p, _i64, _i32, _p, _p],
@@ -237,7 +241,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_route_unique_workspace_elems": ctypes.c_int64, "mi_slot_fm_bwd_segments_workspace_elems": ctypes.c_int64,
              "mi_gather_fm_soft_bwd_workspace_elems": ctypes.c_int64, "mi_binary_auc_workspace_bytes": ctypes.c_int64,
              "mi_ctr_metric_append_workspace_bytes": ctypes.c_int64,
-             "mi_cerp_prune_loss_workspace_elems": ctypes.c_int64}
+             "mi_cerp_prune_loss_workspace_elems": ctypes.c_int64,
+             "mi_gather_fm_qat_bwd_workspace_elems": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

@@ -11,17 +11,10 @@
 // backward re-derives the forward's rounding instead of storing it; tests may pass an explicit `prob`
 // array (the reference's torch.rand_like draw) to pin the arithmetic bit for bit.
 #include "common.hpp"
+#include "sr_round.hpp"      // uniform01, sr_round: shared with the fused lookup of gather_fm_quant.hip
 
 namespace {
 using namespace mi;
-
-__device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  const uint32_t r = (uint32_t)((z ^ (z >> 31)) >> 40);   // 24 random bits: exactly representable, < 1
-  return (float)r * (1.0f / 16777216.0f);
-}
 
 struct QatArgs {
   const int64_t *idx;   // nullable: identity (row i)
@@ -35,15 +28,6 @@ struct QatArgs {
   int D;
   int64_t N;
 };
-
-__device__ __forceinline__ float sr_round(const QatArgs &a, float w, float s, int64_t e, float &qf) {
-  qf = w / s;
-  const float q = fminf(fmaxf(qf, a.qmin), a.qmax);
-  const float fl = floorf(q);
-  const float pf = fl + 1.f - q;
-  const float u = a.prob ? a.prob[e] : uniform01((uint64_t)(a.seed[0] + a.salt), (uint64_t)e);
-  return fl + (u > pf ? 1.f : 0.f);
-}
 
 __global__ __launch_bounds__(kBlock) void k_qat_fwd(QatArgs a, float *__restrict__ out, int *err) {
   const int64_t total = a.n * a.D;

@@ -13,6 +13,7 @@ What runs where:
          mi_gather_fm_masked_{fwd,bwd_rows,bwd_dense}      (OptEmbed: a search candidate in eval, the retraining table), or
          mi_gather_fm_{soft,elemmask}_{fwd,bwd_rows}       (PEP: the threshold search, the retraining table), or
          mi_gather_fm_dual_{fwd,bwd_rows,finish}           (QR add / mult, CERP, CERP retrain), or
+         mi_gather_fm_qat_{fwd,bwd_rows} / _quant_fwd      (QAT; the post-training-quantised tables in eval), or
          IEmbedding.forward + mi_fm_fwd / mi_fm_bwd        (compressed tables)
   the MLP tail (a real GEMM): the library's own fp32-MFMA products with BatchNorm1d / ReLU / Dropout in
       their operand loads and epilogues (tail.py, csrc/tail.hip) in training, eval() and no-BatchNorm stacks alike; the
@@ -24,13 +25,22 @@ from typing import Any, Dict, List, Optional, Union, cast
 import torch
 from torch import nn
 
-from . import _kernels
+from . import _kernels, quant_fm
 from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
 from .embeddings.cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
 from .embeddings.pep_embedding import PepEmbeeding, RetrainPepEmbedding
+from .embeddings.ptq_emb import PTQEmb_Fp16, PTQEmb_Int
+from .embeddings.qat_emb import QAT_EmbInt
 from .embeddings.qr_embedding import QRHashingEmbedding
 from .mlp import field_offsets, hidden_stack, run_tail
+
+
+def _hooked(module: nn.Module) -> bool:
+    """Whether a forward hook or pre-hook would fire on a call of `module`: its own, or one registered for every module."""
+    from torch.nn.modules import module as _m
+
+    return bool(module._forward_hooks or module._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks)
 
 
 class DeepFM(nn.Module):
@@ -138,6 +148,21 @@ class DeepFM(nn.Module):
         if dual is not None:
             return _kernels.gather_fm_dual(x, self.offsets, w1=self.fc.weight, bias=self._bias,
                                            sparse_w1=bool(self.fc.sparse), **dual)
+        # QAT / PTQ: the rounding, or the dequantisation of the code rows, inside the same launch (mi_gather_fm_qat_* /
+        # mi_gather_fm_quant_fwd).  This branch never calls the embedding module, so a module with a forward hook or
+        # pre-hook — its own or a global one — keeps the path below: the hooks keep firing.  Bag modes and CPU tables keep
+        # it too.  The PTQ launch is inference only (no autograd node): a forward whose first-order term or bias wants a
+        # gradient keeps the path below as well, where fm_first_order hands fc.weight and _bias theirs.
+        if isinstance(emb_mod, (QAT_EmbInt, PTQEmb_Int, PTQEmb_Fp16)) and not _hooked(emb_mod):
+            if isinstance(emb_mod, QAT_EmbInt):
+                quant = emb_mod.fm_quant(x)
+                if quant is not None:
+                    return quant_fm.gather_fm_qat(x, self.offsets, w1=self.fc.weight, bias=self._bias,
+                                                  sparse_w1=bool(self.fc.sparse), **quant)
+            elif not (torch.is_grad_enabled() and (self.fc.weight.requires_grad or self._bias.requires_grad)):
+                quant = emb_mod.fm_quant(x)
+                if quant is not None:
+                    return quant_fm.gather_fm_quant(x, self.offsets, w1=self.fc.weight, bias=self._bias, **quant)
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

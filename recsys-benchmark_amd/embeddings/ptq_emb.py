@@ -41,6 +41,14 @@ class _FrozenTable(IEmbedding):
         rows, width = self.weight.shape
         return rows * width
 
+    def fm_quant(self, x):
+        """The operands of DeepFM's fused lookup + dequantisation + FM launch (quant_fm.gather_fm_quant) for the ids x, or
+        None when this table keeps forward(): a CPU table, an input that is not [B, F] on the table's device.  (These
+        tables have no bag mode: `mode` is accepted and ignored.)"""
+        if not self.weight.is_cuda or not x.is_cuda or x.dim() != 2:
+            return None
+        return self._fm_operands()
+
 
 class PTQEmb_Fp16(_FrozenTable):
     def __init__(self, field_dims, num_factor, mode, ori_checkpoint_path):
@@ -49,6 +57,9 @@ class PTQEmb_Fp16(_FrozenTable):
 
     def forward(self, x):
         return _kernels.gather_rows_quant(x, self.weight)                     # fp16 rows -> fp32
+
+    def _fm_operands(self):
+        return dict(Wq=self.weight)
 
     def get_weight(self) -> torch.Tensor:
         return self.weight
@@ -67,6 +78,9 @@ class PTQEmb_Int(_FrozenTable):
 
     def forward(self, x):
         return _kernels.gather_rows_quant(x, self.weight, self.scale.reshape(1), self.bias.reshape(1))
+
+    def _fm_operands(self):
+        return dict(Wq=self.weight, scale=self.scale, zero_point=self.bias)
 
     def get_weight(self) -> torch.Tensor:
         return (self.weight - self.bias) * self.scale

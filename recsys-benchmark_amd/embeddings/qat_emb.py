@@ -81,5 +81,20 @@ class QAT_EmbInt(VanillaEmbedding):
         bag = super().forward(x)                       # EmbeddingBag modes reduce first, then the bag is rounded
         return _QatLookup.apply(self.scale, bag, None, int(self.n_bits), seed, 0, prob, None)
 
+    def fm_quant(self, x):
+        """The operands of DeepFM's fused lookup + rounding + FM launch (quant_fm.gather_fm_qat) for the ids x, or None
+        when this table keeps forward(): a bag mode, a CPU or non-fp32 table, an input that is not [B, F], a width past the
+        fused backward's limit.  Like forward() it takes the next word of the rounding stream — call it only for a lookup
+        that is then made."""
+        from .. import quant_fm
+
+        W = self._emb_module.weight
+        if (self._mode is not None or not W.is_cuda or W.dtype != torch.float32 or not x.is_cuda or x.dim() != 2
+                or W.shape[1] > quant_fm.QAT_BWD_MAX_D):
+            return None
+        seed = self._sr_seed.clone()
+        self._sr_seed.add_(1)
+        return dict(W=W, scale=self.scale, n_bits=int(self.n_bits), seed=seed, sparse_W=self.sparse_grad)
+
     def get_weight(self):
         return super().get_weight()
