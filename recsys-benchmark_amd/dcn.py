@@ -112,10 +112,11 @@ class DCNv2(_FieldModel):
         if self.structure == "Stacked":
             # _dnn + _last_fc is the same (Linear, BatchNorm1d, ReLU, Dropout) x k + Linear(., 1) tail as DeepFM's: one node
             # over the fused kernels, the first-order term added inside its last kernel (src/models/dcn.py:196-222)
-            tail = self.__dict__.get("_stacked_tail")
-            if tail is None or len(tail) != len(self._dnn) + 1 or tail[-1] is not self._last_fc:
-                tail = nn.Sequential(*self._dnn, self._last_fc)
+            tail, mods = self.__dict__.get("_stacked_tail"), [*self._dnn, self._last_fc]
+            if tail is None or len(tail) != len(mods) or not all(a is b for a, b in zip(tail, mods)):
+                tail = nn.Sequential(*mods)
                 self.__dict__["_stacked_tail"] = tail          # (not a registered submodule: state_dict keys unchanged)
-            return run_tail(tail, crossed, last_add=first_order, labels=labels).squeeze(-1)
+            # (model.eval() / .train() never reach the unregistered container: the labels are gated on the model's own mode)
+            return run_tail(tail, crossed, last_add=first_order, labels=labels if self.training else None).squeeze(-1)
         features = torch.concat([crossed, run_tail(self._dnn, fields)], dim=1)
         return (self._last_fc(features) + first_order).squeeze(-1)

@@ -70,7 +70,8 @@ class _HeadBCEFn(torch.autograd.Function):
     def backward(ctx, g):
         head = ctx.head
         (x,) = ctx.saved_tensors
-        if g.data_ptr() == head.seed.data_ptr():       # the very scalar the head launch scaled its gradient by
+        # the very scalar the head launch scaled its gradient by, holding the value it read then (not updated in place since)
+        if g.data_ptr() == head.seed.data_ptr() and head.seed_current():
             return head.gvec.view(ctx.shape), None
         g = _kernels._f32c(g).view(1)
         x = x.reshape(-1)

@@ -240,8 +240,16 @@ class _Lead:
 
 class _HeadLoss:
     """What mi_tail_head_bce left for the criterion: losses.BCEWithLogitsLoss(logits, labels) picks it up when it is handed
-    exactly these logits and labels (take_head_loss), otherwise computes the loss itself."""
-    __slots__ = ("out", "y", "y_key", "loss", "gvec", "seed")
+    exactly these logits and labels (take_head_loss), otherwise computes the loss itself.  The launch READ the logits and the
+    upstream seed's value: out_version / seed_version are their versions then — the loss stands only for unmodified logits
+    (current), the gradient only for an unmodified seed (seed_current)."""
+    __slots__ = ("out", "y", "y_key", "loss", "gvec", "seed", "out_version", "seed_version")
+
+    def current(self) -> bool:
+        return self.out._version == self.out_version
+
+    def seed_current(self) -> bool:
+        return self.seed._version == self.seed_version
 
 
 _HEAD_LOSS = {}
@@ -258,7 +266,8 @@ def take_head_loss(logits: torch.Tensor, target: torch.Tensor):
     if h is None:
         return None
     if (logits.dtype == torch.float32 and logits.requires_grad and logits.data_ptr() == h.out.data_ptr()
-            and logits.numel() == h.out.numel() and logits.is_contiguous() and _label_key(target) == h.y_key):
+            and logits.numel() == h.out.numel() and logits.is_contiguous() and _label_key(target) == h.y_key
+            and h.current() and logits._version == h.out_version):        # (a view shares its base's version counter)
         return h
     return None
 
@@ -442,6 +451,7 @@ def _tail_forward(plan, seed, x, last_add, Ws, w_head, b_head, lead: Optional[_L
             w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(add), y.data_ptr(), out.data_ptr(), head.gvec.data_ptr(), DY.data_ptr(),
             zeros[hoff:].data_ptr(), zeros[hoff + Rh * 2 * N:].data_ptr(), Rh, zeros[loff:].data_ptr(), M, N,
             ctypes.byref(stats) if stats is not None else None, _lib.ptr(loss_seed), s), "mi_tail_head_bce")
+        head.out_version, head.seed_version = out._version, head.seed._version
         _HEAD_LOSS[str(dev)] = head
     elif head_epi:
         pass                               # (the logits came out of the last product's epilogue)

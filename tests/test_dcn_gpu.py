@@ -227,3 +227,59 @@ def test_mix_expert_kernels_vs_float64(M, d, E, r):
     with pytest.raises(_lib.MI355XLibraryError):          # rank 48 is outside the fused form: the caller keeps the separate products
         _lib.check(lib.mi_mix_expert_fwd(xd.data_ptr(), Vd.data_ptr(), Cd.data_ptr(), gd.data_ptr(), H1.data_ptr(), H2.data_ptr(),
                                          H2g.data_ptr(), M, d, E, 48, st), "fwd")
+
+
+def _small_dcnv2():
+    from recsys_benchmark_amd.dcn import DCNv2
+
+    torch.manual_seed(21)
+    dims, B = [11, 7, 5], 37
+    model = DCNv2(dims, 8, [24, 16], num_layers=2, p_dropout=0.0, structure="Stacked")
+    with torch.no_grad():
+        for m in model._dnn:
+            if isinstance(m, torch.nn.BatchNorm1d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.3)
+                m.running_mean.normal_(0, 0.3)
+                m.running_var.uniform_(0.5, 1.5)
+    gen = torch.Generator().manual_seed(5)
+    x = torch.stack([torch.randint(0, d, (B,), generator=gen) for d in dims], 1)
+    y = (torch.rand(B, generator=gen) < 0.4).float()
+    return model, x, y
+
+
+def _dcnv2_float64(model, x, training):
+    """The oracle's DCNv2 forward in float64 on the model's CURRENT parameters and buffers."""
+    p = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in model.state_dict().items()}
+    emb = p["embedding._emb_module.weight"][x + p["offsets"]]
+    return ro.dcnv2_forward(x, p, emb, 2, 2, training, "Stacked")
+
+
+def test_stacked_dcnv2_runs_the_layer_that_is_there_now():
+    """The stacked tail's container is rebuilt when a module of `_dnn` was replaced: the forward after the swap is the
+    float64 evaluation with the NEW layer."""
+    model, x, _ = _small_dcnv2()
+    model.to(DEV).train()
+    before = model(x.to(DEV)).detach()
+    torch.manual_seed(22)
+    model._dnn[0] = torch.nn.Linear(24, 24).to(DEV)
+    want = _dcnv2_float64(model, x, True)
+    got = model(x.to(DEV))
+    assert float((before.cpu().double() - want).abs().max()) > 1e-2, "the replaced layer makes no difference: a vacuous test"
+    assert_close(got, want.float(), 1e-4, 1e-5, "logits with the replaced layer")
+
+
+def test_stacked_dcnv2_in_eval_mode_leaves_no_head_loss_behind():
+    """model.eval() after a training forward, then model(x, labels=y): the logits are the eval-mode oracle's and the criterion
+    is NOT evaluated in the head launch (labels belong to a training step: the gate is the model's own mode)."""
+    from recsys_benchmark_amd import tail as _tail_mod
+
+    model, x, y = _small_dcnv2()
+    model.to(DEV).train()
+    model(x.to(DEV), labels=y.to(DEV))
+    _tail_mod._HEAD_LOSS.clear()
+    model.eval()
+    want = _dcnv2_float64(model, x, False)
+    got = model(x.to(DEV), labels=y.to(DEV))
+    assert_close(got, want.float(), 1e-4, 1e-5, "eval-mode logits")
+    assert not _tail_mod._HEAD_LOSS, "an eval-mode forward registered a head loss"

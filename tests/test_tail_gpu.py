@@ -290,6 +290,67 @@ def test_head_launch_with_the_criterion_and_a_named_upstream_seed(M, K, hidden, 
         assert_close(u, v, 2e-4, 1e-6 + 2e-8 * M, name)
 
 
+def _criterion_step(seq0, x, add, y, labels_in_forward, up=None, between=None, on_logits=None):
+    """One step through run_tail + the package's criterion on the dropout seed 1234; `between(up)` runs after the criterion and
+    before backward, `on_logits(logits)` before the criterion.  Returns (loss, dx, dadd, parameter gradients)."""
+    from recsys_benchmark_amd.losses import BCEWithLogitsLoss
+
+    dev = torch.device(DEV, 0)
+    seq = copy.deepcopy(seq0).to(DEV)
+    xd, ad, yd = x.to(DEV).requires_grad_(True), add.to(DEV).requires_grad_(True), y.to(DEV)
+    _mlp._seed_word(dev).fill_(1234)
+    out = run_tail(seq, xd, last_add=ad, labels=yd if labels_in_forward else None, loss_seed=up if labels_in_forward else None)
+    logits = out.squeeze(-1)
+    if on_logits is not None:
+        on_logits(logits)
+    loss = BCEWithLogitsLoss()(logits, yd)
+    if between is not None:
+        between(up)
+    loss.backward(up)
+    return loss.detach(), xd.grad, ad.grad, [q.grad for q in seq.parameters()]
+
+
+def _same_step(a, b, seq0, M):
+    assert_close(a[0], b[0], 1e-5, 1e-6, "loss")
+    assert_close(a[1], b[1], 2e-4, 1e-7, "dx")
+    assert_close(a[2], b[2], 1e-5, 1e-9, "d last_add")
+    for u, v, (name, _) in zip(a[3], b[3], seq0.named_parameters()):
+        assert_close(u, v, 2e-4, 1e-6 + 2e-8 * M, name)
+
+
+def test_named_seed_updated_in_place_before_backward_is_read_at_backward_time():
+    """A loss scale kept in one buffer: the head launch scaled its gradient by the seed's value at FORWARD time; updated in
+    place before backward, the gradients are those of the value at backward time, as with any upstream gradient."""
+    torch.manual_seed(17)
+    M, K = 200, 48
+    seq0 = _seq(K, [40, 72], 0.5).train()
+    x, add, y = torch.randn(M, K), torch.randn(M), (torch.rand(M) < 0.4).float()
+    dev = torch.device(DEV, 0)
+    got = _criterion_step(seq0, x, add, y, True, torch.full((), 0.25, device=dev), between=lambda up: up.fill_(0.5))
+    want = _criterion_step(seq0, x, add, y, False, torch.full((), 0.5, device=dev))
+    assert float(want[1].abs().max()) > 0
+    _same_step(got, want, seq0, M)
+
+
+def test_logits_modified_in_place_before_the_criterion_give_their_own_loss():
+    """The head launch evaluated the criterion on the logits as it wrote them; logits changed in place afterwards get the
+    loss (and the gradients) of what they hold now."""
+    torch.manual_seed(18)
+    M, K = 200, 48
+    seq0 = _seq(K, [40, 72], 0.5).train()
+    x, add, y = torch.randn(M, K), torch.randn(M), (torch.rand(M) < 0.4).float()
+    dev = torch.device(DEV, 0)
+
+    def halve(logits):
+        logits.mul_(0.5)
+
+    got = _criterion_step(seq0, x, add, y, True, torch.ones((), device=dev), on_logits=halve)
+    want = _criterion_step(seq0, x, add, y, False, torch.ones((), device=dev), on_logits=halve)
+    plain = _criterion_step(seq0, x, add, y, False, torch.ones((), device=dev))
+    assert abs(float(want[0]) - float(plain[0])) > 1e-3, "halving the logits makes no difference: a vacuous test"
+    _same_step(got, want, seq0, M)
+
+
 def test_fused_tail_default_and_deterministic_weight_gradients_agree():
     """Default mode keeps a(z) and dz as the operand loads computed them and runs the three weight gradients as ONE
     multi-problem launch (split-K atomics); deterministic mode recomputes them inside its own kernel.  Same numbers up to

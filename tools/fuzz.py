@@ -389,6 +389,121 @@ def tail_case(seed):
                      f"pre-activations within {KINK:g} of the kink: {near_kink}, no assignment of them reproduces the fused result; seed={seed}")
 
 
+def tail_mixed_case(seed):
+    """tail_case with every hidden layer drawn on its own: a training-mode, frozen or absent BatchNorm, a Dropout in training
+    (p = 0, 0.3, 0.5), in eval or absent, a Linear with or without bias; depth 1-5, widths 8 U[1, 40], 2-300 rows, an input
+    that wants a gradient or not.  Same rule as tail_case (float64 with the kernels' masks, near-kink ReLU decisions
+    enumerated, 32 x the stock float32 error); also the running statistics and the seed word."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import copy
+
+    from tail_helpers import active_ps, build_tail, hidden_layers, tail_masks, zero_bias_names
+
+    from recsys_benchmark_amd import mlp as _mlp
+    from recsys_benchmark_amd.tail import fused_tail_plan
+
+    g = torch.Generator().manual_seed(seed)
+    ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))  # noqa: E731
+    M, K, depth = ri(2, 300), 8 * ri(1, 40), ri(1, 5)
+    layers = [(8 * ri(1, 40), ("train", "eval", None)[ri(0, 2)], (0.0, 0.3, 0.5, "eval", None)[ri(0, 4)], bool(ri(0, 1)))
+              for _ in range(depth)]
+    head_bias, x_grad = bool(ri(0, 1)), bool(ri(0, 1))
+    torch.manual_seed(seed)
+    seq = build_tail(K, layers, head_bias)
+    x, add, G = torch.randn(M, K, generator=g) * 0.7 + 0.2, torch.randn(M, generator=g), torch.randn(M, 1, generator=g)
+    seed_value = 1000 + seed
+    masks = tail_masks(seq, seed_value, M)
+    KINK = 3e-6
+
+    def reference(dtype, flips=None):
+        """flips: None, or a set of indices (in order of appearance) of near-kink elements whose ReLU decision is inverted"""
+        r = copy.deepcopy(seq).to(dtype)
+        xr, ar = x.detach().clone().to(dtype).requires_grad_(True), add.detach().clone().to(dtype).requires_grad_(True)
+        h, seen = xr, 0
+        hidden, head = hidden_layers(r)
+        for i, (_, lin, bn, _) in enumerate(hidden):
+            h = lin(h)
+            if bn is not None:
+                h = bn(h)                     # (in its own mode: batch statistics, or the frozen running ones)
+            near = (h.detach().abs() < KINK)
+            n_here = int(near.sum())
+            on = h.detach() > 0
+            if flips and n_here:
+                pos = near.flatten().nonzero().view(-1)
+                inv = torch.zeros(h.numel(), dtype=torch.bool)
+                for j in range(n_here):
+                    if seen + j in flips:
+                        inv[pos[j]] = True
+                on = on ^ inv.view_as(on)
+            seen += n_here
+            h = h * on.to(dtype) * masks[i].to(dtype)
+        o = head(h) + ar.view(-1, 1)
+        (o * G.to(dtype)).sum().backward()
+        return r, xr, o, seen
+
+    r32, x32, out32, _ = reference(torch.float32)
+    what = f"mixed tail M={M} K={K} layers={layers} head_bias={head_bias} x_grad={x_grad}"
+    was = _mlp.FUSED_TAIL
+    _mlp.FUSED_TAIL = True
+    try:
+        _mlp._seed_word(DEV).fill_(seed_value)
+        fs = copy.deepcopy(seq).to(DEV)
+        xd, ad = x.detach().to(DEV).requires_grad_(x_grad), add.detach().to(DEV).requires_grad_(True)
+        if fused_tail_plan(fs, xd, _mlp._groups(fs)) is None:
+            raise SystemExit(f"tail_mixed_case seed={seed}: the fused node refused {what}")
+        out = _mlp.run_tail(fs, xd, last_add=ad)
+        if type(out.grad_fn).__name__ != "FusedTailFnBackward":
+            raise SystemExit(f"tail_mixed_case seed={seed}: not the fused node for {what}")
+        (out * G.to(DEV)).sum().backward()
+    finally:
+        _mlp.FUSED_TAIL = was
+    drops = any(p > 0 for p in active_ps(seq))
+    if int(_mlp._seed_word(DEV)) != seed_value + (1 if drops else 0):
+        raise SystemExit(f"MISMATCH {what}: the seed word went from {seed_value} to {int(_mlp._seed_word(DEV))}; seed={seed}")
+    zero = zero_bias_names(seq)
+
+    def worst(ref):
+        """(name, fused error, stock error) of the tensor furthest beyond k x stock, errors relative to max|float64|"""
+        r64, x64, out64, _ = ref
+        p64, p32 = dict(r64.named_parameters()), dict(r32.named_parameters())
+        items = [("out", out, out64, out32)] + ([("dx", xd.grad, x64.grad, x32.grad)] if x_grad else [])
+        for name, q in fs.named_parameters():
+            if name in zero:
+                if q.grad is None or float(q.grad.abs().max()) != 0.0:
+                    return (name + " (exactly zero under a training-mode BatchNorm)", float("inf"), 0.0)
+                continue
+            items.append((name, q.grad, p64[name].grad, p32[name].grad))
+        b64, b32 = dict(r64.named_buffers()), dict(r32.named_buffers())
+        for name, q in fs.named_buffers():
+            if name.endswith("num_batches_tracked"):
+                if int(q) != int(b64[name]):
+                    return (name, float("inf"), 0.0)
+            else:
+                items.append((name, q, b64[name], b32[name]))
+        bad = None
+        for name, got, a64, a32 in items:
+            got, a64, a32 = got.detach().double().cpu(), a64.detach().double(), a32.detach().double()
+            scale = float(a64.abs().max()) + 1e-30
+            e_f, e_s = float((got - a64).abs().max()) / scale, float((a32 - a64).abs().max()) / scale
+            if e_f > max(32.0 * e_s, 1e-5 if a64.numel() > 8 else 1e-3) and (bad is None or e_f > bad[1]):
+                bad = (name, e_f, e_s)
+        return bad
+
+    ref0 = reference(torch.float64)
+    bad = worst(ref0)
+    if bad is None:
+        return
+    near_kink = ref0[3]
+    if 0 < near_kink <= 4:
+        for bits in range(1, 1 << near_kink):
+            alt = reference(torch.float64, {j for j in range(near_kink) if bits >> j & 1})
+            if worst(alt) is None:
+                ambiguous.append(seed)
+                return
+    raise SystemExit(f"MISMATCH {what} {bad[0]}: fused {bad[1]:.3e} vs stock float32 {bad[2]:.3e} (relative to max|ref|); "
+                     f"pre-activations within {KINK:g} of the kink: {near_kink}, no assignment of them reproduces the fused result; seed={seed}")
+
+
 if __name__ == "__main__":
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 150
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0          # python tools/fuzz.py 500 1000: seeds 1000 .. 1499 of every family
@@ -399,6 +514,7 @@ if __name__ == "__main__":
         lookup_case(500000 + s)
         crossnet_case(700000 + s)
         tail_case(900000 + s)
+        tail_mixed_case(1100000 + s)
         if s % 25 == 24:
             print(f"{s + 1} cases ok", flush=True)
     print(f"FUZZ_OK ({len(ambiguous)} tail cases matched float64 with a ReLU decision on the kink taken the other way: seeds {ambiguous[:8]})")
