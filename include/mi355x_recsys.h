@@ -523,6 +523,28 @@ MI_API int mi_csr_rows_fwd(const float *values, const int64_t *crow, const int64
                            const int64_t *ids, float *out, int64_t n, int32_t D,
                            int64_t N, int32_t *err, void *stream);
 
+/* ---- the CTR models served from a CSR-pruned table (inference only) --------------
+ * scripts/deepfm/infer_deepfm.py (_load_pep: PrunedEmbedding.from_other_emb inside a DeepFM).  The triple is trusted as
+ * mi_csr_rows_fwd trusts it; crow is int32 (crow_bytes = 4) or int64 (8), col one unsigned byte (col_bytes = 1) or
+ * int64 (8).  A row is densified as mi_csr_rows_fwd densifies it — zero, then out[col[j]] = values[j] for j ascending in
+ * crow[row] .. crow[row + 1]: a later duplicate wins, a column outside [0, D) is ignored — by the lanes of a row slot
+ * together: the entries are loaded once and passed round in order.  values / col may be NULL for a table without entries.
+ * mi_gather_fm_csr_fwd: DeepFM's lookup in ONE launch.  row = idx[b,f] + offsets[f] (offsets nullable); emb fp32[B,F,D]
+ *   the densified rows; yfm[b] = the FM second-order term of emb[b] + sum_f w1[row * ldw1] + bias[0] (bias nullable);
+ *   rows_out int64[B,F], nullable: the row ids.  A row outside [0, N) reads as a zero row, adds nothing to yfm and ORs
+ *   MI_IDX_OUT_OF_RANGE into *err.  D = 4 * 2^k <= 256 with emb 16-byte aligned runs the float4 kernels, anything else
+ *   the scalar ones: the same emb bits.
+ * mi_csr_rows_typed_fwd: the densify alone, out fp32[n,D] over the n flat ids.  offsets non-NULL (int64[F], n % F == 0):
+ *   row = ids[i] + offsets[i % F].  rows_out int64[n], nullable: the row ids.                                           */
+MI_API int mi_gather_fm_csr_fwd(const int64_t *idx, const int64_t *offsets, const float *values, const void *crow,
+                                int32_t crow_bytes, const void *col, int32_t col_bytes, const float *w1, int64_t ldw1,
+                                const float *bias, float *emb_out, float *yfm_out, int64_t *rows_out,
+                                int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, void *stream);
+MI_API int mi_csr_rows_typed_fwd(const float *values, const void *crow, int32_t crow_bytes, const void *col,
+                                 int32_t col_bytes, const int64_t *ids, const int64_t *offsets, int32_t F,
+                                 int64_t *rows_out, float *out, int64_t n, int32_t D, int64_t N, int32_t *err,
+                                 void *stream);
+
 /* ---- a9: DHE universal hash features ------------------------------------------
  * src/models/embeddings/dh_embedding.py:213-236:
  *   out[i,k] = 2*(((slopes[k]*(ids[i]+prefix+1)+bias[k]) mod primes[k]) mod m)/(m-1) - 1

@@ -10,8 +10,8 @@ from .ctr_metric import CTRMetric
 from .deepfm import DeepFM
 from .embeddings import IEmbedding, NAME_TO_CLS, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import RetrainOptEmbed as DeepFMRetrainOptEmbed, build_retrain_deepfm, evol_search_deepfm
-from .factory import (get_ctr_model, get_graph_model, load_ctr_model, load_graph_model, save_cf_emb_checkpoint,
-                      save_ctr_checkpoint)
+from .factory import (get_ctr_model, get_graph_model, load_ctr_model, load_graph_model, load_pruned_ctr_model,
+                      pruned_ctr_checkpoint, save_cf_emb_checkpoint, save_ctr_checkpoint)
 from .hccf import HCCFModelCore
 from .lightgcn import LightGCN, SingleLightGCN
 from .losses import BCEWithLogitsLoss
@@ -55,4 +55,5 @@ __all__ = [
     "BCEWithLogitsLoss", "NeuMF", "ModelFlag", "prune", "prune_table", "to_pruned_tables", "evaluate_pruned", "search_min_item",
     "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "CTRMetric",
     "DeviceCFGraphDataset", "DeviceCFLoader", "DeviceCFTestDataset", "DeviceCFTestLoader", "DeviceTruth",
+    "pruned_ctr_checkpoint", "load_pruned_ctr_model",
 ]

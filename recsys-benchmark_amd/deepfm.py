@@ -14,6 +14,7 @@ What runs where:
          mi_gather_fm_{soft,elemmask}_{fwd,bwd_rows}       (PEP: the threshold search, the retraining table), or
          mi_gather_fm_dual_{fwd,bwd_rows,finish}           (QR add / mult, CERP, CERP retrain), or
          mi_gather_fm_qat_{fwd,bwd_rows} / _quant_fwd      (QAT; the post-training-quantised tables in eval), or
+         mi_gather_fm_csr_fwd                              (a CSR-pruned table, wide or compact indices; inference), or
          IEmbedding.forward + mi_fm_fwd / mi_fm_bwd        (compressed tables)
   the MLP tail (a real GEMM): the library's own fp32-MFMA products with BatchNorm1d / ReLU / Dropout in
       their operand loads and epilogues (tail.py, csrc/tail.hip) in training, eval() and no-BatchNorm stacks alike; the
@@ -25,8 +26,8 @@ from typing import Any, Dict, List, Optional, Union, cast
 import torch
 from torch import nn
 
-from . import _kernels, quant_fm
-from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
+from . import _kernels, csr_fm, quant_fm
+from .embeddings import IEmbedding, PrunedEmbedding, VanillaEmbedding, get_embedding
 from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
 from .embeddings.cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
 from .embeddings.pep_embedding import PepEmbeeding, RetrainPepEmbedding
@@ -163,6 +164,14 @@ class DeepFM(nn.Module):
                 quant = emb_mod.fm_quant(x)
                 if quant is not None:
                     return quant_fm.gather_fm_quant(x, self.offsets, w1=self.fc.weight, bias=self._bias, **quant)
+        # A CSR-pruned table (inference only): the row densify inside the same launch (mi_gather_fm_csr_fwd), for wide and
+        # compact index buffers alike.  The guards are the PTQ launch's: hooks, a first-order term or bias that wants a
+        # gradient, bag modes and CPU tables keep the path below.
+        if (isinstance(emb_mod, PrunedEmbedding) and not _hooked(emb_mod)
+                and not (torch.is_grad_enabled() and (self.fc.weight.requires_grad or self._bias.requires_grad))):
+            csr = emb_mod.fm_csr(x)
+            if csr is not None:
+                return csr_fm.gather_fm_csr(x, self.offsets, w1=self.fc.weight, bias=self._bias, **csr)
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

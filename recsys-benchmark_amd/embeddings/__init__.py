@@ -51,6 +51,9 @@ OUT_OF_SCOPE = {
                                "deepfm_opt_embed.build_retrain_deepfm(field_dims, model_config, mask_e, mask_d), which "
                                "attaches a deepfm_opt_embed.RetrainOptEmbed to a DeepFM (the supernet is 'deepfm_optembed', "
                                "the CF retraining table 'optembed_retrain')",
+    "pruned-sparse-csr": "a CSR table comes out of a deployed checkpoint, not out of a config: use "
+                         "recsys_benchmark_amd.load_pruned_ctr_model(checkpoint_or_path), which attaches "
+                         "PrunedEmbedding.from_weight(embedding.sparse_w) to the loaded DeepFM / DCN_Mix",
     "tt_emb": "FBTT-Embedding CUDA extension, not in the reference tree (SURVEY.md §2.3 K3-K12); use 'tt_emb_torch'",
 }
 

@@ -74,6 +74,60 @@ def load_ctr_model(model_config, checkpoint, strict=True, *, empty_embedding=Fal
                   lambda cls, cfg: cls.load(checkpoint, strict, empty_embedding=empty_embedding))
 
 
+PRUNED_CSR = "pruned-sparse-csr"     # embedding_config name of the reference's deployed checkpoints (scripts/raspberry/postprocess_weight.py)
+
+
+def _own_checkpoint(checkpoint) -> dict:
+    """The checkpoint (a dict or a path) with dicts of its own down to the embedding config: loading pops from them."""
+    saved = torch.load(checkpoint, map_location="cpu") if isinstance(checkpoint, (str, os.PathLike)) else checkpoint
+    saved = dict(saved)
+    saved["model_config"] = dict(saved["model_config"])
+    if isinstance(saved["model_config"].get("embedding_config"), dict):
+        saved["model_config"]["embedding_config"] = dict(saved["model_config"]["embedding_config"])
+    saved["state_dict"] = dict(saved["state_dict"])
+    return saved
+
+
+def pruned_ctr_checkpoint(checkpoint: dict, weight: Optional[torch.Tensor] = None) -> dict:
+    """scripts/raspberry/postprocess_weight.py: the checkpoint of a DeepFM / DCN_Mix with its table stored as CSR — the
+    state_dict loses its `embedding.*` keys and gains `embedding.sparse_w`, the to_sparse_csr() of the loaded model's
+    embedding.get_weight() (or of `weight`, when given: a pruned table, say), and the embedding config becomes
+    {"name": "pruned-sparse-csr"}.  The caller's dict is not modified."""
+    saved = _own_checkpoint(checkpoint)
+    if weight is None:
+        source = _own_checkpoint(checkpoint)
+        model = load_ctr_model(source["model_config"], source)
+        with torch.no_grad():
+            weight = model.embedding.get_weight()
+    weight = weight.detach()
+    sparse_w = weight if weight.layout == torch.sparse_csr else weight.to_sparse_csr()
+    state = {name: t for name, t in saved["state_dict"].items() if "embedding." not in name}
+    state["embedding.sparse_w"] = sparse_w
+    saved["state_dict"] = state
+    saved["model_config"]["embedding_config"] = {"name": PRUNED_CSR}
+    return saved
+
+
+def load_pruned_ctr_model(checkpoint, compact: bool = False):
+    """`_load_pep` of scripts/deepfm/infer_deepfm.py for DeepFM and DCN_Mix (the kind is model_config["name"], as in
+    load_ctr_model): a "pruned-sparse-csr" checkpoint is loaded without an embedding and gets
+    PrunedEmbedding.from_weight(embedding.sparse_w); any other checkpoint is loaded (strict=False) and its table replaced
+    by PrunedEmbedding.from_other_emb.  compact: one-byte columns and int32 row pointers.  `checkpoint`: a dict (left as it
+    was) or a path."""
+    from .embeddings import PrunedEmbedding
+
+    saved = _own_checkpoint(checkpoint)
+    emb_config = saved["model_config"].get("embedding_config") or {}
+    if emb_config.get("name") != PRUNED_CSR:
+        model = load_ctr_model(saved["model_config"], saved, strict=False)
+        model.embedding = PrunedEmbedding.from_other_emb(model.embedding, compact=compact)
+        return model
+    sparse_w = saved["state_dict"].pop("embedding.sparse_w")
+    model = load_ctr_model(saved["model_config"], saved, empty_embedding=True)
+    model.register_module("embedding", PrunedEmbedding.from_weight(sparse_w, compact=compact))
+    return model
+
+
 def load_graph_model(checkpoint_path: str, strict=True):
     checkpoint = torch.load(checkpoint_path, map_location="cpu")
     model = get_graph_model(checkpoint["num_users"], checkpoint["num_items"], checkpoint["model_config"])

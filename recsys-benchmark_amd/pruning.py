@@ -152,30 +152,44 @@ def _pruned_csr(weight: torch.Tensor, p: float, min_item: int = 0):
 
 
 # ---- serving and the min-item search --------------------------------------------------------------------------------
+def _is_ctr(model) -> bool:
+    from .dcn import DCN_Mix, DCNv2
+    from .deepfm import DeepFM
+
+    return isinstance(model, (DeepFM, DCN_Mix, DCNv2))
+
+
 def _table_slots(model):
-    """(owner module, attribute name) of every embedding table of a LightGCN / SingleLightGCN / NeuMF."""
+    """(owner module, attribute name) of every embedding table of a LightGCN / SingleLightGCN / NeuMF, or the one shared
+    table of a DeepFM / DCN_Mix / DCNv2."""
     from .lightgcn import LightGCN, SingleLightGCN
     from .neumf import NeuMF
 
+    if _is_ctr(model):
+        return [(model, "embedding")]
     if isinstance(model, LightGCN):
         return [(model, "user_emb_table"), (model, "item_emb_table")]
     if isinstance(model, SingleLightGCN):
         return [(model, "emb_table")]
     if isinstance(model, NeuMF):
         return [(part, name) for part in (model._gmf, model._mlp) for name in ("user_emb_table", "item_emb_table")]
-    raise TypeError(f"to_pruned_tables takes a LightGCN, SingleLightGCN or NeuMF, got {type(model).__name__}")
+    raise TypeError("to_pruned_tables takes a LightGCN, SingleLightGCN, NeuMF, DeepFM, DCN_Mix or DCNv2, got "
+                    f"{type(model).__name__}")
 
 
 @torch.no_grad()
-def to_pruned_tables(model, p: float = 0.0, min_item: int = 0):
+def to_pruned_tables(model, p: float = 0.0, min_item: int = 0, compact: bool = False):
     """Replace each table of the model by a PrunedEmbedding (CSR) of its current weight — what `_load_pep` of
-    scripts/lightgcn/infer_lightgcn.py:224-247 does — pruned by (p, min_item) on the way when p > 0.  The model then
+    scripts/lightgcn/infer_lightgcn.py:224-247 and scripts/deepfm/infer_deepfm.py does — pruned by (p, min_item) on the
+    way when p > 0.  A CTR model's table is taken through get_weight(), whatever its kind (the reference's
+    `from_other_emb`).  compact: one-byte columns and int32 row pointers (PrunedEmbedding.compact_()).  The model then
     serves through the usual validation and scoring paths.  Returns the model."""
     from .embeddings import PrunedEmbedding
 
     for owner, name in _table_slots(model):
         table = getattr(owner, name)
-        setattr(owner, name, PrunedEmbedding.from_pruned(table, p, min_item, mode=getattr(table, "_mode", None)))
+        setattr(owner, name, PrunedEmbedding.from_pruned(table, p, min_item, mode=getattr(table, "_mode", None),
+                                                         compact=compact))
     if hasattr(model, "clear_cache"):
         model.clear_cache()
     return model
@@ -185,12 +199,16 @@ def _default_validate(model) -> Callable:
     from . import trainer
     from .neumf import NeuMF
 
+    if _is_ctr(model):
+        return trainer.validate_epoch
     return trainer.validate_epoch_nmf if isinstance(model, NeuMF) else trainer.validate_epoch_cf
 
 
 def _default_keys(model, state) -> List[str]:
     from .neumf import NeuMF
 
+    if _is_ctr(model):                                         # scripts/deepfm/run_l2_benchmark.py: the embedding's entries
+        return ["embedding." + k for k in model.embedding.state_dict()]
     if isinstance(model, NeuMF):
         return [k for k in state if "emb_table" in k]         # scripts/cf_train/run_mag_prune.py:69-73
     return list(state)                                         # scripts/lightgcn/run_mag_prune.py:63-69: every entry
@@ -231,10 +249,13 @@ class _Candidates:
 def _validate_candidate(cands: _Candidates, p, min_item, val_loader, train_dataset, device, validate) -> float:
     try:
         cands.apply(p, min_item)
-        metrics = validate(train_dataset, val_loader, cands.model, device, metrics=["ndcg", "recall"])
+        if _is_ctr(cands.model):
+            score = validate(val_loader, cands.model, device)["auc"]
+        else:
+            score = validate(train_dataset, val_loader, cands.model, device, metrics=["ndcg", "recall"])["ndcg"]
     finally:
         cands.restore()
-    return metrics["ndcg"]
+    return score
 
 
 def evaluate_pruned(model, p: float, min_item: int, val_loader, train_dataset, device="cuda",
@@ -243,8 +264,11 @@ def evaluate_pruned(model, p: float, min_item: int, val_loader, train_dataset, d
     keys=None: every state entry for a LightGCN / SingleLightGCN (all must be 2-D, as the reference asserts), the
     entries whose name contains `emb_table` for a NeuMF.  validate=None: trainer.validate_epoch_cf or
     trainer.validate_epoch_nmf by model type; a callable is called as
-    validate(train_dataset, val_loader, model, device, metrics=["ndcg", "recall"]).  The model's state is bit-identical
-    afterwards, also when validation raises."""
+    validate(train_dataset, val_loader, model, device, metrics=["ndcg", "recall"]).
+    A DeepFM / DCN_Mix / DCNv2 (scripts/deepfm/run_l2_benchmark.py): keys=None is every entry of
+    model.embedding.state_dict() (all must be 2-D), validate=None is trainer.validate_epoch, a callable is called as
+    validate(val_loader, model, device), and the "auc" of its result is returned; train_dataset is ignored (None will do).
+    The model's state is bit-identical afterwards, also when validation raises."""
     validate = _default_validate(model) if validate is None else validate
     return _validate_candidate(_Candidates(model, keys), p, min_item, val_loader, train_dataset, device, validate)
 
@@ -300,6 +324,7 @@ def search_min_item(model, p: float, hidden_size: int, val_loader=None, train_da
                     evaluate: Optional[Callable[[int], float]] = None) -> int:
     """`bin_search` (mode="binary") / `run_all` (mode="all") of the two run_mag_prune.py scripts, with the reference's
     probe order and its 1-based return value: the floor to use is `result - 1`, as both scripts do.
+    A DeepFM / DCN_Mix / DCNv2 is scored by its validation AUC (evaluate_pruned), train_dataset ignored.
     evaluate: a callable floor -> score replacing the validation of a candidate (the model is then not touched);
     otherwise every candidate is `evaluate_pruned`, the original tables being kept on the device once for the search."""
     if mode not in ("binary", "all"):
