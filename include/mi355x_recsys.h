@@ -723,6 +723,39 @@ MI_API int mi_gemm_f32_k_groups(const float *A, const float *B, float *C, int32_
                                 int32_t lda, int32_t ldb, int32_t ldc, int64_t sC, const int64_t *kseg,
                                 int32_t nseg, void *stream);
 
+/* ---- a10, LFU row cache: the `tt_emb` table (TTEmbeddingBag with use_cache) ---------------------------
+ * Buffers of src/models/embeddings/tt_embedding_ops.py:585-649: hashtbl int64[S] (ids, -1 empty), cache_freq int64[S],
+ * cache_state int32[S] (row of cache_weight fp32[C, D] holding the slot's id, or -1).  The FBTT kernels behind
+ * update_cache_state / preprocess_indices_sync / cache_forward are not in the reference tree; the probe rule is this
+ * build's own: open addressing, start slot id % S, linear probing, a probe stops at the id, at an empty slot or after
+ * MI_TT_CACHE_PROBE_BOUND probes — the same bound for insert and find.  S >= N is direct addressing (slot == id).
+ *   mi_tt_cache_probe_count: for every lookup, in ONE launch: find or insert idx[i] (64-bit compare-and-swap on an empty
+ *     slot; a loser re-reads the slot it lost), cache_freq[slot] += 1 (the lanes of a wave holding the same id elect one
+ *     adder that carries their number; integer atomics only), loc[i] = cache_state[slot], or -1 when the id found no slot
+ *     within the bound, is not cached, names a row >= cache_size, or *warmup != 0 (warmup: device word, nullable).  Ids
+ *     outside [0, N) count nothing, get loc -1 and set MI_IDX_OUT_OF_RANGE.
+ *   mi_tt_cache_rehash: inserts every src_ids[i] >= 0 by the rule above and stores (src_freq[i], src_state[i]) at its slot;
+ *     the caller pre-fills hashtbl / cache_state with -1 and cache_freq with 0.  The sources must not alias the
+ *     destinations.  An id that finds no slot within the bound is dropped (untracked).
+ *   mi_tt_cached_fwd / mi_tt_cached_bwd: mi_tt_fwd / mi_tt_bwd where a lookup with 0 <= loc[i] < cache_size copies its
+ *     cached row forward and adds nothing to gcores backward; every other lookup runs mi_tt_fwd / mi_tt_bwd's statements
+ *     in their order (same bits forward).  cache_weight's gradient is the caller's (rows of g added at loc).          */
+#define MI_TT_CACHE_PROBE_BOUND 64
+MI_API int mi_tt_cache_probe_count(const int64_t *idx, int64_t n, int64_t N, int64_t *hashtbl, int64_t *cache_freq,
+                                   const int32_t *cache_state, int64_t hashtbl_size, int32_t cache_size,
+                                   const int32_t *warmup, int32_t *loc, int32_t *err, void *stream);
+MI_API int mi_tt_cache_rehash(const int64_t *src_ids, const int64_t *src_freq, const int32_t *src_state,
+                              int64_t n_src, int64_t *hashtbl, int64_t *cache_freq, int32_t *cache_state,
+                              int64_t hashtbl_size, void *stream);
+MI_API int mi_tt_cached_fwd(const int64_t *idx, const int32_t *loc, const float *cache_weight, int32_t cache_size,
+                            const float *const *cores, int32_t ncores, const int32_t *p_shapes,
+                            const int32_t *q_shapes, const int32_t *ranks, float *out, int64_t n, int32_t D,
+                            int64_t N, int32_t *err, void *stream);
+MI_API int mi_tt_cached_bwd(const int64_t *idx, const int32_t *loc, int32_t cache_size, const float *g_out,
+                            const float *const *cores, float *const *gcores, int32_t ncores,
+                            const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks, int64_t n,
+                            int32_t D, int64_t N, void *stream);
+
 /* ---- a12/a13: fp32 MFMA GEMM with fused CrossNet epilogues ------------------
  * C[M,N] = epi( sum_{g<kgroups} opA(A + g*gA)[M,K] . opB(B + g*gB)[K,N] ), batched over `batch`
  * with element strides sA/sB/sC (and sR1/sR2/sC2).  transA=0: A[m*lda+k], 1: A[k*lda+m];

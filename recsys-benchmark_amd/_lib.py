@@ -121,6 +121,10 @@ SIGNATURES = {
     "mi_tt_last_bwd": [_p, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _i64, _p, _p, _i32, _p, _i64, _p],
     "mi_tt_plan_level": [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p, _i32, _p],
     "mi_segment_sum": [_p, _i64, _i32, _p, _i32, _p, _i64, _p],
+    "mi_tt_cache_probe_count": [_p, _i64, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p, _p],
+    "mi_tt_cache_rehash": [_p, _p, _p, _i64, _p, _p, _p, _i64, _p],
+    "mi_tt_cached_fwd": [_p, _p, _p, _i32, _p, _i32, _p, _p, _p, _p, _i64, _i32, _i64, _p, _p],
+    "mi_tt_cached_bwd": [_p, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _i64, _i32, _i64, _p],
     "mi_rowsq_fwd": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p],
     "mi_rowsq_fwd_armed": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p],
     "mi_rowsq_bwd": [_p, _p, _p, _p, _p, _p, _i64, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],

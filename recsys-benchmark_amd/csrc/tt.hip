@@ -69,13 +69,30 @@ __device__ __forceinline__ void tt_forward_levels(const TTDesc &t, const int *di
   }
 }
 
+// The LFU row cache of `tt_emb` (tt_cache.hip): loc[i] >= 0 names the row of cache_weight[C, D] that holds lookup i's
+// row uncompressed.  CACHED instantiations copy that row forward and leave the cores' gradients alone backward; every
+// other lookup runs the same statements as the plain instantiation, in the same order.
+struct CacheRows {
+  const int32_t *loc;
+  const float *weight;
+  int32_t C;
+};
+
+template <bool CACHED>
 __global__ __launch_bounds__(kBlock) void k_tt_fwd(const int64_t *__restrict__ idx, TTDesc t, float *__restrict__ out,
-                                                   int64_t n, int D, int64_t N, int *err) {
+                                                   int64_t n, int D, int64_t N, int *err, CacheRows cache) {
   extern __shared__ float smem[];
   int dig[kMaxCores];
   int bad = 0;
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
     const bool ok = tt_digits(idx[i], t, N, dig);
+    if constexpr (CACHED) {
+      const int32_t l = cache.loc[i];
+      if (ok && (uint32_t)l < (uint32_t)cache.C) {
+        for (int e = threadIdx.x; e < D; e += blockDim.x) out[i * D + e] = cache.weight[(int64_t)l * D + e];
+        continue;
+      }
+    }
     if (!ok) {
       bad = 1;
       for (int e = threadIdx.x; e < D; e += blockDim.x) out[i * D + e] = 0.f;
@@ -89,8 +106,10 @@ __global__ __launch_bounds__(kBlock) void k_tt_fwd(const int64_t *__restrict__ i
   if (bad && err && threadIdx.x == 0) atomicOr(err, MI_IDX_OUT_OF_RANGE);
 }
 
+template <bool CACHED>
 __global__ __launch_bounds__(kBlock) void k_tt_bwd(const int64_t *__restrict__ idx, TTDesc t,
-                                                   const float *__restrict__ g, int64_t n, int D, int64_t N) {
+                                                   const float *__restrict__ g, int64_t n, int D, int64_t N,
+                                                   CacheRows cache) {
   extern __shared__ float smem[];
   float *dA = smem + t.lvl_total;       // gradient of the current level
   float *dB = dA + t.lvl_max;           // gradient of the previous level
@@ -98,6 +117,9 @@ __global__ __launch_bounds__(kBlock) void k_tt_bwd(const int64_t *__restrict__ i
   const int tid = threadIdx.x, nt = blockDim.x;
   for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
     if (!tt_digits(idx[i], t, N, dig)) continue;
+    if constexpr (CACHED) {
+      if ((uint32_t)cache.loc[i] < (uint32_t)cache.C) continue;
+    }
     tt_forward_levels(t, dig, smem);
     for (int e = tid; e < D; e += nt) dA[e] = g[i * D + e];
     __syncthreads();
@@ -161,13 +183,10 @@ int fill_desc(TTDesc &t, int32_t ncores, const int32_t *p, const int32_t *q, con
   return MI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mi_tt_fwd(const int64_t *idx, const float *const *cores /*host array of device pointers*/, int32_t ncores,
-              const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks /*host, ncores+1*/, float *out,
-              int64_t n, int32_t D, int64_t N, int32_t *err, void *stream) {
+template <bool CACHED>
+int launch_fwd(const int64_t *idx, const float *const *cores, int32_t ncores, const int32_t *p_shapes,
+               const int32_t *q_shapes, const int32_t *ranks, float *out, int64_t n, int32_t D, int64_t N, int32_t *err,
+               void *stream, CacheRows cache) {
   if (n < 0 || D <= 0) return MI_ERR_INVALID_ARG;
   TTDesc t;
   int rc = fill_desc(t, ncores, p_shapes, q_shapes, ranks, cores, nullptr, D);
@@ -178,16 +197,17 @@ int mi_tt_fwd(const int64_t *idx, const float *const *cores /*host array of devi
   if (shmem > 160 * 1024) return MI_ERR_UNSUPPORTED;
   const int grid = (int)(n < 4096 ? n : 4096);
   hipEvent_t ea, eb;
-  if (mi::prof_acquire("tt_fwd", &ea, &eb))
-    hipExtLaunchKernelGGL(k_tt_fwd, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, ea, eb, 0, idx, t, out, n, D, N, err);
+  if (mi::prof_acquire(CACHED ? "tt_cached_fwd" : "tt_fwd", &ea, &eb))
+    hipExtLaunchKernelGGL(k_tt_fwd<CACHED>, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, ea, eb, 0, idx, t, out, n, D, N, err, cache);
   else
-    hipLaunchKernelGGL(k_tt_fwd, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, idx, t, out, n, D, N, err);
+    hipLaunchKernelGGL(k_tt_fwd<CACHED>, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, idx, t, out, n, D, N, err, cache);
   return launch_status();
 }
 
-int mi_tt_bwd(const int64_t *idx, const float *g_out, const float *const *cores, float *const *gcores,
-              int32_t ncores, const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks, int64_t n,
-              int32_t D, int64_t N, void *stream) {
+template <bool CACHED>
+int launch_bwd(const int64_t *idx, const float *g_out, const float *const *cores, float *const *gcores, int32_t ncores,
+               const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks, int64_t n, int32_t D, int64_t N,
+               void *stream, CacheRows cache) {
   if (n < 0 || D <= 0 || !gcores) return MI_ERR_INVALID_ARG;
   TTDesc t;
   int rc = fill_desc(t, ncores, p_shapes, q_shapes, ranks, cores, gcores, D);
@@ -200,11 +220,43 @@ int mi_tt_bwd(const int64_t *idx, const float *g_out, const float *const *cores,
   if (shmem > 160 * 1024) return MI_ERR_UNSUPPORTED;
   const int grid = (int)(n < 4096 ? n : 4096);
   hipEvent_t ea, eb;
-  if (mi::prof_acquire("tt_bwd", &ea, &eb))
-    hipExtLaunchKernelGGL(k_tt_bwd, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, ea, eb, 0, idx, t, g_out, n, D, N);
+  if (mi::prof_acquire(CACHED ? "tt_cached_bwd" : "tt_bwd", &ea, &eb))
+    hipExtLaunchKernelGGL(k_tt_bwd<CACHED>, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, ea, eb, 0, idx, t, g_out, n, D, N, cache);
   else
-    hipLaunchKernelGGL(k_tt_bwd, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, idx, t, g_out, n, D, N);
+    hipLaunchKernelGGL(k_tt_bwd<CACHED>, dim3(grid), dim3(kBlock), shmem, (hipStream_t)stream, idx, t, g_out, n, D, N, cache);
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_tt_fwd(const int64_t *idx, const float *const *cores /*host array of device pointers*/, int32_t ncores,
+              const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks /*host, ncores+1*/, float *out,
+              int64_t n, int32_t D, int64_t N, int32_t *err, void *stream) {
+  return launch_fwd<false>(idx, cores, ncores, p_shapes, q_shapes, ranks, out, n, D, N, err, stream, CacheRows{});
+}
+
+int mi_tt_bwd(const int64_t *idx, const float *g_out, const float *const *cores, float *const *gcores,
+              int32_t ncores, const int32_t *p_shapes, const int32_t *q_shapes, const int32_t *ranks, int64_t n,
+              int32_t D, int64_t N, void *stream) {
+  return launch_bwd<false>(idx, g_out, cores, gcores, ncores, p_shapes, q_shapes, ranks, n, D, N, stream, CacheRows{});
+}
+
+int mi_tt_cached_fwd(const int64_t *idx, const int32_t *loc, const float *cache_weight, int32_t cache_size,
+                     const float *const *cores, int32_t ncores, const int32_t *p_shapes, const int32_t *q_shapes,
+                     const int32_t *ranks, float *out, int64_t n, int32_t D, int64_t N, int32_t *err, void *stream) {
+  if (cache_size < 0 || (n > 0 && (!loc || (cache_size > 0 && !cache_weight)))) return MI_ERR_INVALID_ARG;
+  return launch_fwd<true>(idx, cores, ncores, p_shapes, q_shapes, ranks, out, n, D, N, err, stream,
+                          CacheRows{loc, cache_weight, cache_size});
+}
+
+int mi_tt_cached_bwd(const int64_t *idx, const int32_t *loc, int32_t cache_size, const float *g_out,
+                     const float *const *cores, float *const *gcores, int32_t ncores, const int32_t *p_shapes,
+                     const int32_t *q_shapes, const int32_t *ranks, int64_t n, int32_t D, int64_t N, void *stream) {
+  if (cache_size < 0 || (n > 0 && !loc)) return MI_ERR_INVALID_ARG;
+  return launch_bwd<true>(idx, g_out, cores, gcores, ncores, p_shapes, q_shapes, ranks, n, D, N, stream,
+                          CacheRows{loc, nullptr, cache_size});
 }
 
 }  // extern "C"

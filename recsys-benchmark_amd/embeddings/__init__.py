@@ -2,10 +2,9 @@
 
 Same registry keys, same `get_embedding(embedding_config, field_dims, hidden_size,
 mode, field_name)` contract (config deep-copied, "name" popped and restored,
-`field_name` forwarded to pep*/cerp* classes).  Keys whose class is outside the
-hot-path scope (the FBTT CUDA extension) or that cannot be built from a config alone (DeepFM's OptEmbed
-retraining table, which needs the searched masks: deepfm_opt_embed.build_retrain_deepfm) raise NotImplementedError with
-the reason instead of silently substituting something.
+`field_name` forwarded to pep*/cerp* classes).  Keys that cannot be built from a config alone (DeepFM's OptEmbed
+retraining table, which needs the searched masks: deepfm_opt_embed.build_retrain_deepfm; a CSR table, which comes out of
+a checkpoint) raise NotImplementedError with the reason instead of silently substituting something.
 """
 import copy
 from typing import Any, Dict, List, Optional, Tuple, Union
@@ -21,7 +20,7 @@ from .pep_embedding import PepEmbeeding, RetrainPepEmbedding
 from .pruned_embedding import PrunedEmbedding
 from .qat_emb import QAT_EmbInt
 from .qr_embedding import QRHashingEmbedding
-from .tensortrain_embeddings import TTRecTorch
+from .tensortrain_embeddings import TTEmbedding, TTRecTorch
 
 # (class, extra constructor arguments forced by the key, whether the class takes `field_name`)
 _REGISTRY = (
@@ -33,6 +32,7 @@ _REGISTRY = (
     ("cerp", CerpEmbedding, {}, True),
     ("cerp_retrain", RetrainCerpEmbedding, {}, True),
     ("tt_emb_torch", TTRecTorch, {}, False),
+    ("tt_emb", TTEmbedding, {}, False),                                 # the same table behind an LFU row cache
     ("qat", QAT_EmbInt, {}, False),
     ("deepfm_optembed", DeepFMOptEmbed, {}, False),
     ("deepfm_optembed_d", DeepFMOptEmbed, {"t_init": None}, False),   # mask E disabled (reference __init__.py:65-67)
@@ -54,7 +54,6 @@ OUT_OF_SCOPE = {
     "pruned-sparse-csr": "a CSR table comes out of a deployed checkpoint, not out of a config: use "
                          "recsys_benchmark_amd.load_pruned_ctr_model(checkpoint_or_path), which attaches "
                          "PrunedEmbedding.from_weight(embedding.sparse_w) to the loaded DeepFM / DCN_Mix",
-    "tt_emb": "FBTT-Embedding CUDA extension, not in the reference tree (SURVEY.md §2.3 K3-K12); use 'tt_emb_torch'",
 }
 
 
@@ -89,4 +88,4 @@ def detect_special(config: Dict[str, Any]) -> Tuple[Optional[str], bool]:
 
 
 __all__ = ["IEmbedding", "VanillaEmbedding", "OptEmbed", "RetrainOptEmbed", "QRHashingEmbedding", "CerpEmbedding", "RetrainCerpEmbedding",
-           "DHEmbedding", "PrunedEmbedding", "DeepFMOptEmbed", "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "TTRecTorch", "PepEmbeeding", "RetrainPepEmbedding", "NAME_TO_CLS", "get_embedding", "detect_special"]
+           "DHEmbedding", "PrunedEmbedding", "DeepFMOptEmbed", "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "TTRecTorch", "TTEmbedding", "PepEmbeeding", "RetrainPepEmbedding", "NAME_TO_CLS", "get_embedding", "detect_special"]

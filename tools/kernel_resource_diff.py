@@ -8,7 +8,8 @@ shared walker did not leak into the instantiations that do not set it (DESIGN.md
     hipcc (same flags) -c recsys-benchmark_amd/csrc/gather_fm.hip -o this.o 2> this.txt
     python tools/kernel_resource_diff.py parent.txt this.txt
 
-Kernels are matched by their DEMANGLED name (an empty template parameter pack changes the mangled one only).  Prints
+Kernels are matched by their DEMANGLED name (an empty template parameter pack changes the mangled one only); a plain kernel
+that the second build turned into a template on one bool flag is matched with its `<false>` instantiation ("AS" line).  Prints
 every kernel of the first build whose VGPR, SGPR, AGPR, scratch, LDS or occupancy figure moved or that is gone, then a
 count per kernel family; exit status 1 if anything moved.
 """
@@ -42,16 +43,28 @@ def family(name):
     return re.sub(r"[<(].*", "", re.sub(r"^void ", "", name))
 
 
+def renamed(name, b):
+    """A plain kernel of the first build that became a template on ONE bool flag in the second (k<false> keeps the old body,
+    possibly behind more parameters): the second build's only `family<false>(...)`, or None."""
+    if "<" in family(name) or re.match(r"^(void )?[\w:]+<", name):
+        return None
+    hits = [n for n in b if re.sub(r"^void ", "", n).startswith(family(name) + "<false>(")]
+    return hits[0] if len(hits) == 1 else None
+
+
 def main():
     a, b = parse(sys.argv[1]), parse(sys.argv[2])
     fam, moved = {}, 0
     for name in sorted(a):
         f = fam.setdefault(family(name), [0, 0])
         f[0] += 1
-        if name not in b:
+        other = name if name in b else renamed(name, b)
+        if other is None:
             print("GONE ", name)
         else:
-            d = [(k, a[name].get(k), b[name].get(k)) for k in KEYS if a[name].get(k) != b[name].get(k)]
+            d = [(k, a[name].get(k), b[other].get(k)) for k in KEYS if a[name].get(k) != b[other].get(k)]
+            if other != name:
+                print("AS   ", name, "->", other)
             if not d:
                 continue
             print("MOVED", name, d)
