@@ -45,6 +45,42 @@ def _i64c(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.int64).contiguous()
 
 
+def _lookup_operands(idx, offsets, w1, N: Optional[int] = None):
+    """(idx int64[B, F], offsets int64[F] or None, w1 and its row stride, N) as the fused lookup launches read them: w1
+    ([N], [N, 1], or a column of a packed table) in place where its rows are evenly strided, one weight per row of the
+    N-row embedding table (N=None: the first-order table says how many rows there are)."""
+    idx = _i64c(idx)
+    if offsets is not None:
+        offsets = _i64c(offsets.reshape(-1))
+    if idx.dim() != 2 or (offsets is not None and idx.shape[1] != offsets.numel()):
+        raise ValueError(f"idx must be [B, F] with one offset per field, got {tuple(idx.shape)}")
+    w1c, ldw1 = _row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
+    if N is None:
+        N = int(w1c.shape[0])
+    if w1c.shape[0] != N or w1c.numel() != N:
+        raise ValueError("first-order table must have one weight per embedding row")
+    return idx, offsets, w1c, ldw1, N
+
+
+def _upstream(g_emb, g_y, B: int, dev):
+    """(g_emb, g_y) as the backward launches read them: fp32 and contiguous, zeros for a y_fm that nothing used (the
+    forwards switch gradient materialisation off), None for an emb that nothing used."""
+    g_y = torch.zeros((B,), dtype=torch.float32, device=dev) if g_y is None else _f32c(g_y)
+    return (None if g_emb is None else _f32c(g_emb)), g_y
+
+
+def _bias_grad(gb, g_y, B: int, launched: bool = True):
+    """The bias gradient (sum of g_y) of a lookup's backward.  gb (fp32 [1], None when it is not wanted) rides in the
+    backward launch; a backward that launched nothing sums g_y itself, and a launch over no sample wrote nothing."""
+    if gb is None:
+        return None
+    if not launched:
+        return g_y.sum().view(1)
+    if B == 0:
+        gb.zero_()
+    return gb
+
+
 def _coo(rows: torch.Tensor, vals: torch.Tensor, shape) -> torch.Tensor:
     return torch.sparse_coo_tensor(rows.view(1, -1), vals, shape, check_invariants=False)
 
@@ -75,10 +111,18 @@ def sort_field_rows(rows_flat: torch.Tensor, N: int):
         return None
     rows, offsets, n_rows = entry
     B, F = rows.shape
-    if rows_flat.numel() != B * F or n_rows != N or B > 65536 or N >= 2**32 - 2 or B == 0:
+    if rows_flat.numel() != B * F or n_rows != N:
+        return None
+    return _sort_fields(rows, offsets, N, B, F)
+
+
+def _sort_fields(rows: torch.Tensor, offsets: torch.Tensor, N: int, B: int, F: int):
+    """(sorted ids, permutation), both flat, of contiguous ids rows[B, F] = x + offsets (ascending offsets) sorted field by
+    field in LDS (mi_sort_field_rows), or None beyond that sort's limits."""
+    if not 0 < B <= 65536 or N >= 2**32 - 2:
         return None
     lib = _lib.load()
-    rows_sorted, perm = torch.empty_like(rows_flat), torch.empty_like(rows_flat)
+    rows_sorted, perm = rows.new_empty(B * F), rows.new_empty(B * F)
     nbytes = int(lib.mi_sort_field_rows_workspace_bytes(B, F))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=rows.device) if nbytes else None
     _lib.check(lib.mi_sort_field_rows(rows.data_ptr(), offsets.data_ptr(), N, B, F, rows_sorted.data_ptr(),
@@ -152,68 +196,42 @@ class GatherFM(torch.autograd.Function):
         if masked and W.shape[-1] > MASKED_MAX_D:
             raise NotImplementedError(f"the masked gather_fm keeps one byte per width: D <= {MASKED_MAX_D}, got "
                                       f"{W.shape[-1]}")
-        idx = _i64c(idx)
-        offsets = _i64c(offsets.reshape(-1))
         if _float4_rows(W.shape[-1]):
             Wc, ldw = _row_strided(W)
-            w1c, ldw1 = _row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
         else:       # widths the float4 kernels do not cover run on the scalar kernels, which read the two plain tensors
-            Wc, w1c = _f32c(W), _f32c(w1)
-            ldw, ldw1 = int(Wc.shape[-1]), 1
-        if idx.dim() != 2 or idx.shape[1] != offsets.numel():
-            raise ValueError(f"idx must be [B, {offsets.numel()}], got {tuple(idx.shape)}")
-        B, F = idx.shape
+            Wc, w1 = _f32c(W), _f32c(w1)
+            ldw = int(Wc.shape[-1])
         N, D = Wc.shape
-        if w1c.numel() != N:
-            raise ValueError("first-order table must have one weight per embedding row")
+        idx, offsets, w1c, ldw1, _ = _lookup_operands(idx, offsets, w1, N)
+        B, F = idx.shape
         emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)
+        # one launch: the form chooses the entry point and what goes between the operands and the outputs
         ctx.xform = None
         if soft is not None:
             srs, scs = _soft_strides(soft, N, D)
             Sc = _f32c(soft)
-            _lib.check(
-                lib.mi_gather_fm_soft_fwd(
-                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
-                    Sc.data_ptr(), srs, scs, emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
-                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
-                ),
-                "mi_gather_fm_soft_fwd",
-            )
+            name, mid = "mi_gather_fm_soft_fwd", (Sc.data_ptr(), srs, scs)
             ctx.xform = ("soft", srs, scs, tuple(soft.shape))
         elif elem_mask is not None:
             if elem_mask.dtype not in (torch.bool, torch.uint8) or tuple(elem_mask.shape) != (N, D):
                 raise ValueError(f"elem_mask must be bool or uint8 [{N}, {D}], got {elem_mask.dtype} {tuple(elem_mask.shape)}")
             Mc = elem_mask.contiguous().view(torch.uint8)      # (a bool is one byte, 0 or 1: read in place)
-            _lib.check(
-                lib.mi_gather_fm_elemmask_fwd(
-                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
-                    Mc.data_ptr(), emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
-                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
-                ),
-                "mi_gather_fm_elemmask_fwd",
-            )
+            name, mid = "mi_gather_fm_elemmask_fwd", (Mc.data_ptr(),)
             ctx.xform = ("mask", Mc)
         elif masked:
             keep, fwidth = _mask_operands(keep, fwidth, N, F)
-            _lib.check(
-                lib.mi_gather_fm_masked_fwd(
-                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
-                    _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
-                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
-                ),
-                "mi_gather_fm_masked_fwd",
-            )
+            name, mid = "mi_gather_fm_masked_fwd", (_lib.ptr(keep), _lib.ptr(fwidth))
         else:
-            _lib.check(
-                lib.mi_gather_fm_fwd_ld(
-                    idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias),
-                    emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N,
-                    _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
-                ),
-                "mi_gather_fm_fwd_ld",
-            )
+            name, mid = "mi_gather_fm_fwd_ld", ()
+        _lib.check(
+            getattr(lib, name)(
+                idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, _lib.ptr(bias), *mid,
+                emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), B, F, D, N, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
+            ),
+            name,
+        )
         if sparse_W or sparse_w1 or DETERMINISTIC:
             note_field_layout(rows, offsets, N)
         # (the threshold is an autograd input: saved, so that an in-place update before the backward raises)
@@ -233,10 +251,7 @@ class GatherFM(torch.autograd.Function):
         sparse_W, sparse_w1 = ctx.sparse
         dev = emb.device
         lib = _lib.load()
-        if g_y is None:
-            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
-        g_y = _f32c(g_y)
-        g_emb = None if g_emb is None else _f32c(g_emb)
+        g_emb, g_y = _upstream(g_emb, g_y, B, dev)
         need_W, need_w1 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         gW = gw1 = None
         stream = _lib.stream_ptr(dev)
@@ -246,72 +261,53 @@ class GatherFM(torch.autograd.Function):
         dense_form = (need_W and not sparse_W) or (need_w1 and not sparse_w1)
         if DETERMINISTIC and dense_form:
             rows_form, dense_form = True, False     # row-form values, then a sorted (ordered) accumulation: no atomics
-        # the bias gradient (sum of g_y) rides in whichever backward kernel runs first
+        # the bias gradient (sum of g_y) rides in whichever backward kernel runs
         gb = torch.empty((1,), dtype=torch.float32, device=dev) if (ctx.has_bias and ctx.needs_input_grad[4]) else None
-        gb_done = False
+        # the kept-width form of either launch: the widths in front (and the row-form launch then reads the row ids and N)
+        masked = ctx.mask is not None
+        widths = (_lib.ptr(ctx.mask[0]), _lib.ptr(ctx.mask[1])) if masked else ()
+        upstream = (emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb))
         if rows_form:
             gvals = torch.empty((B * F, D), dtype=torch.float32, device=dev)
             g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev)
-            if ctx.mask is not None:
-                keep, fwidth = ctx.mask
-                _lib.check(
-                    lib.mi_gather_fm_masked_bwd_rows(rows.data_ptr(), _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(),
-                                                     g_y.data_ptr(), _lib.ptr(g_emb), gvals.data_ptr(), g1vals.data_ptr(),
-                                                     _lib.ptr(gb), B, F, D, N, stream),
-                    "mi_gather_fm_masked_bwd_rows",
-                )
-            else:
-                _lib.check(
-                    lib.mi_gather_fm_bwd_rows(emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb),
-                                              gvals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb), B, F, D, stream),
-                    "mi_gather_fm_bwd_rows",
-                )
-            gb_done = True
-            gW, gw1 = _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1,
-                                   stream)
+            name = "mi_gather_fm_masked_bwd_rows" if masked else "mi_gather_fm_bwd_rows"
+
+            def launch(gvals, g1vals, gb):
+                _lib.check(getattr(lib, name)(*((rows.data_ptr(), *widths) if masked else ()), *upstream, gvals.data_ptr(),
+                                              g1vals.data_ptr(), _lib.ptr(gb), B, F, D, *((N,) if masked else ()), stream), name)
+
+            gW, gw1, gb, _ = _row_backward(launch, B, rows, gvals, g1vals, gb, N, D, Wshape, w1shape, sparse_W, sparse_w1,
+                                           need_W, need_w1, stream)
         elif dense_form:
             gWd = torch.zeros((N, D), dtype=torch.float32, device=dev)
             gw1d = torch.zeros((N,), dtype=torch.float32, device=dev)
-            if ctx.mask is not None:
-                keep, fwidth = ctx.mask
-                _lib.check(
-                    lib.mi_gather_fm_masked_bwd_dense(rows.data_ptr(), _lib.ptr(keep), _lib.ptr(fwidth), emb.data_ptr(),
-                                                      g_y.data_ptr(), _lib.ptr(g_emb), gWd.data_ptr(), gw1d.data_ptr(),
-                                                      _lib.ptr(gb), B, F, D, N, stream),
-                    "mi_gather_fm_masked_bwd_dense",
-                )
-            else:
-                _lib.check(
-                    lib.mi_gather_fm_bwd_dense(rows.data_ptr(), emb.data_ptr(), g_y.data_ptr(),
-                                               _lib.ptr(g_emb), gWd.data_ptr(), gw1d.data_ptr(),
-                                               _lib.ptr(gb), B, F, D, N, stream),
-                    "mi_gather_fm_bwd_dense",
-                )
-            gb_done = True
+            name = "mi_gather_fm_masked_bwd_dense" if masked else "mi_gather_fm_bwd_dense"
+            _lib.check(getattr(lib, name)(rows.data_ptr(), *widths, *upstream, gWd.data_ptr(), gw1d.data_ptr(), _lib.ptr(gb),
+                                          B, F, D, N, stream), name)
             if need_W:
                 gW = gWd.view(Wshape)
             if need_w1:
                 gw1 = gw1d.view(w1shape)
-        if gb is not None and not gb_done:          # neither table needs a gradient: nothing was launched
-            gb = g_y.sum().view(1)
+        else:                                       # neither table needs a gradient: nothing was launched
+            gb = _bias_grad(gb, g_y, B, launched=False)
         return None, None, gW, gw1, gb, None, None, None, None, None, None
 
     @staticmethod
     def _xform_backward(ctx, emb, rows, g_emb, g_y, need_W, need_w1, stream):
-        """The PEP forms: one row-form launch, then the tables' gradients out of its values (_table_grads)."""
+        """The PEP forms: one row-form launch, then the tables' gradients out of its values (_row_backward)."""
         B, F, D, N, Wshape, w1shape = ctx.shapes
         sparse_W, sparse_w1 = ctx.sparse
         dev = emb.device
         lib = _lib.load()
         need_S = ctx.xform[0] == "soft" and ctx.needs_input_grad[9]
-        need_b = ctx.has_bias and ctx.needs_input_grad[4]
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if (ctx.has_bias and ctx.needs_input_grad[4]) else None
         if not (need_W or need_w1 or need_S):
-            return (None, None, None, None, g_y.sum().view(1) if need_b else None) + (None,) * 6
-        gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+            return (None, None, None, None, _bias_grad(gb, g_y, B, launched=False)) + (None,) * 6
         gvals = torch.empty((B * F, D), dtype=torch.float32, device=dev)
         g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev)
-        gS = None
-        if ctx.xform[0] == "soft":
+        upstream = (emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb))
+
+        def soft(gvals, g1vals, gb):
             _, srs, scs, Sshape = ctx.xform
             Sc = ctx.saved_tensors[2]
             svals = torch.empty((B * F, D) if srs == D and scs == 1 else (B * F,) if srs else (D,) if scs else (1,),
@@ -319,28 +315,28 @@ class GatherFM(torch.autograd.Function):
             ws, armed = (_losses._ticket_workspace("gather_fm_soft", dev, lib.mi_gather_fm_soft_bwd_workspace_elems(B, D, srs))
                          if srs == 0 and B > 0 else (None, True))
             _lib.check(
-                lib.mi_gather_fm_soft_bwd_rows(rows.data_ptr(), Sc.data_ptr(), srs, scs, emb.data_ptr(), g_y.data_ptr(),
-                                               _lib.ptr(g_emb), gvals.data_ptr(), svals.data_ptr(), g1vals.data_ptr(),
-                                               _lib.ptr(gb), _lib.ptr(ws), int(armed), B, F, D, N, stream),
+                lib.mi_gather_fm_soft_bwd_rows(rows.data_ptr(), Sc.data_ptr(), srs, scs, *upstream, gvals.data_ptr(),
+                                               svals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb), _lib.ptr(ws), int(armed),
+                                               B, F, D, N, stream),
                 "mi_gather_fm_soft_bwd_rows",
             )
-            if need_S:
-                if srs == 0:                  # [D] / [1]: the launch summed it
-                    gS = svals.view(Sshape)
-                else:                         # [N, D] / [N, 1]: one value row per lookup, like the table's
-                    width = D if scs else 1
-                    gS = (_coo(rows, svals.view(B * F, *Sshape[1:]), Sshape) if sparse_W
-                          else _scatter_rows(rows, svals, N, width, stream).view(Sshape))
-        else:
+            if not need_S:
+                return None
+            if srs == 0:                      # [D] / [1]: the launch summed it
+                return svals.view(Sshape)
+            width = D if scs else 1           # [N, D] / [N, 1]: one value row per lookup, like the table's
+            return (_coo(rows, svals.view(B * F, *Sshape[1:]), Sshape) if sparse_W
+                    else _scatter_rows(rows, svals, N, width, stream).view(Sshape))
+
+        def elemmask(gvals, g1vals, gb):
             _lib.check(
-                lib.mi_gather_fm_elemmask_bwd_rows(rows.data_ptr(), ctx.xform[1].data_ptr(), emb.data_ptr(), g_y.data_ptr(),
-                                                   _lib.ptr(g_emb), gvals.data_ptr(), g1vals.data_ptr(), _lib.ptr(gb),
-                                                   B, F, D, N, stream),
+                lib.mi_gather_fm_elemmask_bwd_rows(rows.data_ptr(), ctx.xform[1].data_ptr(), *upstream, gvals.data_ptr(),
+                                                   g1vals.data_ptr(), _lib.ptr(gb), B, F, D, N, stream),
                 "mi_gather_fm_elemmask_bwd_rows",
             )
-        if gb is not None and B == 0:
-            gb.zero_()
-        gW, gw1 = _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1, stream)
+
+        gW, gw1, gb, gS = _row_backward(soft if ctx.xform[0] == "soft" else elemmask, B, rows, gvals, g1vals, gb, N, D, Wshape,
+                                        w1shape, sparse_W, sparse_w1, need_W, need_w1, stream)
         return None, None, gW, gw1, gb, None, None, None, None, gS, None
 
 
@@ -397,6 +393,16 @@ def _table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1
         gw1 = (_coo(rows, g1vals.view((-1,) + (1,) * (len(w1shape) - 1)), w1shape) if sparse_w1
                else _scatter_rows(rows, g1vals, N, 1, stream).view(w1shape))
     return gW, gw1
+
+
+def _row_backward(launch, B: int, rows, gvals, g1vals, gb, *tables):
+    """The row-form backward of a fused lookup: ONE launch that writes a value row per lookup into the caller's gvals /
+    g1vals (and sums the bias gradient into its gb), then the two tables' gradients out of those values.
+    launch(gvals, g1vals, gb) issues the form's kernel and returns the gradient it produces besides (a threshold's, a
+    scale's) or None; `tables` is what _table_grads takes behind the values.  -> (gW, gw1, gb, launch's extra)."""
+    extra = launch(gvals, g1vals, gb)
+    gW, gw1 = _table_grads(rows, gvals, g1vals, *tables)
+    return gW, gw1, _bias_grad(gb, None, B), extra
 
 
 def gather_fm(idx, offsets, W, w1, bias, sparse_W=False, sparse_w1=False, keep=None, fwidth=None, soft=None, elem_mask=None):
@@ -507,7 +513,7 @@ class FMFirstOrder(torch.autograd.Function):
         B, F, D, N, w1shape, sparse_w1, has_bias = ctx.meta
         dev = embc.device
         lib = _lib.load()
-        g_y = _f32c(g_y)
+        _, g_y = _upstream(None, g_y, B, dev)
         stream = _lib.stream_ptr(dev)
         g_emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
         g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev)
@@ -526,7 +532,7 @@ class FMFirstOrder(torch.autograd.Function):
                 _lib.check(lib.mi_scatter_add_rows(rowsc.data_ptr(), g1vals.data_ptr(), gw1.data_ptr(),
                                                    B * F, 1, N, stream), "mi_scatter_add_rows")
                 gw1 = gw1.view(w1shape)
-        return (g_emb if ctx.needs_input_grad[0] else None), None, gw1, gb, None
+        return (g_emb if ctx.needs_input_grad[0] else None), None, gw1, _bias_grad(gb, g_y, B), None
 
 
 def fm_first_order(emb, rows, w1, bias, sparse_w1=False) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -828,20 +834,13 @@ class GatherFMDual(torch.autograd.Function):
         De = int(T1.shape[1])
         if De > DUAL_FM_MAX_D:
             raise NotImplementedError(f"gather_fm_dual covers De <= {DUAL_FM_MAX_D}, got {De}")
-        idx = _i64c(idx)
-        offsets = _i64c(offsets.reshape(-1))
-        if idx.dim() != 2 or idx.shape[1] != offsets.numel():
-            raise ValueError(f"idx must be [B, {offsets.numel()}], got {tuple(idx.shape)}")
+        idx, offsets, w1c, ldw1, N = _lookup_operands(idx, offsets, w1)
         T1c, T2c = _f32c(T1), _f32c(T2)
         S1c = None if S1 is None else _f32c(S1)
         S2c = None if S2 is None else _f32c(S2)
         M1c = None if M1 is None else M1.contiguous().view(torch.uint8)      # (a bool is one byte, 0 or 1: read in place)
         M2c = None if M2 is None else M2.contiguous().view(torch.uint8)
-        w1c, ldw1 = _row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
         B, F = idx.shape
-        N = int(w1c.shape[0])
-        if w1c.numel() != N and ldw1 == 1:
-            raise ValueError("first-order table must have one weight per embedding row")
         emb = torch.empty((B, F, De), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)
@@ -905,13 +904,10 @@ class GatherFMDual(torch.autograd.Function):
             return done(zero(T1shape, sparse1, need_T1), zero(T2shape, sparse2, need_T2), zero(w1shape, sparse_w1, need_w1),
                         torch.zeros((1,), dtype=torch.float32, device=dev) if need_b else None,
                         torch.zeros_like(S1c) if need_S else None, torch.zeros_like(S2c) if need_S else None)
-        if g_y is None:
-            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
-        g_y = _f32c(g_y)
-        g_emb = None if g_emb is None else _f32c(g_emb)
-        if not (need_T1 or need_T2 or need_w1 or need_S):
-            return done(gb=g_y.sum().view(1) if need_b else None)
+        g_emb, g_y = _upstream(g_emb, g_y, B, dev)
         gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+        if not (need_T1 or need_T2 or need_w1 or need_S):
+            return done(gb=_bias_grad(gb, g_y, B, launched=False))
         g1vals = torch.empty((n,), dtype=torch.float32, device=dev)
         gT1 = gT2 = gS1 = gS2 = None
         qr_rows = sparse2 and not sparse1 and xform == XF_NONE      # QR(sparse=True): emb2 as COO, emb1 dense
@@ -2424,6 +2420,31 @@ def unpack_rows(packed: torch.Tensor, D: int):
     return vals, lin
 
 
+def _slot_fm_forward(ctx, buf, slot, bias, segments=None, shared=False):
+    """The forward of SlotFM and SlotFMUnique (one kernel: a shared slot is a repeated read).  Saved for the backward: emb
+    and what addresses the slots' gradient rows — the slot ids, or routing's `segments` where lookups share slots."""
+    dev = _lib.require_gpu(buf, slot, bias, segments)
+    buf = _f32c(buf)
+    slot = _i64c(slot)
+    B, F = slot.shape
+    D = buf.shape[1] - 4
+    nslot = buf.shape[0] - 1
+    if shared and (segments is None or segments.dtype != torch.int32 or not segments.is_contiguous()
+                   or segments.numel() != 2 * nslot + B * F):
+        raise ValueError(f"segments must be a contiguous int32 tensor of 2 * {nslot} + {B * F} entries")
+    emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
+    yfm = torch.empty((B,), dtype=torch.float32, device=dev)
+    _lib.check(
+        _lib.load().mi_slot_fm_fwd(slot.data_ptr(), buf.data_ptr(), buf.shape[0], _lib.ptr(bias), emb.data_ptr(),
+                                   yfm.data_ptr(), B, F, D, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
+        "mi_slot_fm_fwd",
+    )
+    ctx.save_for_backward(emb, segments if shared else slot)
+    ctx.meta = (B, F, D, buf.shape[0], bias is not None)
+    ctx.set_materialize_grads(False)
+    return emb, yfm
+
+
 class SlotFM(torch.autograd.Function):
     """(emb[B,F,D], y_fm[B]) from the packed rows a sharded lookup received, addressed by slot
     (src/models/deepfm.py:88-98 on exchanged rows).  buf is [S+1, D+4] with row S all zeros (the
@@ -2431,23 +2452,7 @@ class SlotFM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, buf, slot, bias):
-        dev = _lib.require_gpu(buf, slot, bias)
-        lib = _lib.load()
-        buf = _f32c(buf)
-        slot = _i64c(slot)
-        B, F = slot.shape
-        D = buf.shape[1] - 4
-        emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
-        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
-        _lib.check(
-            lib.mi_slot_fm_fwd(slot.data_ptr(), buf.data_ptr(), buf.shape[0], _lib.ptr(bias), emb.data_ptr(),
-                               yfm.data_ptr(), B, F, D, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
-            "mi_slot_fm_fwd",
-        )
-        ctx.save_for_backward(emb, slot)
-        ctx.meta = (B, F, D, buf.shape[0], bias is not None)
-        ctx.set_materialize_grads(False)
-        return emb, yfm
+        return _slot_fm_forward(ctx, buf, slot, bias)
 
     @staticmethod
     def backward(ctx, g_emb, g_y):
@@ -2455,13 +2460,9 @@ class SlotFM(torch.autograd.Function):
         B, F, D, rows, has_bias = ctx.meta
         dev = emb.device
         lib = _lib.load()
-        if g_y is None:
-            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
-        g_y = _f32c(g_y)
-        g_emb = None if g_emb is None else _f32c(g_emb)
+        g_emb, g_y = _upstream(g_emb, g_y, B, dev)
         gbuf = None
-        want_gb = has_bias and ctx.needs_input_grad[2]
-        gb = torch.empty((1,), dtype=torch.float32, device=dev) if want_gb else None
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if (has_bias and ctx.needs_input_grad[2]) else None
         if ctx.needs_input_grad[0]:
             gbuf = torch.empty((rows, D + 4), dtype=torch.float32, device=dev)
             # the kernel zeroes rows [0, S) itself and never stores to the dump row: that row (what the all-to-all does not
@@ -2472,9 +2473,7 @@ class SlotFM(torch.autograd.Function):
                                    gbuf.data_ptr(), _lib.ptr(gb), rows - 1, B, F, D, _lib.stream_ptr(dev)),
                 "mi_slot_fm_bwd",
             )
-        elif want_gb:
-            gb = g_y.sum().view(1)
-        return gbuf, None, gb
+        return gbuf, None, _bias_grad(gb, g_y, B, launched=gbuf is not None)
 
 
 def slot_fm(buf, slot, bias):
@@ -2510,15 +2509,8 @@ def route_buckets_unique(idx: torch.Tensor, offsets: Optional[torch.Tensor], wor
     err = _lib.err_word(dev).data_ptr()
     stream = _lib.stream_ptr(dev)
     flat = rows.reshape(-1)
-    B = n // F
-    if field_sort and off is not None and idxc.dim() == 2 and 0 < B <= 65536 and num_rows < 2**32 - 2:
-        rs, perm = torch.empty_like(flat), torch.empty_like(flat)
-        nbytes = int(lib.mi_sort_field_rows_workspace_bytes(B, F))
-        sws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-        _lib.check(lib.mi_sort_field_rows(rows.data_ptr(), off.data_ptr(), num_rows, B, F, rs.data_ptr(), perm.data_ptr(),
-                                          _lib.ptr(sws), err, stream), "mi_sort_field_rows")
-    else:
-        rs, perm = torch.sort(flat, stable=True)
+    found = _sort_fields(rows, off, num_rows, n // F, F) if field_sort and off is not None and idxc.dim() == 2 else None
+    rs, perm = found if found is not None else torch.sort(flat, stable=True)
     ws = torch.empty(int(lib.mi_route_unique_workspace_elems(n, world)), dtype=torch.int32, device=dev)
 
     def _out(given, shape, dtype, what):
@@ -2547,26 +2539,7 @@ class SlotFMUnique(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, buf, slot, bias, segments):
-        dev = _lib.require_gpu(buf, slot, bias, segments)
-        lib = _lib.load()
-        buf = _f32c(buf)
-        slot = _i64c(slot)
-        B, F = slot.shape
-        D = buf.shape[1] - 4
-        nslot = buf.shape[0] - 1
-        if segments.dtype != torch.int32 or not segments.is_contiguous() or segments.numel() != 2 * nslot + B * F:
-            raise ValueError(f"segments must be a contiguous int32 tensor of 2 * {nslot} + {B * F} entries")
-        emb = torch.empty((B, F, D), dtype=torch.float32, device=dev)
-        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
-        _lib.check(
-            lib.mi_slot_fm_fwd(slot.data_ptr(), buf.data_ptr(), buf.shape[0], _lib.ptr(bias), emb.data_ptr(),
-                               yfm.data_ptr(), B, F, D, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
-            "mi_slot_fm_fwd",
-        )
-        ctx.save_for_backward(emb, segments)
-        ctx.meta = (B, F, D, buf.shape[0], bias is not None)
-        ctx.set_materialize_grads(False)
-        return emb, yfm
+        return _slot_fm_forward(ctx, buf, slot, bias, segments, shared=True)
 
     @staticmethod
     def backward(ctx, g_emb, g_y):
@@ -2574,13 +2547,9 @@ class SlotFMUnique(torch.autograd.Function):
         B, F, D, rows, has_bias = ctx.meta
         dev = emb.device
         lib = _lib.load()
-        if g_y is None:
-            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
-        g_y = _f32c(g_y)
-        g_emb = None if g_emb is None else _f32c(g_emb)
+        g_emb, g_y = _upstream(g_emb, g_y, B, dev)
         gbuf = None
-        want_gb = has_bias and ctx.needs_input_grad[2]
-        gb = torch.empty((1,), dtype=torch.float32, device=dev) if want_gb else None
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if (has_bias and ctx.needs_input_grad[2]) else None
         if ctx.needs_input_grad[0]:
             gbuf = torch.empty((rows, D + 4), dtype=torch.float32, device=dev)      # every row is written by the kernel
             ws = torch.empty(int(lib.mi_slot_fm_bwd_segments_workspace_elems(B, F, D)), dtype=torch.float32, device=dev)
@@ -2590,9 +2559,7 @@ class SlotFMUnique(torch.autograd.Function):
                                             _lib.stream_ptr(dev)),
                 "mi_slot_fm_bwd_segments",
             )
-        elif want_gb:
-            gb = g_y.sum().view(1)
-        return gbuf, None, gb, None
+        return gbuf, None, _bias_grad(gb, g_y, B, launched=gbuf is not None), None
 
 
 def slot_fm_unique(buf, slot, bias, segments):

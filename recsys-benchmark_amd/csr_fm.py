@@ -12,8 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _kernels, _lib
-from .layer_dcn import _new
-from .quant_fm import _int64_rows, _lookup_operands
+from .layer_dcn import _int64_rows, _new
 
 CROW_DTYPES = {torch.int32: 4, torch.int64: 8}      # crow_bytes of the two entry points
 COL_DTYPES = {torch.uint8: 1, torch.int64: 8}       # col_bytes
@@ -51,7 +50,7 @@ def gather_fm_csr(idx, offsets, values, crow, col, w1, bias, D: int, N: int) -> 
     D, N = int(D), int(N)
     values, crow, col, crow_bytes, col_bytes = _csr_operands(values, crow, col, D, N)
     with torch.no_grad():
-        idx, offsets, w1c, ldw1 = _lookup_operands(idx, offsets, w1.detach(), N)
+        idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1.detach(), N)
         B, F = idx.shape
         emb = _new((B, F, D), dev)
         yfm = _new((B,), dev)

@@ -26,22 +26,9 @@ from typing import Any, Dict, List, Optional, Union, cast
 import torch
 from torch import nn
 
-from . import _kernels, csr_fm, quant_fm
-from .embeddings import IEmbedding, PrunedEmbedding, VanillaEmbedding, get_embedding
-from .embeddings.deepfm_opt_embed import OptEmbed as DeepFMOptEmbed, RetrainOptEmbed
-from .embeddings.cerp_embedding import CerpEmbedding, RetrainCerpEmbedding
-from .embeddings.pep_embedding import PepEmbeeding, RetrainPepEmbedding
-from .embeddings.ptq_emb import PTQEmb_Fp16, PTQEmb_Int
-from .embeddings.qat_emb import QAT_EmbInt
-from .embeddings.qr_embedding import QRHashingEmbedding
+from . import _kernels
+from .embeddings import IEmbedding, VanillaEmbedding, get_embedding
 from .mlp import field_offsets, hidden_stack, run_tail
-
-
-def _hooked(module: nn.Module) -> bool:
-    """Whether a forward hook or pre-hook would fire on a call of `module`: its own, or one registered for every module."""
-    from torch.nn.modules import module as _m
-
-    return bool(module._forward_hooks or module._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks)
 
 
 class DeepFM(nn.Module):
@@ -124,54 +111,13 @@ class DeepFM(nn.Module):
                     and W.untyped_storage().data_ptr() == w1.untyped_storage().data_ptr())
 
     def _fm_and_embedding(self, x):
+        """(emb, y_fm).  The table is asked for its own fused launch first (IEmbedding.fm_lookup: the rows of the module
+        docstring); a table without one, or one that declines this call, is looked up through its forward()."""
         emb_mod = self.embedding
-        if type(emb_mod) is VanillaEmbedding and emb_mod._mode is None:      # subclasses (QAT) transform the rows
-            return _kernels.gather_fm(
-                x, self.offsets, emb_mod.get_weight(), self.fc.weight, self._bias,
-                sparse_W=emb_mod.sparse_grad, sparse_w1=bool(self.fc.sparse),
-            )
-        # OptEmbed: a search candidate in eval, the retraining table in training and eval alike — the same launch with a
-        # kept width per looked-up row, no masked copy of the table and no [B, F] index tensors
-        mask = emb_mod.fm_mask() if isinstance(emb_mod, (DeepFMOptEmbed, RetrainOptEmbed)) else None
-        if mask is not None:
-            W, keep, fwidth, sparse_W = mask
-            return _kernels.gather_fm(x, self.offsets, W, self.fc.weight, self._bias, sparse_W=sparse_W,
-                                      sparse_w1=bool(self.fc.sparse), keep=keep, fwidth=fwidth)
-        # PEP: the threshold search and the retraining table — the same launch with the soft threshold, or the element
-        # mask, applied to the looked-up rows
-        xform = emb_mod.fm_xform() if isinstance(emb_mod, (PepEmbeeding, RetrainPepEmbedding)) else None
-        if xform is not None:
-            return _kernels.gather_fm(x, self.offsets, xform.pop("W"), self.fc.weight, self._bias,
-                                      sparse_w1=bool(self.fc.sparse), **xform)
-        # QR / CERP / CERP retrain: the two row gathers, their transform and the combine inside the same launch
-        # (mi_gather_fm_dual_*); "cat", bag modes and CPU tables keep the path below
-        dual = emb_mod.fm_dual() if isinstance(emb_mod, (QRHashingEmbedding, CerpEmbedding, RetrainCerpEmbedding)) else None
-        if dual is not None:
-            return _kernels.gather_fm_dual(x, self.offsets, w1=self.fc.weight, bias=self._bias,
-                                           sparse_w1=bool(self.fc.sparse), **dual)
-        # QAT / PTQ: the rounding, or the dequantisation of the code rows, inside the same launch (mi_gather_fm_qat_* /
-        # mi_gather_fm_quant_fwd).  This branch never calls the embedding module, so a module with a forward hook or
-        # pre-hook — its own or a global one — keeps the path below: the hooks keep firing.  Bag modes and CPU tables keep
-        # it too.  The PTQ launch is inference only (no autograd node): a forward whose first-order term or bias wants a
-        # gradient keeps the path below as well, where fm_first_order hands fc.weight and _bias theirs.
-        if isinstance(emb_mod, (QAT_EmbInt, PTQEmb_Int, PTQEmb_Fp16)) and not _hooked(emb_mod):
-            if isinstance(emb_mod, QAT_EmbInt):
-                quant = emb_mod.fm_quant(x)
-                if quant is not None:
-                    return quant_fm.gather_fm_qat(x, self.offsets, w1=self.fc.weight, bias=self._bias,
-                                                  sparse_w1=bool(self.fc.sparse), **quant)
-            elif not (torch.is_grad_enabled() and (self.fc.weight.requires_grad or self._bias.requires_grad)):
-                quant = emb_mod.fm_quant(x)
-                if quant is not None:
-                    return quant_fm.gather_fm_quant(x, self.offsets, w1=self.fc.weight, bias=self._bias, **quant)
-        # A CSR-pruned table (inference only): the row densify inside the same launch (mi_gather_fm_csr_fwd), for wide and
-        # compact index buffers alike.  The guards are the PTQ launch's: hooks, a first-order term or bias that wants a
-        # gradient, bag modes and CPU tables keep the path below.
-        if (isinstance(emb_mod, PrunedEmbedding) and not _hooked(emb_mod)
-                and not (torch.is_grad_enabled() and (self.fc.weight.requires_grad or self._bias.requires_grad))):
-            csr = emb_mod.fm_csr(x)
-            if csr is not None:
-                return csr_fm.gather_fm_csr(x, self.offsets, w1=self.fc.weight, bias=self._bias, **csr)
+        lookup = getattr(emb_mod, "fm_lookup", None)
+        fused = None if lookup is None else lookup(x, self.offsets, self.fc.weight, self._bias, bool(self.fc.sparse))
+        if fused is not None:
+            return fused
         rows = x + self.offsets
         _kernels.note_field_layout(rows, self.offsets, self.fc.weight.shape[0])   # lets the sparse optimizer sort by field
         emb = emb_mod(rows)

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from .. import _kernels
-from .base import IEmbedding
+from .base import IEmbedding, _dual_fm_lookup
 
 
 class CerpEmbedding(IEmbedding):
@@ -113,6 +113,8 @@ class CerpEmbedding(IEmbedding):
             return None
         return dict(T1=self.p_weight, T2=self.q_weight, mod1=self._bucket_size, div2=self.q_entity_per_row, op="add",
                     S1=self.p_threshold, S2=self.q_threshold)
+
+    fm_lookup = _dual_fm_lookup
 
     def _on_kernels(self) -> bool:
         tables = (self.p_weight, self.q_weight, self.p_threshold, self.q_threshold)
@@ -252,6 +254,8 @@ class RetrainCerpEmbedding(IEmbedding):
             return None
         return dict(T1=self.p_weight, T2=self.q_weight, mod1=self._bucket_size, div2=self.q_entity_per_row, op="add",
                     M1=self.p_mask, M2=self.q_mask, sparse1=self._sparse, sparse2=self._sparse)
+
+    fm_lookup = _dual_fm_lookup
 
     def get_num_params(self):
         return (torch.count_nonzero(self.q_mask) + torch.count_nonzero(self.p_mask)).item()

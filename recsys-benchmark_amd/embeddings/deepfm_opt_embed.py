@@ -31,6 +31,16 @@ def get_mask(hidden_size: int) -> torch.Tensor:
     return torch.tril(torch.ones((hidden_size, hidden_size), dtype=torch.bool))
 
 
+def _masked_fm_lookup(self, x, offsets, w1, bias, sparse_w1: bool):
+    """IEmbedding.fm_lookup of the two OptEmbed tables: a search candidate in eval, the retraining table in training and
+    eval alike — the plain launch with a kept width per looked-up row, no masked copy of the table."""
+    mask = self.fm_mask()
+    if mask is None:
+        return None
+    W, keep, fwidth, sparse_W = mask
+    return _kernels.gather_fm(x, offsets, W, w1, bias, sparse_W=sparse_W, sparse_w1=sparse_w1, keep=keep, fwidth=fwidth)
+
+
 class _OptLookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, W, t, idx, tix, F: int, dmax, norm: int):
@@ -207,6 +217,8 @@ class OptEmbed(IEmbedding):
             return None
         return self._weight, self._cand_keep, (self._cand_fwidth if self._mode_d == "field" else None), False
 
+    fm_lookup = _masked_fm_lookup
+
     # ---- reference API -----------------------------------------------------------------------------
     def get_l_s(self):
         if self._t_init is None:
@@ -374,6 +386,8 @@ class RetrainOptEmbed(IEmbedding):
         if self._mode is not None:
             return None
         return self._weight, self._keep, None, self.sparse_grad
+
+    fm_lookup = _masked_fm_lookup
 
     def get_weight(self, mask_d: Optional[torch.Tensor] = None):
         self._cur_weight = self._weight * self._mask

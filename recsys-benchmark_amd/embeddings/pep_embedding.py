@@ -43,6 +43,15 @@ def _milestone_file(directory: str, sparsity) -> str:
     return os.path.join(directory, f"{sparsity}.pth")
 
 
+def _xform_fm_lookup(self, x, offsets, w1, bias, sparse_w1: bool):
+    """IEmbedding.fm_lookup of the two PEP tables: the threshold search and the retraining table — the plain launch with
+    the soft threshold, or the element mask, applied to the looked-up rows."""
+    xform = self.fm_xform()
+    if xform is None:
+        return None
+    return _kernels.gather_fm(x, offsets, xform.pop("W"), w1, bias, sparse_w1=sparse_w1, **xform)
+
+
 class PepEmbeeding(IEmbedding):   # (sic: the reference's class name)
     def __init__(
         self,
@@ -106,6 +115,8 @@ class PepEmbeeding(IEmbedding):   # (sic: the reference's class name)
             return None
         return dict(W=self.emb.weight, soft=self.s, sparse_W=False)
 
+    fm_lookup = _xform_fm_lookup
+
     def get_num_params(self) -> int:
         if self.emb.weight.is_cuda:       # counted in one pass over the table and the thresholds, no soft(W) copy
             return int(_kernels.soft_count_kept(self.emb.weight.detach(), self.s.detach()).item())
@@ -166,6 +177,8 @@ class RetrainPepEmbedding(IEmbedding):
         if self._mode is not None:
             return None
         return dict(W=self.emb.weight, elem_mask=self.mask, sparse_W=bool(self._sparse))
+
+    fm_lookup = _xform_fm_lookup
 
     def get_num_params(self):
         return self._nnz

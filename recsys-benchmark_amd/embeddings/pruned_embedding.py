@@ -14,7 +14,7 @@ from typing import List, Optional, Union
 import torch
 
 from .. import _kernels, csr_fm
-from .base import IEmbedding
+from .base import IEmbedding, _unhooked
 
 _BUFFERS = {"values": (torch.float32,), "crow_indices": (torch.int64, torch.int32), "col_indices": (torch.int64, torch.uint8)}
 COMPACT_MAX_D = 256            # a column fits one byte
@@ -165,3 +165,11 @@ class PrunedEmbedding(IEmbedding):
         if x.dim() != 2 or x.device != self.crow_indices.device:
             return None
         return dict(values=self.values, crow=self.crow_indices, col=self.col_indices, D=self._hidden_size, N=self._num_item)
+
+    def fm_lookup(self, x, offsets, w1, bias, sparse_w1: bool):
+        """The row densify inside DeepFM's lookup launch (mi_gather_fm_csr_fwd), for wide and compact index buffers alike:
+        inference only, no autograd node."""
+        csr = self.fm_csr(x) if _unhooked(self, w1, bias) else None
+        if csr is None:
+            return None
+        return csr_fm.gather_fm_csr(x, offsets, w1=w1, bias=bias, **csr)

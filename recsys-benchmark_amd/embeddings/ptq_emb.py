@@ -7,7 +7,7 @@ inside the HIP gather (mi_gather_rows_quant): 32- or 16-byte rows at D=16 instea
 import torch
 
 from .. import _kernels
-from .base import IEmbedding
+from .base import IEmbedding, _unhooked
 
 _TABLE_KEY = "embedding._emb_module.weight"
 
@@ -48,6 +48,16 @@ class _FrozenTable(IEmbedding):
         if not self.weight.is_cuda or not x.is_cuda or x.dim() != 2:
             return None
         return self._fm_operands()
+
+    def fm_lookup(self, x, offsets, w1, bias, sparse_w1: bool):
+        """The dequantisation of the code rows inside DeepFM's lookup launch (mi_gather_fm_quant_fwd): inference only, no
+        autograd node."""
+        from .. import quant_fm
+
+        quant = self.fm_quant(x) if _unhooked(self, w1, bias) else None
+        if quant is None:
+            return None
+        return quant_fm.gather_fm_quant(x, offsets, w1=w1, bias=bias, **quant)
 
 
 class PTQEmb_Fp16(_FrozenTable):

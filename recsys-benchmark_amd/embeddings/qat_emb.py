@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from .. import _kernels, _lib
-from .base import VanillaEmbedding
+from .base import VanillaEmbedding, _unhooked
 
 
 def get_qmax_qmin(n_bits):
@@ -95,6 +95,16 @@ class QAT_EmbInt(VanillaEmbedding):
         seed = self._sr_seed.clone()
         self._sr_seed.add_(1)
         return dict(W=W, scale=self.scale, n_bits=int(self.n_bits), seed=seed, sparse_W=self.sparse_grad)
+
+    def fm_lookup(self, x, offsets, w1, bias, sparse_w1: bool):
+        """The rounding inside DeepFM's lookup launch (mi_gather_fm_qat_*); fm_quant() is asked only for a lookup that
+        is then made here: a hooked module keeps forward()."""
+        from .. import quant_fm
+
+        quant = self.fm_quant(x) if _unhooked(self) else None
+        if quant is None:
+            return None
+        return quant_fm.gather_fm_qat(x, offsets, w1=w1, bias=bias, sparse_w1=sparse_w1, **quant)
 
     def get_weight(self):
         return super().get_weight()

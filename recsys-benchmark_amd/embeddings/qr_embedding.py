@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from .. import _kernels
-from .base import IEmbedding
+from .base import IEmbedding, _dual_fm_lookup
 
 _COMBINE = ("cat", "add", "mult")
 
@@ -120,6 +120,8 @@ class QRHashingEmbedding(IEmbedding):
         d = self._divider
         return dict(T1=w1, T2=w2, mod1=d, div2=d, op=self._operation, sparse2=self._sparse2,
                     fields=self._field_hint(w1.device))
+
+    fm_lookup = _dual_fm_lookup
 
     def takes_offsets(self, tensor: torch.Tensor) -> bool:
         """Whether forward(tensor, offsets=...) folds the addition into the lookup kernel (float4 rows, [B, F] ids on the GPU)."""

@@ -23,6 +23,11 @@ def _new(shape, dev):
     return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
+def _int64_rows(B: int, F: int, dev) -> torch.Tensor:
+    """int64[B, F] a lookup launch fills with idx + offsets: two floats per id of a float32 buffer, viewed as int64."""
+    return _new((B, F, 2), dev).view(torch.int64).view(B, F)
+
+
 def _expert_fused(r: int, d: int) -> bool:
     """mi_mix_expert_fwd/bwd cover ranks 16 / 32 / 64 (the reference's configs use 64) and d % 4 == 0."""
     return _kernels.PANEL_GEMM and r in (16, 32, 64) and d % 4 == 0

@@ -16,29 +16,11 @@ import torch
 
 from . import _kernels, _lib
 from . import losses as _losses
-from .layer_dcn import _new
+from .layer_dcn import _int64_rows, _new
 
 QTYPES = {torch.float16: 1, torch.int8: 2, torch.int16: 3}      # the qtype codes of mi_gather_rows_quant
 QAT_BWD_MAX_D = 256                                            # MI_GATHER_FM_QAT_BWD_MAX_D
 SCALE_GRAD_MAX_BITS = 21      # the backward recovers the rounded code as rintf(emb / scale): exact for |code| <= 2^20
-
-
-def _lookup_operands(idx, offsets, w1, N: int):
-    """(idx int64[B, F], offsets int64[F] or None, w1 and its row stride) as the launches read them."""
-    idx = _kernels._i64c(idx)
-    if offsets is not None:
-        offsets = _kernels._i64c(offsets.reshape(-1))
-    if idx.dim() != 2 or (offsets is not None and idx.shape[1] != offsets.numel()):
-        raise ValueError(f"idx must be [B, F] with one offset per field, got {tuple(idx.shape)}")
-    w1c, ldw1 = _kernels._row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
-    if w1c.shape[0] != N or (ldw1 == 1 and w1c.numel() != N):
-        raise ValueError("first-order table must have one weight per embedding row")
-    return idx, offsets, w1c, ldw1
-
-
-def _int64_rows(B: int, F: int, dev) -> torch.Tensor:
-    """int64[B, F] the forward launch fills with idx + offsets: two floats per id of a float32 buffer, viewed as int64."""
-    return _new((B, F, 2), dev).view(torch.int64).view(B, F)
 
 
 def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None):
@@ -66,7 +48,7 @@ def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None):
     Wc = Wq if Wq.is_contiguous() else Wq.contiguous()
     N, D = Wc.shape
     with torch.no_grad():
-        idx, offsets, w1c, ldw1 = _lookup_operands(idx, offsets, w1.detach(), N)
+        idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1.detach(), N)
         B, F = idx.shape
         emb = _new((B, F, D), dev)
         yfm = _new((B,), dev)
@@ -101,7 +83,7 @@ class GatherFMQat(torch.autograd.Function):
         N, D = Wc.shape
         if D > QAT_BWD_MAX_D:
             raise NotImplementedError(f"gather_fm_qat's backward covers D <= {QAT_BWD_MAX_D}, got {D}")
-        idx, offsets, w1c, ldw1 = _lookup_operands(idx, offsets, w1, N)
+        idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1, N)
         B, F = idx.shape
         sc = _kernels._f32c(scale.reshape(1))
         probc = None
@@ -145,30 +127,29 @@ class GatherFMQat(torch.autograd.Function):
         stream = _lib.stream_ptr(dev)
         need_W, need_s, need_w1 = ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         need_b = ctx.has_bias and ctx.needs_input_grad[5]
-        if g_y is None:
-            g_y = torch.zeros((B,), dtype=torch.float32, device=dev)
-        g_y = _kernels._f32c(g_y)
-        g_emb = None if g_emb is None else _kernels._f32c(g_emb)
-        if not (need_W or need_s or need_w1):
-            return (None,) * 5 + (g_y.sum().view(1) if need_b else None,) + (None,) * 6
+        g_emb, g_y = _kernels._upstream(g_emb, g_y, B, dev)
         gb = _new((1,), dev) if need_b else None
+        if not (need_W or need_s or need_w1):
+            return (None,) * 5 + (_kernels._bias_grad(gb, g_y, B, launched=False),) + (None,) * 6
         gvals = _new((B * F, D), dev)
         g1vals = _new((B * F,), dev)
-        ds = _new((1,), dev) if need_s else None
-        ws, armed = (_losses._ticket_workspace("gather_fm_qat", dev, lib.mi_gather_fm_qat_bwd_workspace_elems(B))
-                     if need_s and B > 0 else (None, True))
-        _lib.check(
-            lib.mi_gather_fm_qat_bwd_rows(_lib.ptr(rows), Wc.data_ptr() if need_s else None, sc.data_ptr(), n_bits,
-                                          emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb), gvals.data_ptr(),
-                                          g1vals.data_ptr(), _lib.ptr(gb), _lib.ptr(ds), _lib.ptr(ws), int(armed), B, F, D, N,
-                                          stream),
-            "mi_gather_fm_qat_bwd_rows",
-        )
-        if gb is not None and B == 0:
-            gb.zero_()
-        gW, gw1 = _kernels._table_grads(rows, gvals, g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1, need_W, need_w1,
-                                        stream)
-        return None, None, gW, None if ds is None else ds.view(sshape), gw1, gb, None, None, None, None, None, None
+
+        def launch(gvals, g1vals, gb):
+            ds = _new((1,), dev) if need_s else None
+            ws, armed = (_losses._ticket_workspace("gather_fm_qat", dev, lib.mi_gather_fm_qat_bwd_workspace_elems(B))
+                         if need_s and B > 0 else (None, True))
+            _lib.check(
+                lib.mi_gather_fm_qat_bwd_rows(_lib.ptr(rows), Wc.data_ptr() if need_s else None, sc.data_ptr(), n_bits,
+                                              emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb), gvals.data_ptr(),
+                                              g1vals.data_ptr(), _lib.ptr(gb), _lib.ptr(ds), _lib.ptr(ws), int(armed), B, F, D, N,
+                                              stream),
+                "mi_gather_fm_qat_bwd_rows",
+            )
+            return None if ds is None else ds.view(sshape)
+
+        gW, gw1, gb, gs = _kernels._row_backward(launch, B, rows, gvals, g1vals, gb, N, D, Wshape, w1shape, sparse_W, sparse_w1,
+                                                 need_W, need_w1, stream)
+        return None, None, gW, gs, gw1, gb, None, None, None, None, None, None
 
 
 def gather_fm_qat(idx, offsets, W, scale, n_bits: int, w1, bias, *, seed: Optional[torch.Tensor] = None,

@@ -690,12 +690,10 @@ class DeepFMFusedFn(torch.autograd.Function):
     def forward(ctx, plan, head, seed, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool, labels, *params):
         dev = _lib.require_gpu(idx, offsets, W, w1, bias)
         lib = _lib.load()
-        idx = _kernels._i64c(idx)
-        offsets = _kernels._i64c(offsets.reshape(-1))
         Wc, ldw = _kernels._row_strided(W)
-        w1c, ldw1 = _kernels._row_strided(w1.reshape(w1.shape[0], -1) if w1.dim() != 2 else w1, align=1)
-        B, F = idx.shape
         N, D = Wc.shape
+        idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1, N)
+        B, F = idx.shape
         emb = torch.empty((B, F * D), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)

@@ -111,7 +111,7 @@ def reached_sites(record, sites=None):
 # Sites the catalogue cannot reach in one eager process, "file:line:column" -> the reason read from the code (needs a process group,
 # runs only inside a capture, is a CPU-only branch).
 NOT_REACHED = {
-    "_kernels.py:2750:15": "runs only inside a capture: _auc_workspace hands a capture a buffer of the graph's own pool",
+    "_kernels.py:2717:15": "runs only inside a capture: _auc_workspace hands a capture a buffer of the graph's own pool",
     "embeddings/dh_embedding.py:153:19": "is a CPU-only branch: the host-built per-item hash table of an empty id range",
     "embeddings/tensortrain_embeddings.py:141:22": "is a CPU-only branch: a numpy array of the host-side approx-uniform initialiser",
     "embeddings/tensortrain_embeddings.py:141:55": "is a CPU-only branch: a numpy array of the host-side approx-uniform initialiser",
