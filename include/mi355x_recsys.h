@@ -476,6 +476,35 @@ MI_API int mi_gather_fm_qat_bwd_rows(const int64_t *rows, const float *W, const 
                                      float *gvals, float *g1vals, float *gbias, float *dscale, float *workspace,
                                      int32_t armed, int64_t B, int32_t F, int32_t D, int64_t N, void *stream);
 
+/* ---- PTQEmb_Int(n_bits=4) with two codes per byte, and the device-side quantiser of the PTQ integer tables ----
+ * The reference keeps one 4-bit code per int8 byte (src/models/embeddings/ptq_emb.py:61-83).  The packed table is
+ * uint8 [N, D/2] (D even): element d of row r in byte r*D/2 + d/2, the low nibble for even d, the high nibble for odd d,
+ * each nibble a two's-complement code in [-8, 7]; scale a device fp32 word, zero a device INT8 word (the zero point of
+ * ptq_emb.py:73 can lie outside the nibble range and is never packed).
+ * MI_QTYPE_INT4_PACKED as the qtype of mi_gather_fm_quant_fwd: Wq is such a table, D the LOGICAL width; emb has the bits of
+ *   qtype 2 over the unpacked codes.  D = 4 * 2^k <= 256 with Wq 2-byte and emb 16-byte aligned runs the kernels that load a
+ *   lane's four codes as one 16-bit word, anything else (D % 4 == 2, an odd base) the scalar ones: the same bits.
+ * mi_gather_rows_int4 (ptq_emb.py:85-91): out[i,:] = (code(W[row_i,:]) - zero[0]) * scale[0], row_i = idx[i] (idx NULL: i, the
+ *   table form of get_weight()) + offsets[i % F] (offsets int64[F], nullable); rows_out int64[n], nullable (needs idx): row_i.
+ *   The bits of mi_gather_rows_quant (qtype 2) over the unpacked codes; a row outside [0, N) reads as zeros and ORs
+ *   MI_IDX_OUT_OF_RANGE into *err.
+ * mi_ptq_quantise (ptq_emb.py:78-83): W fp32 [N, D] with row stride ldw >= D (elements) -> codes_out, in one pass:
+ *   rintf(W / scale[0] + (float)zero[0]) — IEEE division, round half to even —, clamped to [-2^(n_bits-1), 2^(n_bits-1) - 1]
+ *   for n_bits < 8, narrowed to the storage type through int32.  n_bits 4 or 8: int8 [N, D] (zero an int8 word), packed != 0
+ *   (n_bits 4, D even): uint8 [N, D/2] in the layout above; n_bits 16: int16 [N, D] (zero an int16 word).
+ * mi_int4_repack (ptq_emb.py:83, a reference n_bits = 4 checkpoint): unpack == 0: src int8 codes [N, D] -> dst packed
+ *   [N, D/2]; a code outside [-8, 7] ORs MI_CODE_OUT_OF_RANGE into *err (dst is then not a table; no host read in the call).
+ *   unpack != 0: src packed -> dst int8 [N, D].  src and dst do not overlap.
+ */
+#define MI_QTYPE_INT4_PACKED 5
+#define MI_CODE_OUT_OF_RANGE 4   /* a bit of *err beside MI_IDX_OUT_OF_RANGE / MI_IDX_OUT_OF_FIELD */
+MI_API int mi_gather_rows_int4(const int64_t *idx, const int64_t *offsets, const void *W, const float *scale,
+                               const void *zero, float *out, int64_t *rows_out, int64_t n, int32_t F, int32_t D,
+                               int64_t N, int32_t *err, void *stream);
+MI_API int mi_ptq_quantise(const float *W, int64_t ldw, const float *scale, const void *zero, int32_t n_bits,
+                           int32_t packed, void *codes_out, int64_t N, int32_t D, void *stream);
+MI_API int mi_int4_repack(const void *src, void *dst, int32_t unpack, int64_t N, int32_t D, int32_t *err, void *stream);
+
 /* ---- §8f rank 4 (fourth flavour): OptEmbed supernet lookup ---------------------------------------
  * OptEmbed.forward / get_weight (src/models/embeddings/deepfm_opt_embed.py:150-243) with _MaskEmbeddingModule
  * and BinaryStep (optembed_utils.py:10-112):

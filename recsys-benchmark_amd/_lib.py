@@ -148,6 +148,9 @@ SIGNATURES = {
     "mi_gather_fm_qat_fwd": [_p, _p, _p, _p, _i32, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
     "mi_gather_fm_qat_bwd_workspace_elems": [_i64],
     "mi_gather_fm_qat_bwd_rows": [_p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i64, _p],
+    "mi_gather_rows_int4": [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _i64, _p, _p],
+    "mi_ptq_quantise": [_p, _i64, _p, _p, _i32, _i32, _p, _i64, _i32, _p],
+    "mi_int4_repack": [_p, _p, _i32, _i64, _i32, _p, _p],
     "mi_optembed_fwd": [_p, _p, _p, _p, _i32, _p, _i32, _p, _i64, _i32, _i64, _p, _p],
     "mi_optembed_bwd": [_p, _p, _p, _p, _i32, _p, _i32, _p, _p, _p, _i64, _i32, _i64, _p],
     "mi_optembed_cf_fwd": [_p, _p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _i32, _p, _i64, _i32, _p, _p],
@@ -341,6 +344,8 @@ def check_index_errors(device: Optional[torch.device] = None) -> None:
             w.zero_()
             if bits & 1:
                 raise IndexError("index out of range in embedding lookup (mi355x_recsys)")
+            if bits & 4 and not bits & 2:      # MI_CODE_OUT_OF_RANGE (mi_int4_repack)
+                raise ValueError("a code outside [-8, 7] cannot be packed as a 4-bit nibble (mi355x_recsys)")
             raise IndexError("an id lies outside its own field's range (inside the concatenated table): the lookup read "
                              "another field's row like the reference does, but the field-sorted sparse optimizer dropped "
                              "its gradient (mi355x_recsys)")

@@ -8,7 +8,7 @@
 // Forward mapping: gather_fm.hip's — one wave per sample, LPR = D / 4 lanes per row (lane q holds columns 4q .. 4q+3),
 // RS = 64 / LPR rows per wave-instruction, the F ids by one coalesced load and shuffles when F <= 64, up to four row steps
 // with all their loads in flight, emb stored non-temporally.  What differs is the row source: a lane's four codes are ONE
-// 32-bit word (int8) or ONE 64-bit word (int16, fp16) of a 16- or 32-byte row at D = 16, the source is a template
+// 32-bit word (int8), ONE 64-bit word (int16, fp16) or ONE 16-bit word (packed int4) of an 8- to 32-byte row at D = 16, the source is a template
 // parameter.  The dequantisation is k_gather_rows_q's (embed.hip), the rounding is sr_round.hpp's, so emb has the bits
 // of mi_gather_rows_quant / mi_qat_gather_fwd over idx + offsets.
 // The walks are bodies of this file on the helpers of gather_fm_walk.hpp: the shared forward walk is not touched, so no
@@ -26,8 +26,9 @@
 namespace {
 using namespace mi;
 
-// the row sources: the first three are the qtype codes of mi_gather_rows_quant
-enum { Q_FP16 = 1, Q_INT8 = 2, Q_INT16 = 3, Q_QAT = 4 };
+// the row sources: the first three are the qtype codes of mi_gather_rows_quant, Q_INT4 is MI_QTYPE_INT4_PACKED (two codes
+// per byte, PTQEmb_Int(n_bits=4, packed=True): the layout of mi_gather_rows_int4)
+enum { Q_FP16 = 1, Q_INT8 = 2, Q_INT16 = 3, Q_QAT = 4, Q_INT4 = MI_QTYPE_INT4_PACKED };
 
 constexpr int kQatBwdMaxD = MI_GATHER_FM_QAT_BWD_MAX_D;
 
@@ -46,7 +47,7 @@ template <int QT>
 __device__ __forceinline__ float src_scale(const QSrc &s) { return QT == Q_FP16 ? 1.f : s.scale[0]; }
 template <int QT>
 __device__ __forceinline__ int src_zero(const QSrc &s) {
-  if constexpr (QT == Q_INT8) return (int)reinterpret_cast<const int8_t *>(s.zero)[0];
+  if constexpr (QT == Q_INT8 || QT == Q_INT4) return (int)reinterpret_cast<const int8_t *>(s.zero)[0];      // (int4: never packed)
   else if constexpr (QT == Q_INT16) return (int)reinterpret_cast<const int16_t *>(s.zero)[0];
   else return 0;
 }
@@ -55,6 +56,7 @@ __device__ __forceinline__ int src_zero(const QSrc &s) {
 template <int QT> struct Raw { using T = uint2; };                 // int16 / fp16: one 64-bit word
 template <> struct Raw<Q_INT8> { using T = uint32_t; };            // int8: one 32-bit word
 template <> struct Raw<Q_QAT> { using T = float4; };
+template <> struct Raw<Q_INT4> { using T = uint32_t; };            // packed int4: one 16-bit word, held widened
 
 // the lane's four codes of the elements o .. o+3 (o = row D + 4 q; D % 4 == 0 and the table's base aligned to four codes:
 // the launchers check)
@@ -62,10 +64,14 @@ template <int QT>
 __device__ __forceinline__ typename Raw<QT>::T load_raw(const void *W, int64_t o) {
   if constexpr (QT == Q_INT8) return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const int8_t *>(W) + o);
   else if constexpr (QT == Q_QAT) return ld4(reinterpret_cast<const float *>(W) + o);
+  else if constexpr (QT == Q_INT4)      // o is a multiple of four: byte o / 2 is even
+    return (uint32_t)*reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(W) + (o >> 1));
   else return *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(W) + o);
 }
 
 __device__ __forceinline__ float deq(int code, int zero, float sc) { return (float)(code - zero) * sc; }
+// nibble k of a word as the two's-complement 4-bit code it is
+__device__ __forceinline__ int nibble(uint32_t w, int k) { return (int)(w << (28 - 4 * k)) >> 28; }
 __device__ __forceinline__ float half_bits(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 
 // the four values of the codes at elements e .. e+3 of emb (e numbers the draws of the rounding)
@@ -77,6 +83,9 @@ __device__ __forceinline__ float4 decode(const typename Raw<QT>::T &r, const QSr
   } else if constexpr (QT == Q_INT16) {
     return make_float4(deq((int)(int16_t)(r.x & 0xffffu), zero, sc), deq((int)(int16_t)(r.x >> 16), zero, sc),
                        deq((int)(int16_t)(r.y & 0xffffu), zero, sc), deq((int)(int16_t)(r.y >> 16), zero, sc));
+  } else if constexpr (QT == Q_INT4) {
+    return make_float4(deq(nibble(r, 0), zero, sc), deq(nibble(r, 1), zero, sc), deq(nibble(r, 2), zero, sc),
+                       deq(nibble(r, 3), zero, sc));
   } else if constexpr (QT == Q_FP16) {
     return make_float4(half_bits(r.x & 0xffffu), half_bits(r.x >> 16), half_bits(r.y & 0xffffu), half_bits(r.y >> 16));
   } else {
@@ -92,6 +101,7 @@ __device__ __forceinline__ float decode_el(const QSrc &s, int64_t o, float sc, i
   if constexpr (QT == Q_INT8) return deq((int)reinterpret_cast<const int8_t *>(s.W)[o], zero, sc);
   else if constexpr (QT == Q_INT16) return deq((int)reinterpret_cast<const int16_t *>(s.W)[o], zero, sc);
   else if constexpr (QT == Q_FP16) return __half2float(reinterpret_cast<const __half *>(s.W)[o]);
+  else if constexpr (QT == Q_INT4) return deq(nibble(reinterpret_cast<const uint8_t *>(s.W)[o >> 1], (int)(o & 1)), zero, sc);
   else {
     float qf;
     return sr_round(s, reinterpret_cast<const float *>(s.W)[o], sc, e, qf) * sc;
@@ -357,7 +367,7 @@ inline int bwd_grid(int64_t B, bool with_bias) { return grid_for_waves(B) + (wit
 // the lane's four codes are one aligned word: D = 4 * 2^k and the table's base on a four-code boundary
 inline bool codes_word_ok(const void *W, int qtype) {
   const uintptr_t p = reinterpret_cast<uintptr_t>(W);
-  return qtype == Q_INT8 ? (p & 3) == 0 : qtype == Q_QAT ? (p & 15) == 0 : (p & 7) == 0;
+  return qtype == Q_INT8 ? (p & 3) == 0 : qtype == Q_INT4 ? (p & 1) == 0 : qtype == Q_QAT ? (p & 15) == 0 : (p & 7) == 0;
 }
 
 template <int QT>
@@ -393,13 +403,16 @@ extern "C" {
 int mi_gather_fm_quant_fwd(const int64_t *idx, const int64_t *offsets, const void *Wq, int32_t qtype, const float *scale,
                            const void *zero, const float *w1, int64_t ldw1, const float *bias, float *emb_out,
                            float *yfm_out, int64_t B, int32_t F, int32_t D, int64_t N, int32_t *err, void *stream) {
-  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw1 < 1 || qtype < Q_FP16 || qtype > Q_INT16) return MI_ERR_INVALID_ARG;
+  if (B < 0 || F < 0 || D <= 0 || N < 0 || ldw1 < 1 || qtype < Q_FP16 || qtype > Q_INT4 || qtype == Q_QAT) return MI_ERR_INVALID_ARG;
+  if (qtype == Q_INT4 && (D & 1)) return MI_ERR_INVALID_ARG;      // two codes per byte: a row is D / 2 bytes
   if (B == 0) return MI_OK;
   if (!idx || !Wq || !w1 || !emb_out || !yfm_out || (qtype != Q_FP16 && (!scale || !zero))) return MI_ERR_INVALID_ARG;
   const QSrc s{Wq, scale, zero, 0.f, 0.f, nullptr, nullptr, 0};
   const char *name = "gather_fm_quant_fwd";
   if (qtype == Q_FP16)
     return launch_q_fwd<Q_FP16>(name, idx, offsets, s, w1, ldw1, bias, emb_out, yfm_out, nullptr, B, F, D, N, err, stream);
+  if (qtype == Q_INT4)
+    return launch_q_fwd<Q_INT4>(name, idx, offsets, s, w1, ldw1, bias, emb_out, yfm_out, nullptr, B, F, D, N, err, stream);
   if (qtype == Q_INT8)
     return launch_q_fwd<Q_INT8>(name, idx, offsets, s, w1, ldw1, bias, emb_out, yfm_out, nullptr, B, F, D, N, err, stream);
   return launch_q_fwd<Q_INT16>(name, idx, offsets, s, w1, ldw1, bias, emb_out, yfm_out, nullptr, B, F, D, N, err, stream);

@@ -1,14 +1,18 @@
 """DeepFM's fused lookup + FM + first-order launch on the quantised tables (csrc/gather_fm_quant.hip).
 
-gather_fm_quant: the post-training-quantised tables (PTQEmb_Int, PTQEmb_Fp16) — fp16 / int8 / int16 codes dequantised
-    inside the launch; inference only, like _kernels.gather_rows_quant.
+gather_fm_quant: the post-training-quantised tables (PTQEmb_Int, PTQEmb_Fp16) — fp16 / int8 / int16 codes, or 4-bit codes
+    packed two to a byte, dequantised inside the launch; inference only, like _kernels.gather_rows_quant.
 gather_fm_qat: the quantisation-aware-training table (QAT_EmbInt) — the fp32 rows rounded stochastically inside the launch;
     one autograd node whose backward is one row-form launch (mi_gather_fm_qat_bwd_rows) feeding _kernels._table_grads, so
     a row-form table gets COO gradients, a dense one the scatter of those values, and deterministic mode their sorted
     fixed-order sum: no float atomic on DeepFM + QAT in that mode.
 
+gather_rows_int4, ptq_quantise, int4_repack: the packed 4-bit table's row gather, the one-pass quantiser of the PTQ integer
+    tables and the int8 <-> nibble repacker (csrc/ptq_int4.hip).  A packed table is uint8 [N, D / 2]; the caller always SAYS
+    that it is packed (packed4=True with the logical D, or one of these functions): a uint8 tensor alone never means it.
+
 Buffers come from the package's float allocator (layer_dcn._new); the int64 row ids the backward needs are written by
-the forward launch into an int64 view of such a buffer.
+the forward launch into an int64 view of such a buffer, and so are the code tables the quantiser and the repacker write.
 """
 from typing import Optional
 
@@ -19,17 +23,55 @@ from . import losses as _losses
 from .layer_dcn import _int64_rows, _new
 
 QTYPES = {torch.float16: 1, torch.int8: 2, torch.int16: 3}      # the qtype codes of mi_gather_rows_quant
+QTYPE_INT4_PACKED = 5                                          # MI_QTYPE_INT4_PACKED
 QAT_BWD_MAX_D = 256                                            # MI_GATHER_FM_QAT_BWD_MAX_D
 SCALE_GRAD_MAX_BITS = 21      # the backward recovers the rounded code as rintf(emb / scale): exact for |code| <= 2^20
 
 
-def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None):
+def _packed4(W, D: int):
+    """The packed 4-bit table uint8 [N, D / 2] (include/mi355x_recsys.h, PTQEmb_Int(packed=True)) of logical width D, row-
+    contiguous."""
+    if W.dtype != torch.uint8 or W.dim() != 2:
+        raise TypeError(f"a packed 4-bit table is uint8 [N, D / 2], got {W.dtype} {tuple(W.shape)}")
+    if D % 2 or W.shape[1] * 2 != D:
+        raise ValueError(f"a packed 4-bit table of logical width {D} holds {D}/2 bytes per row, got {W.shape[1]}")
+    return W if W.is_contiguous() else W.contiguous()
+
+
+def _int8_word(zero_point):
+    if zero_point.dtype != torch.int8 or zero_point.numel() != 1:
+        raise TypeError(f"the zero point of a 4-bit table is one int8 word (it is never packed), got {zero_point.dtype}")
+    return zero_point.reshape(1)
+
+
+def _new_codes(shape, dtype, dev):
+    """A code table the launch fills, out of the float allocator like layer_dcn._int64_rows: whole float words, viewed."""
+    n = 1
+    for d in shape:
+        n *= int(d)
+    size = {torch.int8: 1, torch.uint8: 1, torch.int16: 2}[dtype]
+    return _new(((n * size + 3) // 4,), dev).view(dtype)[:n].view(shape)
+
+
+def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None, packed4: bool = False, D: Optional[int] = None):
     """(emb fp32[B, F, D], y_fm[B]) of DeepFM over a quantised table in one launch (mi_gather_fm_quant_fwd):
     emb[b, f] = dequant(Wq[idx[b, f] + offsets[f]]) — (code - zero_point) * scale for int8 / int16 codes, the value itself
     for fp16 —, y_fm the FM second-order term of emb plus the first-order bag over w1 plus bias.  offsets may be None.
-    No autograd: inference only."""
+    packed4=True with the logical width D: Wq is the packed 4-bit table uint8 [N, D / 2] of PTQEmb_Int(packed=True), the
+    zero point one int8 word; emb has the bits of the int8 table of the unpacked codes (a uint8 table is never taken for
+    packed without being told).  No autograd: inference only."""
     dev = _lib.require_gpu(idx, offsets, Wq, w1, bias, scale, zero_point)
-    qtype = QTYPES.get(Wq.dtype)
+    if packed4:
+        if D is None:
+            raise ValueError("a packed 4-bit table needs its logical width D")
+        if scale is None or zero_point is None:
+            raise ValueError("an integer table needs its scale and zero point")
+        Wq, qtype = _packed4(Wq, int(D)), QTYPE_INT4_PACKED
+        zero_point = _int8_word(zero_point)
+    else:
+        if D is not None:
+            raise ValueError("D is the logical width of a packed 4-bit table (packed4=True)")
+        qtype = QTYPES.get(Wq.dtype)
     if qtype is None:
         raise TypeError(f"unsupported quantised table dtype {Wq.dtype}")
     if Wq.dim() != 2:
@@ -37,7 +79,7 @@ def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None):
     if qtype != 1:
         if scale is None or zero_point is None:
             raise ValueError("an integer table needs its scale and zero point")
-        if zero_point.dtype != Wq.dtype:
+        if not packed4 and zero_point.dtype != Wq.dtype:
             raise TypeError(f"the zero point is held in the table's type {Wq.dtype}, got {zero_point.dtype}")
         scale = _kernels._f32c(scale.reshape(1))
         zero_point = zero_point.reshape(1)
@@ -46,7 +88,7 @@ def gather_fm_quant(idx, offsets, Wq, w1, bias, scale=None, zero_point=None):
     # (a view that is row-contiguous is read in place, wherever it starts: the launch picks the scalar kernels for a base
     #  that is not on a four-code boundary)
     Wc = Wq if Wq.is_contiguous() else Wq.contiguous()
-    N, D = Wc.shape
+    N, D = Wc.shape[0], (int(D) if packed4 else Wc.shape[1])
     with torch.no_grad():
         idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1.detach(), N)
         B, F = idx.shape
@@ -157,3 +199,81 @@ def gather_fm_qat(idx, offsets, W, scale, n_bits: int, w1, bias, *, seed: Option
     """(emb, y_fm) of DeepFM over a QAT table, one autograd node.  seed: one int64 device word (the rounding stream of
     this forward); prob: the draw itself, one value per element of emb (tests)."""
     return GatherFMQat.apply(idx, offsets, W, scale, w1, bias, int(n_bits), seed, 0, prob, sparse_W, sparse_w1)
+
+
+def gather_rows_int4(idx, W, scale, zero_point, D: int, offsets=None):
+    """Dequantising row gather over a PACKED 4-bit table (mi_gather_rows_int4): out fp32 idx.shape + (D,) with the bits of
+    _kernels.gather_rows_quant over the unpacked int8 codes.  idx None: the whole table [N, D] (row r is r, no index tensor).
+    offsets ([F], with idx [B, F]): the raw per-field ids plus their offsets inside the launch; returns (out, rows)."""
+    dev = _lib.require_gpu(idx, W, scale, zero_point, offsets)
+    Wc = _packed4(W, int(D))
+    N = Wc.shape[0]
+    sc, zp = _kernels._f32c(scale.reshape(1)), _int8_word(zero_point)
+    rows, F = None, 1
+    if idx is None:
+        if offsets is not None:
+            raise ValueError("the table form takes no offsets")
+        idxc, n, shape = None, N, (N,)
+    else:
+        idxc = _kernels._i64c(idx)
+        n, shape = idxc.numel(), tuple(idx.shape)
+        if offsets is not None:
+            offsets = _kernels._i64c(offsets.reshape(-1))
+            F = offsets.numel()
+            if idxc.dim() != 2 or idxc.shape[1] != F:
+                raise ValueError(f"offsets of {F} fields need ids [B, {F}], got {shape}")
+            rows = _int64_rows(shape[0], F, dev)
+    out = _new(shape + (int(D),), dev)
+    _lib.check(
+        _lib.load().mi_gather_rows_int4(_lib.ptr(idxc), _lib.ptr(offsets), Wc.data_ptr(), sc.data_ptr(), zp.data_ptr(),
+                                        out.data_ptr(), _lib.ptr(rows), n, F, int(D), N, _lib.err_word(dev).data_ptr(),
+                                        _lib.stream_ptr(dev)),
+        "mi_gather_rows_int4",
+    )
+    return out if offsets is None else (out, rows)
+
+
+def ptq_quantise(table, scale, zero_point, n_bits: int, packed: bool = False):
+    """The codes of the fp32 table [N, D] (a view of any row stride is read in place) under a given scale and zero point —
+    device scalars: fp32, and the storage type's — in one launch (mi_ptq_quantise): int8 [N, D] (n_bits 4, 8), int16 [N, D]
+    (16) or, packed, uint8 [N, D / 2].  The arithmetic of embeddings.ptq_emb.affine_codes, bit for bit."""
+    dev = _lib.require_gpu(table, scale, zero_point)
+    if table.dtype != torch.float32 or table.dim() != 2:
+        raise TypeError(f"the table must be fp32 [N, D], got {table.dtype} {tuple(table.shape)}")
+    storage = torch.int16 if n_bits == 16 else torch.int8
+    if zero_point.dtype != storage or zero_point.numel() != 1:
+        raise TypeError(f"the zero point of an n_bits = {n_bits} table is one {storage} word, got {zero_point.dtype}")
+    N, D = table.shape
+    if packed and (n_bits != 4 or D % 2):
+        raise ValueError("packing takes n_bits = 4 and an even width")
+    if (D > 1 and table.stride(1) != 1) or (N > 1 and table.stride(0) < D):
+        table = table.contiguous()
+    ldw = table.stride(0) if N > 1 else D
+    out = _new_codes((N, D // 2) if packed else (N, D), torch.uint8 if packed else storage, dev)
+    _lib.check(
+        _lib.load().mi_ptq_quantise(table.data_ptr(), ldw, _kernels._f32c(scale.reshape(1)).data_ptr(), zero_point.data_ptr(),
+                                    int(n_bits), int(packed), out.data_ptr(), N, D, _lib.stream_ptr(dev)),
+        "mi_ptq_quantise",
+    )
+    return out
+
+
+def int4_repack(W, D: int, unpack: bool):
+    """int8 codes [N, D] -> packed uint8 [N, D / 2] (unpack False), or back (mi_int4_repack).  A code outside [-8, 7] is
+    refused through the error word (_lib.check_index_errors raises ValueError): nothing is read back here."""
+    dev = _lib.require_gpu(W)
+    D = int(D)
+    if unpack:
+        src = _packed4(W, D)
+        out = _new_codes((src.shape[0], D), torch.int8, dev)
+    else:
+        if W.dtype != torch.int8 or W.dim() != 2 or W.shape[1] != D or D % 2:
+            raise ValueError(f"packing takes int8 codes [N, D] of an even D = {D}, got {W.dtype} {tuple(W.shape)}")
+        src = W.contiguous()
+        out = _new_codes((src.shape[0], D // 2), torch.uint8, dev)
+    _lib.check(
+        _lib.load().mi_int4_repack(src.data_ptr(), out.data_ptr(), int(unpack), src.shape[0], D,
+                                   _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
+        "mi_int4_repack",
+    )
+    return out
