@@ -374,8 +374,17 @@ MI_API int mi_dual_gather_bwd(const int64_t *idx, const float *g_out, const floa
  * zero-fill.  gT1 (dense) is added to (caller-zeroed) as above, EXCEPT in the joined form below.
  * workspace (nullable): mi_dual_gather_bwd_rows_workspace_elems(De, n1) floats (0: this shape has no use for one) whose first
  * word is ZERO on entry (the kernel leaves it zero): table 1's per-workgroup sums are then joined by the last workgroup to
- * arrive, in a fixed order, instead of by same-address float atomics — and gT1 is WRITTEN, not added to (no zero fill
- * needed), whenever a workspace is passed and mi_dual_gather_bwd_rows_overwrites(De, n1) != 0 (16-byte aligned operands). */
+ * arrive, in a fixed order, instead of by same-address float atomics — and gT1 is WRITTEN, not added to.  Which of the
+ * three forms a launch takes is the library's decision alone: ask mi_dual_gather_bwd_rows_form with the operands the launch
+ * will get (it reads addresses and shapes and dereferences nothing).
+ * ONLY MI_DUAL_ROWS_FORM_WORKSPACE lets the caller skip zeroing gT1; the other two forms add into it.
+ * mi_dual_gather_bwd_rows_overwrites(De, n1) != 0: the shape reaches MI_DUAL_ROWS_FORM_WORKSPACE when a workspace is passed
+ * and the operands are aligned — a shape rule only, not an answer for a launch. */
+#define MI_DUAL_ROWS_FORM_ELEMENT 0   /* element-per-thread kernel; adds into gT1 */
+#define MI_DUAL_ROWS_FORM_ATOMIC 1    /* float4 kernel, workgroup sums joined by float atomics; adds into gT1 */
+#define MI_DUAL_ROWS_FORM_WORKSPACE 2 /* float4 kernel, workgroup sums joined through the workspace; writes gT1 */
+MI_API int32_t mi_dual_gather_bwd_rows_form(const float *g_out, const float *T1, const float *T2, const float *g2vals,
+                                            const float *workspace, int32_t De, int64_t n1);
 MI_API int32_t mi_dual_gather_bwd_rows_overwrites(int32_t De, int64_t n1);
 MI_API int64_t mi_dual_gather_bwd_rows_workspace_elems(int32_t De, int64_t n1);
 MI_API int mi_dual_gather_bwd_rows(const int64_t *idx, const float *g_out, const float *T1, const float *T2, float *gT1,

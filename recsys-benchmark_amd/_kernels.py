@@ -559,25 +559,43 @@ OPS = {"mult": 0, "add": 1, "cat": 2}
 XF_NONE, XF_SOFT, XF_MASK = 0, 1, 2
 
 
+def _byte_mask(m: torch.Tensor) -> torch.Tensor:
+    return m.contiguous().view(torch.uint8) if m.dtype in (torch.bool, torch.uint8) else m.to(torch.uint8).contiguous()
+
+
+def _dual_operands(T1, T2, S1, S2, M1, M2, what: str = "dual_gather"):
+    """(T1, T2, S1, S2, M1, M2, xform, De, n1, n2) as every launch of the two-table family (QR, CERP, CERP retrain) reads
+    them: contiguous fp32 tables [n1, De] and [n2, De]; XF_SOFT with the threshold logits S1 / S2 or XF_MASK with the
+    masks M1 / M2, each shaped like its table, else XF_NONE.  A bool or uint8 mask is read in place (a bool is one byte,
+    0 or 1); a mask of another dtype is converted."""
+    if (S1 is None) != (S2 is None) or (M1 is None) != (M2 is None):
+        raise ValueError(f"{what}: the thresholds S1 / S2 (and the masks M1 / M2) come in pairs")
+    if S1 is not None and M1 is not None:
+        raise ValueError(f"{what}: soft (S1 / S2) and mask (M1 / M2) exclude each other")
+    s1, s2 = T1.shape, T2.shape
+    if len(s1) != 2 or len(s2) != 2 or s1[1] != s2[1]:
+        raise ValueError(f"{what}: both tables must share the row width, got {tuple(s1)} and {tuple(s2)}")
+    for name, t, shape in (("S1", S1, s1), ("S2", S2, s2), ("M1", M1, s1), ("M2", M2, s2)):
+        if t is not None and t.shape != shape:
+            raise ValueError(f"{what}: {name} must be shaped like its table {tuple(shape)}, got {tuple(t.shape)}")
+    if S1 is not None:
+        return _f32c(T1), _f32c(T2), _f32c(S1), _f32c(S2), None, None, XF_SOFT, s1[1], s1[0], s2[0]
+    if M1 is not None:
+        return _f32c(T1), _f32c(T2), None, None, _byte_mask(M1), _byte_mask(M2), XF_MASK, s1[1], s1[0], s2[0]
+    return _f32c(T1), _f32c(T2), None, None, None, None, XF_NONE, s1[1], s1[0], s2[0]
+
+
 class DualGather(torch.autograd.Function):
     """out = T1'[idx % mod1] (op) T2'[idx // div2]  (mi_dual_gather_fwd / _bwd)."""
 
     @staticmethod
-    def forward(ctx, idx, T1, T2, S1, S2, M1, M2, mod1: int, div2: int, op: int, xform: int, fields=None, sparse2: bool = False,
-                offsets=None):
+    def forward(ctx, idx, T1, T2, S1, S2, M1, M2, mod1: int, div2: int, op: int, fields=None, sparse2: bool = False, offsets=None):
         """offsets ([F], optional): idx holds the model's raw per-field ids and the per-field row offsets are added inside
         the lookup; the second output is then the row ids idx + offsets (int64, not differentiable)."""
         dev = _lib.require_gpu(idx, T1, T2)
         idxc = _i64c(idx)
-        T1c, T2c = _f32c(T1), _f32c(T2)
-        S1c = None if S1 is None else _f32c(S1)
-        S2c = None if S2 is None else _f32c(S2)
-        M1c = None if M1 is None else M1.to(torch.uint8).contiguous()
-        M2c = None if M2 is None else M2.to(torch.uint8).contiguous()
+        T1c, T2c, S1c, S2c, M1c, M2c, xform, De, n1, n2 = _dual_operands(T1, T2, S1, S2, M1, M2)
         n = idxc.numel()
-        De = T1c.shape[1]
-        if T2c.shape[1] != De:
-            raise ValueError("both tables must share the row width")
         F = idx.shape[1] if idx.dim() == 2 else 1
         if op == OPS["cat"]:
             if idx.dim() == 1:
@@ -598,7 +616,7 @@ class DualGather(torch.autograd.Function):
         _lib.check(
             _lib.load().mi_dual_gather_fwd_off(
                 idxc.data_ptr(), _lib.ptr(offs) if rows is not None else None, _lib.ptr(rows), T1c.data_ptr(), T2c.data_ptr(),
-                _lib.ptr(S1c), _lib.ptr(S2c), _lib.ptr(M1c), _lib.ptr(M2c), out.data_ptr(), n, F, De, T1c.shape[0], T2c.shape[0],
+                _lib.ptr(S1c), _lib.ptr(S2c), _lib.ptr(M1c), _lib.ptr(M2c), out.data_ptr(), n, F, De, n1, n2,
                 mod1, div2, op, xform, _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)),
             "mi_dual_gather_fwd_off",
         )
@@ -619,37 +637,45 @@ class DualGather(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_rows=None):
         if g is None:                # (materialisation is off when the row ids are a second output: nothing flowed back)
-            return (None,) * 14
-        idxc, T1c, T2c, S1c, S2c, M1c, M2c = ctx.saved_tensors
+            return (None,) * 13
+        idxc, *tables = ctx.saved_tensors
         n, F, De, mod1, div2, op, xform = ctx.meta
-        dev = g.device
         _no_atomics_promised("the two-table (QR / CERP) gather backward")
-        g = _f32c(g)
-        if ctx.sparse2:
-            # table 2 (the quotient table: ~N / divider rows) gets its gradient in ROW form: one value row per lookup, no
-            # atomics into scattered rows and no [n2, De] zero-fill; table 1 (divider rows) stays dense
-            ws = _dual_rows_workspace(dev, De, T1c.shape[0])
-            g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
-            gT1 = _dual_rows_grad1(ws, De, T1c, g, T2c, g2vals)
-            rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
-            _lib.check(_lib.load().mi_dual_gather_bwd_rows(idxc.data_ptr(), g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), gT1.data_ptr(),
-                                                           g2vals.data_ptr(), rows2.data_ptr(), n, F, De, T1c.shape[0], T2c.shape[0],
-                                                           mod1, div2, op, _lib.ptr(ws), _lib.stream_ptr(dev)), "mi_dual_gather_bwd_rows")
-            # (ids out of range carry row 0 and a zero value row: they add nothing)
-            return None, gT1, _coo(rows2, g2vals, ctx.t2_shape), None, None, None, None, None, None, None, None, None, None, None
-        gT1, gT2 = torch.zeros_like(T1c), torch.zeros_like(T2c)
-        gS1 = torch.zeros_like(S1c) if xform == XF_SOFT else None
-        gS2 = torch.zeros_like(S2c) if xform == XF_SOFT else None
-        small, row0, flags = (ctx.fields[0], ctx.fields[1], ctx.fields[2]) if ctx.fields is not None else (None, None, None)
-        _lib.check(
-            _lib.load().mi_dual_gather_bwd_fields(
-                idxc.data_ptr(), g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
-                _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1), _lib.ptr(gS2),
-                n, F, De, T1c.shape[0], T2c.shape[0], mod1, div2, op, xform, _lib.ptr(small),
-                small.numel() if small is not None else 0, _lib.ptr(row0), _lib.ptr(flags), _lib.stream_ptr(dev)),
-            "mi_dual_gather_bwd_fields",
-        )
-        return None, gT1, gT2, gS1, gS2, None, None, None, None, None, None, None, None, None
+        ops = (*tables, xform, De, tables[0].shape[0], tables[1].shape[0])
+        grads = _dual_scatter_backward(idxc, _f32c(g), ops, n, F, op, mod1, div2, ctx.fields, ctx.sparse2, ctx.t2_shape)
+        return (None,) + grads + (None,) * 8
+
+
+def _dual_scatter_backward(ids, g, ops, n: int, F: int, op: int, mod1: int, div2: int, fields, rows_form: bool, t2_shape):
+    """(gT1, gT2, gS1, gS2) of n two-table lookups in default mode (float atomics): ids int64 [n], g their upstream
+    gradient rows (fp32, contiguous), ops as _dual_operands returns them, fields the small-field hint or None."""
+    T1c, T2c, S1c, S2c, M1c, M2c, xform, De, n1, n2 = ops
+    lib, dev = _lib.load(), g.device
+    if rows_form:
+        # table 2 (the quotient table: ~N / divider rows) gets its gradient in ROW form: one value row per lookup, no
+        # atomics into scattered rows and no [n2, De] zero-fill; table 1 (divider rows) stays dense
+        ws = _dual_rows_workspace(dev, De, n1)
+        g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
+        gT1 = _dual_rows_grad1(ws, De, T1c, g, T2c, g2vals)
+        rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
+        _lib.check(lib.mi_dual_gather_bwd_rows(ids.data_ptr(), g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), gT1.data_ptr(),
+                                               g2vals.data_ptr(), rows2.data_ptr(), n, F, De, n1, n2, mod1, div2, op,
+                                               _lib.ptr(ws), _lib.stream_ptr(dev)), "mi_dual_gather_bwd_rows")
+        # (ids out of range carry row 0 and a zero value row: they add nothing)
+        return gT1, _coo(rows2, g2vals, t2_shape), None, None
+    gT1, gT2 = torch.zeros_like(T1c), torch.zeros_like(T2c)
+    gS1 = torch.zeros_like(S1c) if xform == XF_SOFT else None
+    gS2 = torch.zeros_like(S2c) if xform == XF_SOFT else None
+    small, row0, flags = fields[:3] if fields is not None else (None, None, None)
+    _lib.check(
+        lib.mi_dual_gather_bwd_fields(
+            ids.data_ptr(), g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
+            _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1), _lib.ptr(gS2),
+            n, F, De, n1, n2, mod1, div2, op, xform, _lib.ptr(small),
+            small.numel() if small is not None else 0, _lib.ptr(row0), _lib.ptr(flags), _lib.stream_ptr(dev)),
+        "mi_dual_gather_bwd_fields",
+    )
+    return gT1, gT2, gS1, gS2
 
 
 _DUAL_WS = {}
@@ -665,14 +691,16 @@ def _dual_rows_workspace(dev, De: int, n1: int):
     return _DUAL_WS[key]
 
 
+DUAL_ROWS_FORM_WORKSPACE = 2      # MI_DUAL_ROWS_FORM_WORKSPACE
+
+
 def _dual_rows_grad1(ws, De: int, T1c, g, T2c, g2vals):
-    """The buffer mi_dual_gather_bwd_rows gets for table 1's dense gradient.  With the workspace the last workgroup of the
-    float4 kernel WRITES it (no zero fill) — but the library takes that kernel only when the shape qualifies
-    (mi_dual_gather_bwd_rows_overwrites) AND g, T1, T2 and g2vals are 16-byte aligned, and otherwise falls back to the
-    kernel that ADDS into it.  A contiguous view need not be aligned (the slice of a flat gradient that cat's backward
-    hands over is not), so the choice made here asks for everything the dispatch of csrc/embed.hip asks for."""
-    written = (ws is not None and _lib.load().mi_dual_gather_bwd_rows_overwrites(De, T1c.shape[0]) != 0
-               and all(t.data_ptr() % 16 == 0 for t in (g, T1c, T2c, g2vals)))
+    """The buffer mi_dual_gather_bwd_rows gets for table 1's dense gradient: the library says which form a launch with
+    these operands takes (mi_dual_gather_bwd_rows_form), and only the form joined through the workspace WRITES gT1; the
+    other two add into it.  (No lookup: nothing is launched and nothing written.)"""
+    written = (ws is not None and g2vals.shape[0] > 0
+               and _lib.load().mi_dual_gather_bwd_rows_form(g.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), g2vals.data_ptr(),
+                                                            ws.data_ptr(), De, T1c.shape[0]) == DUAL_ROWS_FORM_WORKSPACE)
     return torch.empty_like(T1c) if written else torch.zeros_like(T1c)
 
 
@@ -704,8 +732,7 @@ def dual_gather(idx, T1, T2, mod1, div2, op="add", S1=None, S2=None, M1=None, M2
     """fields (optional): small_field_hint(...) — lets the backward sum the gradient of low-cardinality fields per field
     instead of with thousands of same-address atomics; same result up to the order of float additions.
     offsets (optional, [F]): idx holds raw per-field ids; returns (out, idx + offsets), the addition done by the lookup."""
-    xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
-    return DualGather.apply(idx, T1, T2, S1, S2, M1, M2, int(mod1), int(div2), OPS[op], xform, fields, bool(sparse2), offsets)
+    return DualGather.apply(idx, T1, T2, S1, S2, M1, M2, int(mod1), int(div2), OPS[op], fields, bool(sparse2), offsets)
 
 
 class DualTable(torch.autograd.Function):
@@ -713,17 +740,12 @@ class DualTable(torch.autograd.Function):
     tensor; the backward writes every gradient element once, in a fixed order, without atomics."""
 
     @staticmethod
-    def forward(ctx, T1, T2, S1, S2, M1, M2, N: int, mod1: int, div2: int, op: int, xform: int):
+    def forward(ctx, T1, T2, S1, S2, M1, M2, N: int, mod1: int, div2: int, op: int):
         dev = _lib.require_gpu(T1, T2)
-        T1c, T2c = _f32c(T1), _f32c(T2)
-        S1c = None if S1 is None else _f32c(S1)
-        S2c = None if S2 is None else _f32c(S2)
-        M1c = None if M1 is None else M1.to(torch.uint8).contiguous()
-        M2c = None if M2 is None else M2.to(torch.uint8).contiguous()
-        De = T1c.shape[1]
+        T1c, T2c, S1c, S2c, M1c, M2c, xform, De, n1, n2 = _dual_operands(T1, T2, S1, S2, M1, M2, "dual_table")
         out = torch.empty((N, 2 * De if op == OPS["cat"] else De), dtype=torch.float32, device=dev)
         _lib.check(_lib.load().mi_dual_table_fwd(T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c), _lib.ptr(M1c),
-                                                 _lib.ptr(M2c), out.data_ptr(), N, De, T1c.shape[0], T2c.shape[0], mod1, div2,
+                                                 _lib.ptr(M2c), out.data_ptr(), N, De, n1, n2, mod1, div2,
                                                  op, xform, _lib.stream_ptr(dev)), "mi_dual_table_fwd")
         ctx.save_for_backward(T1c, T2c, S1c, S2c, M1c, M2c)
         ctx.meta = (N, De, mod1, div2, op, xform)
@@ -746,35 +768,38 @@ class DualTable(torch.autograd.Function):
                                          _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1),
                                          _lib.ptr(gS2), N, De, T1c.shape[0], T2c.shape[0], mod1, div2, op, xform, _lib.ptr(ws),
                                          _lib.stream_ptr(dev)), "mi_dual_table_bwd")
-        return gT1, gT2, gS1, gS2, None, None, None, None, None, None, None
+        return gT1, gT2, gS1, gS2, None, None, None, None, None, None
 
 
 def dual_table_supported(N: int, mod1: int, div2: int, *tables) -> bool:
     """Whether mi_dual_table_* takes this shape (csrc/dual_table.hip, fill(): float4 rows of 16-byte aligned fp32 tables
     on the GPU, 32-bit element counters); otherwise the caller keeps `dual_gather` over an explicit arange(N).
-    tables: T1, T2 and, where the transform has them, the logits or masks."""
-    T1, T2 = tables[0], tables[1]
-    De = T1.shape[1] if T1.dim() == 2 else 0
-    if not (T1.is_cuda and T2.dim() == 2 and De % 4 == 0 and 4 <= De <= 1024 and N >= 0 and mod1 > 0 and div2 > 0):
+    tables: T1, T2 and, where the transform has them, the logits or masks — judged as the launch would read them."""
+    pair, none = tuple(tables[2:]) or (None, None), (None, None)
+    S, M = (pair, none) if pair[0] is not None and pair[0].is_floating_point() else (none, pair)
+    try:
+        *tables, _xform, De, n1, n2 = _dual_operands(tables[0], tables[1], *S, *M, "dual_table")
+    except (TypeError, ValueError):        # (a dtype or a shape the family refuses)
+        return False
+    if not (tables[0].is_cuda and De % 4 == 0 and 4 <= De <= 1024 and N >= 0 and mod1 > 0 and div2 > 0):
         return False
 
     def chunks(contributors):          # kLongRow / kChunk of the kernel
         return -(-contributors // 8) if contributors > 16 else 1
 
-    items = T1.shape[0] * chunks(-(-N // mod1)) + T2.shape[0] * chunks(min(div2, N))
-    if max(2 * N * De, items * De, T1.shape[0], T2.shape[0], mod1, div2) >= 2 ** 31:
+    items = n1 * chunks(-(-N // mod1)) + n2 * chunks(min(div2, N))
+    if max(2 * N * De, items * De, n1, n2, mod1, div2) >= 2 ** 31:
         return False
-    if T1.shape[0] < min(N, mod1) or T2.shape[0] < -(-N // div2):
+    if n1 < min(N, mod1) or n2 < -(-N // div2):
         return False                   # (tables that cannot cover N rows: the lookup flags those ids)
-    return all(t is None or (t.dim() == 2 and t.shape[1] == De and t.data_ptr() % 16 == 0) for t in tables)
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tables)
 
 
 def dual_table(T1, T2, N, mod1, div2, op="add", S1=None, S2=None, M1=None, M2=None):
     """The two-table family's whole table [N, De] ([N, 2 De] for cat): `dual_gather(arange(N), ...)` bit for bit, without
     the index tensor, and with a backward that has no atomics and no zero fill (gradients differ from dual_gather's in
     the order of the float additions only).  Check `dual_table_supported` first."""
-    xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
-    return DualTable.apply(T1, T2, S1, S2, M1, M2, int(N), int(mod1), int(div2), OPS[op], xform)
+    return DualTable.apply(T1, T2, S1, S2, M1, M2, int(N), int(mod1), int(div2), OPS[op])
 
 
 # --------------------------------------------------------------------------------------
@@ -812,34 +837,19 @@ class GatherFMDual(torch.autograd.Function):
                 sparse2: bool, sparse_w1: bool, fields):
         dev = _lib.require_gpu(idx, offsets, T1, T2, w1, bias, S1, S2, M1, M2)
         lib = _lib.load()
-        if (S1 is None) != (S2 is None) or (M1 is None) != (M2 is None):
-            raise ValueError("gather_fm_dual: the thresholds S1 / S2 (and the masks M1 / M2) come in pairs")
-        if S1 is not None and M1 is not None:
-            raise ValueError("gather_fm_dual: soft (S1 / S2) and mask (M1 / M2) exclude each other")
         if op == OPS["cat"]:
             raise NotImplementedError('gather_fm_dual: "cat" changes the field count; it keeps dual_gather + fm_first_order')
-        xform = XF_SOFT if S1 is not None else (XF_MASK if M1 is not None else XF_NONE)
-        if op == OPS["mult"] and xform != XF_NONE:
-            raise NotImplementedError("gather_fm_dual: mult goes with untransformed tables only")
-        if T1.dim() != 2 or T2.dim() != 2 or T1.shape[1] != T2.shape[1]:
-            raise ValueError(f"gather_fm_dual: both tables must share the row width, got {tuple(T1.shape)} and {tuple(T2.shape)}")
-        for name, t, table in (("S1", S1, T1), ("S2", S2, T2), ("M1", M1, T1), ("M2", M2, T2)):
-            if t is not None and tuple(t.shape) != tuple(table.shape):
-                raise ValueError(f"gather_fm_dual: {name} must be shaped like its table {tuple(table.shape)}, got {tuple(t.shape)}")
         for name, m in (("M1", M1), ("M2", M2)):
             if m is not None and m.dtype not in (torch.bool, torch.uint8):
                 raise ValueError(f"gather_fm_dual: {name} must be bool or uint8, got {m.dtype}")
+        T1c, T2c, S1c, S2c, M1c, M2c, xform, De, n1, n2 = _dual_operands(T1, T2, S1, S2, M1, M2, "gather_fm_dual")
+        if op == OPS["mult"] and xform != XF_NONE:
+            raise NotImplementedError("gather_fm_dual: mult goes with untransformed tables only")
         if xform == XF_SOFT and (sparse1 or sparse2):
             raise ValueError("gather_fm_dual: a soft-thresholded table has no row-form gradient")
-        De = int(T1.shape[1])
         if De > DUAL_FM_MAX_D:
             raise NotImplementedError(f"gather_fm_dual covers De <= {DUAL_FM_MAX_D}, got {De}")
         idx, offsets, w1c, ldw1, N = _lookup_operands(idx, offsets, w1)
-        T1c, T2c = _f32c(T1), _f32c(T2)
-        S1c = None if S1 is None else _f32c(S1)
-        S2c = None if S2 is None else _f32c(S2)
-        M1c = None if M1 is None else M1.contiguous().view(torch.uint8)      # (a bool is one byte, 0 or 1: read in place)
-        M2c = None if M2 is None else M2.contiguous().view(torch.uint8)
         B, F = idx.shape
         emb = torch.empty((B, F, De), dtype=torch.float32, device=dev)
         yfm = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -853,7 +863,7 @@ class GatherFMDual(torch.autograd.Function):
             lib.mi_gather_fm_dual_fwd(
                 idx.data_ptr(), offsets.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
                 _lib.ptr(M1c), _lib.ptr(M2c), w1c.data_ptr(), ldw1, _lib.ptr(bias), emb.data_ptr(), yfm.data_ptr(),
-                rows.data_ptr(), _lib.ptr(rows_bwd), B, F, De, N, T1c.shape[0], T2c.shape[0], int(mod1), int(div2), op, xform,
+                rows.data_ptr(), _lib.ptr(rows_bwd), B, F, De, N, n1, n2, int(mod1), int(div2), op, xform,
                 _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev),
             ),
             "mi_gather_fm_dual_fwd",
@@ -922,28 +932,9 @@ class GatherFMDual(torch.autograd.Function):
             _lib.check(lib.mi_gather_fm_bwd_rows(emb.data_ptr(), g_y.data_ptr(), _lib.ptr(g_emb), dE.data_ptr(),
                                                  g1vals.data_ptr(), _lib.ptr(gb), B, F, De, stream), "mi_gather_fm_bwd_rows")
             if need_T1 or need_T2 or need_S:
-                if qr_rows:
-                    ws = _dual_rows_workspace(dev, De, n1)
-                    g2vals = torch.empty((n, De), dtype=torch.float32, device=dev)
-                    gT1 = _dual_rows_grad1(ws, De, T1c, dE, T2c, g2vals)
-                    rows2 = torch.empty((n,), dtype=torch.int64, device=dev)
-                    _lib.check(lib.mi_dual_gather_bwd_rows(ids.data_ptr(), dE.data_ptr(), T1c.data_ptr(), T2c.data_ptr(),
-                                                           gT1.data_ptr(), g2vals.data_ptr(), rows2.data_ptr(), n, F, De, n1, n2,
-                                                           mod1, div2, op, _lib.ptr(ws), stream), "mi_dual_gather_bwd_rows")
-                    gT2 = _coo(rows2, g2vals, T2shape)
-                else:
-                    gT1, gT2 = torch.zeros_like(T1c), torch.zeros_like(T2c)
-                    gS1 = torch.zeros_like(S1c) if xform == XF_SOFT else None
-                    gS2 = torch.zeros_like(S2c) if xform == XF_SOFT else None
-                    small, row0, flags = ctx.fields[:3] if ctx.fields is not None else (None, None, None)
-                    _lib.check(
-                        lib.mi_dual_gather_bwd_fields(
-                            ids.data_ptr(), dE.data_ptr(), T1c.data_ptr(), T2c.data_ptr(), _lib.ptr(S1c), _lib.ptr(S2c),
-                            _lib.ptr(M1c), _lib.ptr(M2c), gT1.data_ptr(), gT2.data_ptr(), _lib.ptr(gS1), _lib.ptr(gS2),
-                            n, F, De, n1, n2, mod1, div2, op, xform, _lib.ptr(small),
-                            small.numel() if small is not None else 0, _lib.ptr(row0), _lib.ptr(flags), stream),
-                        "mi_dual_gather_bwd_fields",
-                    )
+                ops = (T1c, T2c, S1c, S2c, M1c, M2c, xform, De, n1, n2)
+                gT1, gT2, gS1, gS2 = _dual_scatter_backward(ids, dE, ops, n, F, op, mod1, div2, ctx.fields, qr_rows, T2shape)
+                if not qr_rows:
                     gT1, gT2 = gT1.view(T1shape), gT2.view(T2shape)
         else:
             # ---- row values and keys, then fixed-order sums per table row: no float atomics

@@ -731,6 +731,40 @@ inline int grid_for_elems(int64_t total) {
   return (int)g;
 }
 
+// ---- host glue of the two-table lookups (mi_dual_gather_fwd_off, _bwd_rows, _bwd_fields)
+// What the three entry points open with: the sign checks, the op and xform ranges, the n == 0 return, the operands that may
+// not be null (`own`: the entry's own ones, all present; the thresholds and masks go with xform), and the tables as the
+// kernels take them.  false: the entry returns `rc` at once.
+inline bool dual_entry(int &rc, DualTables &t, bool own, const float *T1, const float *T2, const float *S1, const float *S2,
+                       const uint8_t *M1, const uint8_t *M2, int64_t n, int F, int De, int64_t n1, int64_t n2, int64_t mod1,
+                       int64_t div2, int op, int xform) {
+  rc = MI_ERR_INVALID_ARG;
+  if (n < 0 || F <= 0 || De <= 0 || n1 <= 0 || n2 <= 0 || mod1 <= 0 || div2 <= 0) return false;
+  if (op < OP_MULT || op > OP_CAT || xform < XF_NONE || xform > XF_MASK) return false;
+  if (n == 0) { rc = MI_OK; return false; }
+  if (!own || !T1 || !T2) return false;
+  if (xform == XF_SOFT && (!S1 || !S2)) return false;
+  if (xform == XF_MASK && (!M1 || !M2)) return false;
+  t = DualTables{T1, T2, S1, S2, M1, M2, n1, n2, mod1, div2};
+  rc = MI_OK;
+  return true;
+}
+
+// The form rule of mi_dual_gather_bwd_rows — the ONLY place that decides which kernel a row-form backward runs and what it
+// does to gT1 (MI_DUAL_ROWS_FORM_* of the header; mi_dual_gather_bwd_rows_form hands it to callers).  Shapes first:
+// k_dual_bwd_rows4 takes float4 rows and keeps one register row per row of table 1 ...
+inline bool dual_rows4_shape(int De, int64_t n1) { return n1 >= 1 && n1 <= 4 && vec_ok(De); }
+// ... the workspace holds the n1 * De sums of every workgroup when they fit one workgroup's threads ...
+inline bool dual_rows_ws_fits(int De, int64_t n1) { return n1 >= 1 && n1 <= 4 && De > 0 && n1 * De <= kBlock; }
+// ... and the last workgroup can join them when they tile it
+inline bool dual_rows_ws_joins(int De, int64_t n1) { return dual_rows_ws_fits(De, n1) && kBlock % (n1 * De) == 0; }
+
+inline int dual_rows_form(int De, int64_t n1, const float *g_out, const float *T1, const float *T2, const float *g2vals,
+                          const float *workspace) {
+  if (!dual_rows4_shape(De, n1) || !all_aligned16(g_out, T1, T2, g2vals)) return MI_DUAL_ROWS_FORM_ELEMENT;
+  return workspace && dual_rows_ws_joins(De, n1) ? MI_DUAL_ROWS_FORM_WORKSPACE : MI_DUAL_ROWS_FORM_ATOMIC;
+}
+
 }  // namespace
 
 extern "C" {
@@ -747,15 +781,11 @@ int mi_dual_gather_fwd_off(const int64_t *idx, const int64_t *offsets, int64_t *
                            const float *S1, const float *S2, const uint8_t *M1, const uint8_t *M2, float *out, int64_t n,
                            int32_t F, int32_t De, int64_t n1, int64_t n2, int64_t mod1, int64_t div2, int32_t op,
                            int32_t xform, int32_t *err, void *stream) {
-  if (n < 0 || F <= 0 || De <= 0 || n1 <= 0 || n2 <= 0 || mod1 <= 0 || div2 <= 0) return MI_ERR_INVALID_ARG;
-  if (op < OP_MULT || op > OP_CAT || xform < XF_NONE || xform > XF_MASK) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  if (!idx || !T1 || !T2 || !out) return MI_ERR_INVALID_ARG;
-  if (xform == XF_SOFT && (!S1 || !S2)) return MI_ERR_INVALID_ARG;
-  if (xform == XF_MASK && (!M1 || !M2)) return MI_ERR_INVALID_ARG;
+  int rc;
+  DualTables t;
+  if (!dual_entry(rc, t, idx && out, T1, T2, S1, S2, M1, M2, n, F, De, n1, n2, mod1, div2, op, xform)) return rc;
   if (op == OP_CAT && n % F != 0) return MI_ERR_INVALID_ARG;
   if (offsets && (n % F != 0 || !rows_out)) return MI_ERR_INVALID_ARG;
-  DualTables t{T1, T2, S1, S2, M1, M2, n1, n2, mod1, div2};
   const bool al = aligned16(T1) && aligned16(T2) && aligned16(out) && (xform != XF_SOFT || (aligned16(S1) && aligned16(S2))) &&
                   (xform != XF_MASK || (((uintptr_t)M1 & 3) == 0 && ((uintptr_t)M2 & 3) == 0));
   if (vec_ok(De) && al) {
@@ -786,25 +816,27 @@ int mi_dual_gather_bwd(const int64_t *idx, const float *g_out, const float *T1, 
                                    nullptr, 0, nullptr, nullptr, stream);
 }
 
-int32_t mi_dual_gather_bwd_rows_overwrites(int32_t De, int64_t n1) {
-  return n1 >= 1 && n1 <= 4 && De > 0 && De % 4 == 0 && De <= 256 && ((De / 4) & (De / 4 - 1)) == 0 && n1 * De <= kBlock &&
-         kBlock % (n1 * De) == 0;
-}
+int32_t mi_dual_gather_bwd_rows_overwrites(int32_t De, int64_t n1) { return dual_rows4_shape(De, n1) && dual_rows_ws_joins(De, n1); }
 
 int64_t mi_dual_gather_bwd_rows_workspace_elems(int32_t De, int64_t n1) {
-  return (n1 >= 1 && n1 <= 4 && De > 0 && n1 * De <= kBlock) ? 1 + (int64_t)512 * n1 * De : 0;
+  return dual_rows_ws_fits(De, n1) ? 1 + (int64_t)512 * n1 * De : 0;
+}
+
+int32_t mi_dual_gather_bwd_rows_form(const float *g_out, const float *T1, const float *T2, const float *g2vals,
+                                     const float *workspace, int32_t De, int64_t n1) {
+  return dual_rows_form(De, n1, g_out, T1, T2, g2vals, workspace);
 }
 
 int mi_dual_gather_bwd_rows(const int64_t *idx, const float *g_out, const float *T1, const float *T2, float *gT1,
                             float *g2vals, int64_t *rows2, int64_t n, int32_t F, int32_t De, int64_t n1, int64_t n2,
                             int64_t mod1, int64_t div2, int32_t op, float *workspace, void *stream) {
-  if (n < 0 || F <= 0 || De <= 0 || n1 <= 0 || n2 <= 0 || mod1 <= 0 || div2 <= 0) return MI_ERR_INVALID_ARG;
-  if (op < OP_MULT || op > OP_CAT) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  if (!idx || !g_out || !T1 || !T2 || !gT1 || !g2vals || !rows2) return MI_ERR_INVALID_ARG;
-  DualTables t{T1, T2, nullptr, nullptr, nullptr, nullptr, n1, n2, mod1, div2};
-  if (n1 <= 4 && De % 4 == 0 && De <= 256 && ((De / 4) & (De / 4 - 1)) == 0 && aligned16(g_out) && aligned16(T1) && aligned16(T2) &&
-      aligned16(g2vals)) {
+  int rc;
+  DualTables t;
+  if (!dual_entry(rc, t, idx && g_out && gT1 && g2vals && rows2, T1, T2, nullptr, nullptr, nullptr, nullptr, n, F, De, n1, n2, mod1,
+                  div2, op, XF_NONE))
+    return rc;
+  const int form = dual_rows_form(De, n1, g_out, T1, T2, g2vals, workspace);
+  if (form != MI_DUAL_ROWS_FORM_ELEMENT) {
     const int lpr = De / 4;
     int64_t fg = (n * lpr / 2 + kBlock - 1) / kBlock;          // two lookups per thread and trip
     // workgroups: one per CU.  Each adds a partial to the last workgroup's join (profiles/r04_dual_rows_grid_sweep.txt: 512
@@ -812,7 +844,7 @@ int mi_dual_gather_bwd_rows(const int64_t *idx, const float *g_out, const float 
     static const int cap = [] { const char *e = getenv("MI_DUAL_ROWS_GRID"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 512 ? v : 256; }();
     if (fg > cap) fg = cap;
     if (fg < 1) fg = 1;
-    float *ws = (workspace && n1 * De <= kBlock && kBlock % (n1 * De) == 0) ? workspace : nullptr;
+    float *ws = form == MI_DUAL_ROWS_FORM_WORKSPACE ? workspace : nullptr;
 #define CALL(LPR) MI_LAUNCH("dual_gather_bwd_rows", (k_dual_bwd_rows4<LPR>), (int)fg, kBlock, stream, idx, t, g_out, gT1, g2vals, rows2, n, F, op, ws)
     MI_DISPATCH_LPR(lpr, CALL)      // (the guard above leaves lpr in 1, 2, 4 .. 64)
 #undef CALL
@@ -837,13 +869,11 @@ int mi_dual_gather_bwd_fields(const int64_t *idx, const float *g_out, const floa
                               int64_t n2, int64_t mod1, int64_t div2, int32_t op, int32_t xform,
                               const int32_t *small_fields, int32_t n_small, const int64_t *field_row0,
                               const uint8_t *is_small, void *stream) {
-  if (n < 0 || F <= 0 || De <= 0 || n1 <= 0 || n2 <= 0 || mod1 <= 0 || div2 <= 0) return MI_ERR_INVALID_ARG;
-  if (op < OP_MULT || op > OP_CAT || xform < XF_NONE || xform > XF_MASK) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  if (!idx || !g_out || !T1 || !T2 || !gT1 || !gT2) return MI_ERR_INVALID_ARG;
-  if (xform == XF_SOFT && (!S1 || !S2 || !gS1 || !gS2)) return MI_ERR_INVALID_ARG;
-  if (xform == XF_MASK && (!M1 || !M2)) return MI_ERR_INVALID_ARG;
-  DualTables t{T1, T2, S1, S2, M1, M2, n1, n2, mod1, div2};
+  int rc;
+  DualTables t;
+  if (!dual_entry(rc, t, idx && g_out && gT1 && gT2 && (xform != XF_SOFT || (gS1 && gS2)), T1, T2, S1, S2, M1, M2, n, F, De, n1, n2,
+                  mod1, div2, op, xform))
+    return rc;
   DualGrads gr{gT1, gT2, gS1, gS2, nullptr, nullptr};
   // LDS pre-aggregation for small tables; fewer, fatter workgroups then bound the flush traffic
   int lds1 = (n1 * De <= kLdsAccFloats / 2), lds2 = (n2 * De <= kLdsAccFloats / 2);

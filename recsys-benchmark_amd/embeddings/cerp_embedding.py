@@ -227,8 +227,8 @@ class RetrainCerpEmbedding(IEmbedding):
     def get_weight(self):
         """The whole table [N, D]: forward(arange(N)) bit for bit; the dense form goes through mi_dual_table_* (see
         CerpEmbedding.get_weight), the row-gradient form (sparse=True) keeps the lookup."""
-        N, tables = self._num_item, (self.p_weight, self.q_weight)
-        if (not self._sparse and self._mode is None and self.p_mask.shape == self.p_weight.shape
+        N, tables = self._num_item, (self.p_weight, self.q_weight, self.p_mask, self.q_mask)
+        if (not self._sparse and self._mode is None
                 and _kernels.dual_table_supported(N, self._bucket_size, self.q_entity_per_row, *tables)):
             return _kernels.dual_table(self.p_weight, self.q_weight, N, self._bucket_size, self.q_entity_per_row, op="add",
                                        M1=self.p_mask, M2=self.q_mask)

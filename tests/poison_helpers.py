@@ -111,7 +111,7 @@ def reached_sites(record, sites=None):
 # Sites the catalogue cannot reach in one eager process, "file:line:column" -> the reason read from the code (needs a process group,
 # runs only inside a capture, is a CPU-only branch).
 NOT_REACHED = {
-    "_kernels.py:2717:15": "runs only inside a capture: _auc_workspace hands a capture a buffer of the graph's own pool",
+    "_kernels.py:2708:15": "runs only inside a capture: _auc_workspace hands a capture a buffer of the graph's own pool",
     "embeddings/dh_embedding.py:153:19": "is a CPU-only branch: the host-built per-item hash table of an empty id range",
     "embeddings/tensortrain_embeddings.py:141:22": "is a CPU-only branch: a numpy array of the host-side approx-uniform initialiser",
     "embeddings/tensortrain_embeddings.py:141:55": "is a CPU-only branch: a numpy array of the host-side approx-uniform initialiser",
@@ -440,11 +440,14 @@ def _dual_gather_case(op, variant, B=37, D=16, div=2):
 ALIGN_OFFSETS = {}          # case name -> data_ptr() % 16 of the upstream gradient the last run handed to DualGather.backward
 
 
-def _alignment_case(n1, De=16, n=333):
+def _alignment_case(n1, De=16, n=333, aligned=False):
     """dual_gather(sparse2=True) with an upstream gradient that is a contiguous view 12 bytes past a 16-byte boundary: the loss
     runs through cat([pad3, out.reshape(-1)]), whose backward hands `out` a narrow view of one flat gradient.  The float4
-    kernel that OVERWRITES table 1's gradient declines such an operand, and the fallback ADDS into it."""
-    name = f"dual_gather-alignment-n1_{n1}"
+    kernel that OVERWRITES table 1's gradient declines such an operand, and the fallback ADDS into it.
+    aligned: the twin whose loss is taken from `out` directly, so the float4 kernel runs.  n1 = 3 is the shape whose 48
+    sums do not tile a workgroup: the float4 kernel joins them with float atomics and ADDS into table 1's gradient — the
+    third form mi_dual_gather_bwd_rows_form can name (n1 in 1, 2, 4 aligned is the dual_gather-*-sparse2 cases)."""
+    name = f"dual_gather-{'aligned' if aligned else 'alignment'}-n1_{n1}"
     N = 1000
 
     def inputs():
@@ -452,17 +455,18 @@ def _alignment_case(n1, De=16, n=333):
         idx = torch.randint(0, N, (n,), generator=gen)
         T1 = torch.randint(-3, 4, (n1, De), generator=gen).float()
         T2 = torch.randint(-3, 4, ((N + n1 - 1) // n1, De), generator=gen).float()
-        return dict(T1=T1, T2=T2, pad3=torch.zeros(3)), dict(idx=idx)
+        return dict(T1=T1, T2=T2, **({} if aligned else dict(pad3=torch.zeros(3)))), dict(idx=idx)
 
-    def op_fn(T1, T2, pad3, idx):
+    def op_fn(T1, T2, idx, pad3=None):
         from recsys_benchmark_amd import _kernels
 
         out = _kernels.dual_gather(idx, T1, T2, n1, n1, "add", sparse2=True)
         out.register_hook(lambda g: ALIGN_OFFSETS.__setitem__(name, (g.data_ptr() % 16, g.is_contiguous())))
-        return dict(flat=torch.cat([pad3, out.reshape(-1)]))
+        return dict(flat=out if aligned else torch.cat([pad3, out.reshape(-1)]))
 
-    def ref(T1, T2, pad3, idx):
-        return dict(flat=torch.cat([pad3, _qr_ref(idx, T1, T2, n1, "add").reshape(-1)]))
+    def ref(T1, T2, idx, pad3=None):
+        out = _qr_ref(idx, T1, T2, n1, "add")
+        return dict(flat=out if aligned else torch.cat([pad3, out.reshape(-1)]))
 
     return autograd_case(name, inputs, op_fn, ref, exact=True, int_grads=True)
 
@@ -2654,7 +2658,7 @@ def _build():
     for op in ("mult", "add", "cat"):
         cases += [_dual_gather_case(op, v) for v in ("plain", "sparse2", "fields", "offsets", "sparse2+offsets", "sparse2+fields")]
     cases += [_dual_gather_case("add", "sparse2", D=12), _dual_gather_case("add", "sparse2", D=16, div=7)]
-    cases += [_alignment_case(n1) for n1 in (1, 2, 4)]
+    cases += [_alignment_case(n1) for n1 in (1, 2, 3, 4)] + [_alignment_case(3, aligned=True)]
     for N, D, bucket in ((37, 8, 12), (5000, 16, 1700)):
         for kind, op, divider in (("qr", "mult", 2), ("qr", "add", 5), ("qr", "cat", 2), ("soft", "add", None), ("mask", "add", None)):
             cases.append(_dual_table_case(kind, op, divider, N, D, bucket))

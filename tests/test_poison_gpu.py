@@ -41,13 +41,17 @@ def test_poisoned_allocations_change_nothing(case):
 
 def test_the_alignment_cases_hand_the_backward_a_gradient_off_the_16_byte_boundary():
     """What makes the alignment cases a test of the fallback: the upstream gradient DualGather.backward receives is a
-    contiguous view that does not start on a 16-byte boundary."""
+    contiguous view that does not start on a 16-byte boundary — and the aligned twin of n1 = 3 one that does, so that it
+    runs the float4 kernel that adds into table 1's gradient."""
     names = [c for c in ph.CASES if c.name.startswith("dual_gather-alignment")]
-    assert len(names) == 3
+    assert len(names) == 4
     for case in names:
         case.run()
         offset, contiguous = ph.ALIGN_OFFSETS[case.name]
         assert contiguous and offset % 16 != 0, (case.name, offset)
+    twin, = [c for c in ph.CASES if c.name.startswith("dual_gather-aligned")]
+    twin.run()
+    assert ph.ALIGN_OFFSETS[twin.name] == (0, True)
 
 
 def test_catalogue_reaches_the_allocation_sites():

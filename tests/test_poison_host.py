@@ -125,4 +125,5 @@ def test_not_reached_names_real_sites_with_a_reason_and_stays_small():
 def test_catalogue_names_are_unique_and_cover_the_alignment_case():
     names = [c.name for c in ph.CASES]
     assert len(set(names)) == len(names)
-    assert sum(n.startswith("dual_gather-alignment") for n in names) == 3
+    assert sum(n.startswith("dual_gather-alignment") for n in names) == 4
+    assert "dual_gather-aligned-n1_3" in names
