@@ -19,14 +19,14 @@ of the same step give bit-identical results.
 tracks running statistics, widths are multiples of 8, fp32 2-D input); everything else keeps the general path of mlp.py.
 """
 import ctypes
-from typing import List, Optional
+import os
+from collections import namedtuple
+from typing import List, NamedTuple, Optional
 
 import torch
 from torch import nn
 
 from . import _kernels, _lib
-
-import os
 
 SALT = 7919          # per-layer salt of the dropout hash: SALT * (layer index + 1)
 # Round 3 (verdict item: "finalize in the consumer's prologue"): the kernels of csrc/tail.hip can join the BatchNorm
@@ -83,7 +83,19 @@ class _AffineJob(ctypes.Structure):      # mi_tail_affine_job
                 ("rstd", ctypes.c_void_p)]
 
 
-def _bn_fwd_struct(part, L, c, seed_bump, shift=None, nrep=0) -> "_BnFwd":
+def _ref(struct):
+    return ctypes.byref(struct) if struct is not None else None
+
+
+def _load(t, ld, c, p, bits):
+    """An activation as the next kernel's operand load, the seven arguments every such kernel takes: (pointer, leading
+    dimension, mu, sc, be, p, keep bits) — BatchNorm + ReLU + Dropout applied on the way in; c (the layer's constants) None:
+    the tensor as it is; bits None: nothing dropped."""
+    mu, sc, be = (c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr()) if c is not None else (None, None, None)
+    return _lib.ptr(t), ld, mu, sc, be, float(p), _lib.ptr(bits)
+
+
+def _bn_fwd_struct(part, L, c, shift, nrep, seed_bump) -> "_BnFwd":
     bn = L.bn
     return _BnFwd(part.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), _lib.ptr(L.lin.bias), bn.running_mean.data_ptr(),
                   bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr(), seed_bump, c[0].data_ptr(), c[1].data_ptr(),
@@ -210,12 +222,6 @@ def _fixed_constants(plan: List[_Layer], dev, stream, defer: bool = False):
     return out
 
 
-class _State:
-    """What the forward leaves for the backward: tensors (flattened for ctx.save_for_backward) + plain metadata."""
-    __slots__ = ("k", "ps", "has_head_bias", "add_shape", "zeros", "plan", "n_saved", "stat_b", "zsize", "boff", "hoff", "head",
-                 "extra")
-
-
 # The gather + FM forward in front of DeepFM's tail carries the keep bits and the zero fill (mi_gather_fm_fwd_ride): the
 # first layer's statistics can then be shifted sums like the others' and the step has no finalize launch at all
 # (MI_TAIL_LEAD_RIDE=0: the first layer keeps its tile statistics and the finalize launch that carries the masks)
@@ -228,14 +234,114 @@ HEAD_EPILOGUE = os.environ.get("MI_TAIL_HEAD_EPILOGUE", "1") == "1"
 HEAD_LOSS = os.environ.get("MI_TAIL_HEAD_LOSS", "1") == "1"
 
 
-class _Lead:
-    """The kernel in front of the tail that produces its input (DeepFM: gather + FM): `launch(job)` runs it — carrying the
-    mask job (a mi_tail_mask_ride or None) — and returns (x[M, K], last_add or None).  extra_zero: floats the step's
-    zero-filled buffer should hold for the caller besides the tail's own accumulators (state.extra)."""
-    __slots__ = ("M", "dev", "launch", "extra_zero")
+class _Form(NamedTuple):
+    """Which launches a step takes: every decision of the driver, made once by _form() at forward time, together with the
+    replica counts and deterministic mode as they stood then.  The zero buffer is laid out for this record (_zero_layout),
+    the seed rule reads it (_seed_launch), and the backward reads it and no module knob: it runs the form the forward ran."""
+    grad: bool            # a backward may follow
+    det: bool             # deterministic mode: no float atomics, the weight-gradient kernel recomputes its operand
+    merge: bool           # MERGE_JOINS: tile statistics, joined by the consuming kernel's prologue
+    sums: bool            # STAT_SUMS: statistics as sums added with float atomics, derived by the consuming kernel's prologue
+    R: int                # replicas of a hidden layer's sums
+    Rh: int               # replicas of the head's sums
+    lead_ride: bool       # the launch in front of the tail carries the keep bits, the zero fill and the fixed layers' constants
+    stat_f: tuple         # per layer: its product ADDS its statistics (the first layer's only when a launch in front zeroed them)
+    stat_b: bool          # the backward's column sums are added sums too
+    head_loss: bool       # head + criterion + the head's backward sums in one launch (mi_tail_head_bce)
+    ride: bool            # the keep bits and the zero fill ride in the first layer's finalize launch
+    head_epi: bool        # the head in the last product's epilogue (nothing kept, nothing zero-filled but the logits)
+    keep_inputs: bool     # a layer's input activation is stored for the weight gradient
 
-    def __init__(self, M, dev, launch, extra_zero: int = 0):
-        self.M, self.dev, self.launch, self.extra_zero = M, dev, launch, int(extra_zero)
+
+def _form(plan, has_lead: bool, has_labels: bool, grad: bool) -> _Form:
+    """The one place that reads the tail's knobs."""
+    det, merge = bool(_kernels.DETERMINISTIC), MERGE_JOINS
+    sums = STAT_SUMS and not merge and not det
+    lead_ride = has_lead and LEAD_RIDE and sums
+    stat_b = sums and grad
+    last = plan[-1].lin.out_features
+    return _Form(
+        grad=grad, det=det, merge=merge, sums=sums, R=STAT_REPS, Rh=HEAD_REPS, lead_ride=lead_ride,
+        stat_f=tuple(sums and (i >= 1 or lead_ride) and not L.fixed for i, L in enumerate(plan)), stat_b=stat_b,
+        head_loss=has_labels and HEAD_LOSS and stat_b and last <= 512 and last % 4 == 0,
+        # (that launch exists — a training-mode BatchNorm on the first layer — and a LATER kernel can advance the seed)
+        ride=RIDE_MASKS and not merge and len(plan) >= 2 and not plan[0].fixed and not lead_ride,
+        # inference, every layer on fixed statistics (so the layout below is empty): the logits are zero-filled by the lead launch
+        head_epi=(HEAD_EPILOGUE and lead_ride and not grad and not has_labels and all(L.fixed and L.p == 0 for L in plan)
+                  and last % 4 == 0),
+        keep_inputs=grad and not det)
+
+
+# _zero_layout's result, slices of the step's zero-filled buffer (None / empty: the form has no such block) and its size.
+# w / b: per layer, where the weight gradient's split-K slices meet and the (exactly zero) bias gradient under a training-mode
+# BatchNorm; fsum / bsum: {layer: its forward sums, R x 4 N (fp64 pairs) / its backward column sums, R x 2 N}; head: the
+# head's column sums, Rh x N x 2, and right behind them head_w: its dw / db rows, Rh x (N + 4); loss: mi_tail_head_bce's
+# workspace (its first float is the loss); extra: the caller's floats (_Lead.extra_zero)
+_Layout = namedtuple("_Layout", "w b fsum bsum head head_w loss extra total")
+
+
+def _zero_layout(dims, form: _Form, extra_zero: int = 0) -> _Layout:
+    """ONE zero-filled buffer per step for everything that accumulates; dims: (N, K) per layer.  The alignment rule: every
+    block starts on a multiple of 4 floats — the zero fill and the kernels' float4 accesses need 16 bytes, the fp64 forward
+    sums 8 — so the total is one too."""
+    at = 0
+
+    def take(n):
+        nonlocal at
+        cut, at = slice(at, at + n), at + (n + 3) // 4 * 4
+        return cut
+
+    wb = [(take(N * K), take(N)) for N, K in dims] if form.grad else []
+    fsum = {i: take(form.R * 4 * N) for i, (N, _) in enumerate(dims) if form.stat_f[i]}
+    bsum, head, head_w, loss = {}, None, None, None
+    if form.stat_b:
+        bsum = {i: take(form.R * 2 * N) for i, (N, _) in enumerate(dims[:-1])}
+        head, head_w = take(form.Rh * 2 * dims[-1][0]), take(form.Rh * (dims[-1][0] + 4))
+        if form.head_loss:
+            loss = take(int(_lib.load().mi_tail_head_bce_ws_elems(form.Rh)))
+    extra = take(extra_zero) if (extra_zero > 0 and form.grad) else None
+    assert not (form.head_epi and at), "the head-in-epilogue form has no zero buffer: the lead launch zero-fills the logits"
+    return _Layout(tuple(w for w, _ in wb), tuple(b for _, b in wb), fsum, bsum, head, head_w, loss, extra, at)
+
+
+def _seed_launch(plan, form: _Form):
+    """The launch that advances the dropout seed — exactly once per step, after the launch that made the keep bits:
+    ("finalize", i): layer i's finalize launch; ("join", i): the first kernel that joins pending statistics, layer i's product
+    or (i = k) the head; ("head", k): the head alone, with nothing to join.  None: no layer drops."""
+    if not any(L.p > 0 for L in plan):
+        return None
+    k, pending = len(plan), False
+    first = 1 if form.ride else 0          # (a finalize launch that carries the mask job MADE the bits: the next one advances)
+    for i, L in enumerate(plan):
+        if pending:
+            return "join", i
+        pending = not L.fixed and (form.stat_f[i] or form.merge)
+        if not L.fixed and not pending and i == first and not (form.sums and k >= 2):
+            return "finalize", i           # (sums: the first deriving kernel advances the seed instead)
+    return ("join", k) if pending else ("head", k)
+
+
+class _Saved(namedtuple("_Saved", "x w_head Ws Zs consts bits gammas acts")):
+    """The tensors the forward keeps for the backward, by name; the fields from Ws on hold one entry per layer, None where
+    nothing is kept.  flat() is what ctx.save_for_backward takes, of() reads it back (a caller's own tensors may follow)."""
+
+    def flat(self):
+        return [self.x, self.w_head, *(t for per_layer in self[2:] for t in per_layer)]
+
+    @classmethod
+    def of(cls, flat, k):
+        return cls(flat[0], flat[1], *(flat[2 + j * k: 2 + (j + 1) * k] for j in range(len(cls._fields) - 2)))
+
+
+class _State:
+    """What the forward leaves for the backward besides the saved tensors."""
+    __slots__ = ("plan", "form", "lay", "zeros", "head", "extra", "has_head_bias", "add_shape")
+
+
+# The kernel in front of the tail that produces its input (DeepFM: gather + FM): `launch(job)` runs it — carrying the
+# mask job (a mi_tail_mask_ride or None) — and returns (x[M, K], last_add or None).  extra_zero: floats the step's
+# zero-filled buffer should hold for the caller besides the tail's own accumulators (state.extra).
+_Lead = namedtuple("_Lead", "M dev launch extra_zero", defaults=(0,))
 
 
 class _HeadLoss:
@@ -272,64 +378,32 @@ def take_head_loss(logits: torch.Tensor, target: torch.Tensor):
     return None
 
 
-def _tail_forward(plan, seed, x, last_add, Ws, w_head, b_head, lead: Optional[_Lead] = None, labels=None, loss_seed=None):
-    """The forward kernels of the tail; returns (out[M, 1], tensors to save, state).  lead (instead of x / last_add): the
-    launch that produces them, run here once the mask job it carries is known.  labels ([M] fp32, optional): the head
-    launch also evaluates BCE-with-logits against them and the head's backward sums (state.head) for the upstream gradient
-    loss_seed (a device scalar: what the caller will seed the criterion's backward with; None: losses.unit_scalar)."""
+def _tail_forward(plan, seed, x, last_add, params, lead: Optional[_Lead] = None, labels=None, loss_seed=None):
+    """The forward kernels of the tail; returns (out[M, 1], tensors to save, state).  params: (W, b, gamma, beta) per hidden
+    layer, then the head's (w, b).  lead (instead of x / last_add): the launch that produces them, run here once the mask job
+    it carries is known.  labels ([M] fp32, optional): the head launch also evaluates BCE-with-logits against them and the
+    head's backward sums (state.head) for the upstream gradient loss_seed (a device scalar: what the caller will seed the
+    criterion's backward with; None: losses.unit_scalar)."""
     lib = _lib.load()
     dev = lead.dev if lead is not None else _lib.require_gpu(x)
     s = _lib.stream_ptr(dev)
     M = lead.M if lead is not None else x.shape[0]
     k = len(plan)
-    grad = bool(getattr(plan, "grad", True))
-    merge = MERGE_JOINS
-    R, Rh = STAT_REPS, HEAD_REPS
-    sums_ok = STAT_SUMS and not merge and not _kernels.DETERMINISTIC
-    lead_ride = lead is not None and LEAD_RIDE and sums_ok
-    # this product ADDS its statistics (the first layer's only when a launch in front of it has zeroed the sums)
-    stat_f = [sums_ok and (i >= 1 or lead_ride) and not L.fixed for i, L in enumerate(plan)]
-    stat_b = sums_ok and grad
-    head_loss = (labels is not None and HEAD_LOSS and stat_b and plan[-1].lin.out_features <= 512
-                 and plan[-1].lin.out_features % 4 == 0)
-    # ONE zero-filled buffer per step for everything that accumulates: the split-K weight gradients and the (exactly zero)
-    # bias gradients under a training-mode BatchNorm (backward), the forward sums of the layers above the first, the
-    # backward column sums of every layer and of the head
-    zsize = 0
-    if grad:
-        zsize = sum(L.lin.out_features * L.lin.in_features + L.lin.out_features for L in plan)
-        zsize = (zsize + 3) // 4 * 4
-    foff, boff, hoff, loff = {}, {}, None, None
-    for i, L in enumerate(plan):
-        if stat_f[i]:                      # (fp64 sums: 4 R N floats, 8-byte aligned — zsize is a multiple of 4 floats here)
-            foff[i] = zsize
-            zsize += (R * 4 * L.lin.out_features + 3) // 4 * 4
-    if stat_b:
-        for i in range(k - 1):
-            boff[i] = zsize
-            zsize += R * 2 * plan[i].lin.out_features
-        hoff = zsize
-        zsize += Rh * (3 * plan[-1].lin.out_features + 4)
-        zsize = (zsize + 3) // 4 * 4
-        if head_loss:
-            loff = zsize
-            zsize += int(lib.mi_tail_head_bce_ws_elems(Rh))
-    eoff = None
-    if lead is not None and lead.extra_zero > 0 and grad:
-        eoff = zsize
-        zsize += (lead.extra_zero + 3) // 4 * 4
-    zeros = torch.empty((zsize,), dtype=torch.float32, device=dev) if zsize else None
-    # the keep bits and the zero fill ride in the first layer's finalize launch (no launch of their own) when that launch
-    # exists (a training-mode BatchNorm on the first layer) and a LATER kernel can advance the seed
-    ride = RIDE_MASKS and not merge and k >= 2 and not plan[0].fixed and not lead_ride
-    # inference (nothing kept, every layer on fixed statistics): the head runs in the last product's epilogue, its logits are
-    # zero-filled by the lead launch
-    head_epi = (HEAD_EPILOGUE and lead_ride and not grad and zeros is None and labels is None and all(L.fixed for L in plan)
-                and all(L.p == 0 for L in plan) and w_head.numel() % 4 == 0)
-    out_pad = torch.empty(((M + 3) // 4 * 4,), dtype=torch.float32, device=dev) if head_epi else None
-    if lead_ride:
+    Ws = [_kernels._f32c(params[4 * i]) for i in range(k)]
+    w_head, b_head = _kernels._f32c(params[4 * k]).view(-1), params[4 * k + 1]
+    form = _form(plan, lead is not None, labels is not None, bool(getattr(plan, "grad", True)))
+    lay = _zero_layout([(L.lin.out_features, L.lin.in_features) for L in plan], form, lead.extra_zero if lead is not None else 0)
+    seed_at = _seed_launch(plan, form)
+    R, Rh = form.R, form.Rh
+
+    def bump(*launch):
+        return seed.data_ptr() if launch == seed_at else None
+
+    zeros = torch.empty((lay.total,), dtype=torch.float32, device=dev) if lay.total else None
+    out_pad = torch.empty(((M + 3) // 4 * 4,), dtype=torch.float32, device=dev) if form.head_epi else None
+    if form.lead_ride:
         # the launch in front of the tail carries the keep bits, the zero fill AND the constants of the fixed-statistics layers
-        bits, lead_job = _masks(seed, plan, M, dev, out_pad if head_epi else zeros, ride=True)
+        bits, lead_job = _masks(seed, plan, M, dev, out_pad if form.head_epi else zeros, ride=True)
         fixed_c, aff = _fixed_constants(plan, dev, s, defer=True)
         ride_struct = lead_job[0] if lead_job is not None else None
         if aff is not None:
@@ -341,38 +415,22 @@ def _tail_forward(plan, seed, x, last_add, Ws, w_head, b_head, lead: Optional[_L
     else:
         if lead is not None:
             x, last_add = lead.launch(None)
-        bits, job = _masks(seed, plan, M, dev, zeros, ride=True) if ride else (_masks(seed, plan, M, dev, zeros), None)
+        bits, job = _masks(seed, plan, M, dev, zeros, ride=True) if form.ride else (_masks(seed, plan, M, dev, zeros), None)
         fixed_c = _fixed_constants(plan, dev, s)
-    keep_inputs = grad and not _kernels.DETERMINISTIC
     Zs, consts, acts = [], [], []
-    prev, prev_c, prev_p, prev_bits = x, None, 0.0, None
-    any_bits = any(b is not None for b in bits)
-    bump_at = 1 if job is not None else 0
-    pending = None            # (part, layer, constants[, shift]) of the layer whose statistics the next kernel joins
-    bumped = False
-
-    def pending_struct():
-        nonlocal bumped
-        bump = seed.data_ptr() if (any_bits and not bumped) else None
-        bumped = bumped or bump is not None
-        if len(pending) == 4:
-            return _bn_fwd_struct(pending[0], pending[1], pending[2], bump, shift=pending[3], nrep=R)
-        return _bn_fwd_struct(pending[0], pending[1], pending[2], bump)
-
+    prev = (x, plan[0].lin.in_features, None, 0.0, None)      # the next kernel's operand load (_load)
+    pending = None            # (part, layer, constants, shift, replicas) of the layer whose statistics the next kernel joins
     for i, L in enumerate(plan):
         N, K = L.lin.out_features, L.lin.in_features
-        if head_epi and i == k - 1:        # the last hidden layer of an inference forward: product + head, z not stored
+        if form.head_epi and i == k - 1:   # the last hidden layer of an inference forward: product + head, z not stored
             c = fixed_c[i]
             hadd = None if last_add is None else _kernels._f32c(last_add).view(-1)
             epi = _HeadEpi(w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(hadd), c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(),
                            out_pad.data_ptr())
-            _lib.check(lib.mi_tail_fwd_gemm_head(
-                prev.data_ptr(), K, _lib.ptr(prev_c[0]) if prev_c is not None else None,
-                _lib.ptr(prev_c[1]) if prev_c is not None else None, _lib.ptr(prev_c[2]) if prev_c is not None else None,
-                float(prev_p), _lib.ptr(prev_bits), Ws[i].data_ptr(), K, M, N, K, None, ctypes.byref(epi), s),
-                "mi_tail_fwd_gemm_head")
-            acts.append(x.new_empty(0))
-            Zs.append(x.new_empty(0))
+            _lib.check(lib.mi_tail_fwd_gemm_head(*_load(*prev), Ws[i].data_ptr(), K, M, N, K, None, ctypes.byref(epi), s),
+                       "mi_tail_fwd_gemm_head")
+            acts.append(None)
+            Zs.append(None)
             consts.append(c)
             continue
         Z = torch.empty((M, N), dtype=torch.float32, device=dev)
@@ -381,62 +439,50 @@ def _tail_forward(plan, seed, x, last_add, Ws, w_head, b_head, lead: Optional[_L
             c = fixed_c[i]
         else:
             c = torch.empty((4, N), dtype=torch.float32, device=dev)          # mu, sc, be, rstd
-            if stat_f[i]:
-                part = zeros[foff[i]: foff[i] + R * 4 * N]
+            if form.stat_f[i]:
+                part = zeros[lay.fsum[i]]
                 shift = torch.empty((N,), dtype=torch.float32, device=dev)
             else:
                 part = torch.empty(int(lib.mi_tail_part_elems(M, N)), dtype=torch.float32, device=dev)
         # the layer's input activation as its operand load computes it, kept for the weight gradient (not in
         # deterministic mode, whose weight-gradient kernel recomputes it)
-        a_in = torch.empty((M, K), dtype=torch.float32, device=dev) if (keep_inputs and prev_c is not None) else None
-        stats = pending_struct() if pending is not None else None
+        a_in = torch.empty((M, K), dtype=torch.float32, device=dev) if (form.keep_inputs and prev[2] is not None) else None
+        stats = _bn_fwd_struct(*pending, bump("join", i)) if pending is not None else None
         pending = None
         _lib.check(lib.mi_tail_fwd_gemm_s(
-            prev.data_ptr(), K, _lib.ptr(prev_c[0]) if prev_c is not None else None,
-            _lib.ptr(prev_c[1]) if prev_c is not None else None, _lib.ptr(prev_c[2]) if prev_c is not None else None,
-            float(prev_p), _lib.ptr(prev_bits), Ws[i].data_ptr(), K, Z.data_ptr(), N, _lib.ptr(part), _lib.ptr(a_in),
-            M, N, K, ctypes.byref(stats) if stats is not None else None, R if stat_f[i] else 0, _lib.ptr(shift),
-            L.bn.running_mean.data_ptr() if stat_f[i] else None, _lib.ptr(L.lin.bias) if stat_f[i] else None, s),
-            "mi_tail_fwd_gemm_s")
-        acts.append(a_in if a_in is not None else x.new_empty(0))
-        if L.fixed:
-            pass
-        elif stat_f[i]:
-            pending = (part, L, c, shift)
-        elif merge:
-            pending = (part, L, c)
-        else:
+            *_load(*prev), Ws[i].data_ptr(), K, Z.data_ptr(), N, _lib.ptr(part), _lib.ptr(a_in), M, N, K, _ref(stats),
+            R if form.stat_f[i] else 0, _lib.ptr(shift), L.bn.running_mean.data_ptr() if form.stat_f[i] else None,
+            _lib.ptr(L.lin.bias) if form.stat_f[i] else None, s), "mi_tail_fwd_gemm_s")
+        acts.append(a_in)
+        if not L.fixed and (form.stat_f[i] or form.merge):
+            pending = (part, L, c, shift, R if form.stat_f[i] else 0)
+        elif not L.fixed:
             bn = L.bn
-            late_bump = (sums_ok and k >= 2) or i != bump_at       # (sums: the first deriving kernel advances the seed)
             _lib.check(lib.mi_tail_bn_finalize_fwd_r(
                 part.data_ptr(), M, N, bn.weight.data_ptr(), bn.bias.data_ptr(), _lib.ptr(L.lin.bias),
                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.momentum), float(bn.eps),
-                bn.num_batches_tracked.data_ptr(), seed.data_ptr() if (any_bits and not late_bump and not bumped) else None,
-                c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), c[3].data_ptr(),
-                ctypes.byref(job[0]) if (i == 0 and job is not None) else None, s), "mi_tail_bn_finalize_fwd_r")
-            bumped = bumped or (any_bits and not late_bump)
+                bn.num_batches_tracked.data_ptr(), bump("finalize", i), c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(),
+                c[3].data_ptr(), _ref(job[0]) if (i == 0 and job is not None) else None, s), "mi_tail_bn_finalize_fwd_r")
         Zs.append(Z)
         consts.append(c)
-        prev, prev_c, prev_p, prev_bits = Z, c, L.p, bits[i]
-    out = out_pad[:M].view(M, 1) if head_epi else torch.empty((M, 1), dtype=torch.float32, device=dev)
+        prev = (Z, N, c, L.p, bits[i])
+    out = out_pad[:M].view(M, 1) if form.head_epi else torch.empty((M, 1), dtype=torch.float32, device=dev)
     add = None if last_add is None else _kernels._f32c(last_add).view(-1)
     N = plan[-1].lin.out_features
     if pending is not None:
-        stats = pending_struct()
-    elif any_bits and not bumped:      # nothing left to join: the head only advances the seed (part = NULL)
-        stats = _BnFwd(None, None, None, None, None, None, None, seed.data_ptr(), None, None, None, None, 0.0, 0.0, None, 0)
-        bumped = True
-    else:
-        stats = None
+        stats = _bn_fwd_struct(*pending, bump("join", k))
+    else:                              # nothing left to join: the head only advances the seed (part = NULL), if it is the one
+        stats = _BnFwd(seed_bump=seed.data_ptr()) if seed_at == ("head", k) else None
     head = None
-    if head_loss:
+    if form.head_loss:
         y = _kernels._f32c(labels).view(-1)
         if y.numel() != M:
             raise ValueError("labels must hold one value per row of the batch")
         head = _HeadLoss()
         head.out, head.y, head.y_key = out, y, _label_key(labels)
         head.gvec = torch.empty((M,), dtype=torch.float32, device=dev)
-        head.loss = zeros[loff: loff + 1]
+        loss_ws = zeros[lay.loss]
+        head.loss = loss_ws[:1]
         if loss_seed is None:
             from .losses import unit_scalar
 
@@ -447,69 +493,52 @@ def _tail_forward(plan, seed, x, last_add, Ws, w_head, b_head, lead: Optional[_L
             head.seed = loss_seed
         DY = torch.empty((M, N), dtype=torch.float32, device=dev)
         _lib.check(lib.mi_tail_head_bce(
-            prev.data_ptr(), N, prev_c[0].data_ptr(), prev_c[1].data_ptr(), prev_c[2].data_ptr(), float(prev_p), _lib.ptr(prev_bits),
-            w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(add), y.data_ptr(), out.data_ptr(), head.gvec.data_ptr(), DY.data_ptr(),
-            zeros[hoff:].data_ptr(), zeros[hoff + Rh * 2 * N:].data_ptr(), Rh, zeros[loff:].data_ptr(), M, N,
-            ctypes.byref(stats) if stats is not None else None, _lib.ptr(loss_seed), s), "mi_tail_head_bce")
+            *_load(*prev), w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(add), y.data_ptr(), out.data_ptr(), head.gvec.data_ptr(),
+            DY.data_ptr(), zeros[lay.head].data_ptr(), zeros[lay.head_w].data_ptr(), Rh, loss_ws.data_ptr(), M, N, _ref(stats),
+            _lib.ptr(loss_seed), s), "mi_tail_head_bce")
         head.out_version, head.seed_version = out._version, head.seed._version
         _HEAD_LOSS[str(dev)] = head
-    elif head_epi:
-        pass                               # (the logits came out of the last product's epilogue)
-    else:
-        _lib.check(lib.mi_tail_head_fwd_m(prev.data_ptr(), N, prev_c[0].data_ptr(), prev_c[1].data_ptr(), prev_c[2].data_ptr(),
-                                          float(prev_p), _lib.ptr(prev_bits), w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(add),
-                                          out.data_ptr(), M, N, ctypes.byref(stats) if stats is not None else None, s),
-                   "mi_tail_head_fwd_m")
+    elif not form.head_epi:            # (head_epi: the logits came out of the last product's epilogue)
+        _lib.check(lib.mi_tail_head_fwd_m(*_load(*prev), w_head.data_ptr(), _lib.ptr(b_head), _lib.ptr(add), out.data_ptr(), M, N,
+                                          _ref(stats), s), "mi_tail_head_fwd_m")
     st = _State()
-    st.k, st.plan, st.zeros = k, plan, zeros
+    st.plan, st.form, st.lay, st.zeros = plan, form, lay, zeros
     st.head = (head.gvec, DY) if head is not None else None
-    st.extra = zeros[eoff: eoff + lead.extra_zero] if eoff is not None else None
-    st.stat_b, st.zsize, st.boff, st.hoff = stat_b, zsize, boff, hoff
-    st.ps = [L.p for L in plan]
-    st.has_head_bias = b_head is not None
-    st.add_shape = None if last_add is None else tuple(last_add.shape)
-    saved = [x, w_head, *Ws, *Zs, *consts, *[b if b is not None else x.new_empty(0) for b in bits],
-             *[L.bn.weight if L.bn is not None else x.new_empty(0) for L in plan], *acts]
-    st.n_saved = len(saved)
-    return out, saved, st
+    st.extra = zeros[lay.extra] if lay.extra is not None else None
+    st.has_head_bias, st.add_shape = b_head is not None, None if last_add is None else tuple(last_add.shape)
+    saved = _Saved(x, w_head, Ws, Zs, consts, bits, [L.bn.weight if L.bn is not None else None for L in plan], acts)
+    return out, saved.flat(), st
 
 
 def _tail_backward(st, saved, g, need_x: bool, need_params, need_add: bool, fm=None, beside_wgrad=None):
-    """The backward kernels of the tail.  need_params[j]: whether parameter j of (W, b, gamma, beta) x k + (w, b)_head wants
-    a gradient.  fm (DeepFM, the tail's input is the embedding block): (emb_sum[M, D], g1vals[M, F] or None, D) — the first
-    layer's input-gradient product then writes the lookup table's row-form gradient instead of dx (mi_tail_dgrad_gemm_fm)
-    and the returned dx IS that [M, F*D] buffer.  Returns (dx, dadd, grads, db_head)."""
+    """The backward kernels of the tail, in the form the forward ran (st.form) on the buffer it laid out (st.lay).  saved: the
+    forward's tensors as ctx.saved_tensors returns them.  need_params[j]: whether parameter j of (W, b, gamma, beta) x k +
+    (w, b)_head wants a gradient.  fm (DeepFM, the tail's input is the embedding block): (emb_sum[M, D], g1vals[M, F] or None,
+    D) — the first layer's input-gradient product then writes the lookup table's row-form gradient instead of dx
+    (mi_tail_dgrad_gemm_fm) and the returned dx IS that [M, F*D] buffer.  Returns (dx, dadd, grads, db_head)."""
     lib = _lib.load()
-    k, plan = st.k, st.plan
-    x, w_head = saved[0], saved[1]
-    Ws, Zs, consts = saved[2:2 + k], saved[2 + k:2 + 2 * k], saved[2 + 2 * k:2 + 3 * k]
-    bits = [b if b.numel() else None for b in saved[2 + 3 * k:2 + 4 * k]]
-    gammas = [t if t.numel() else None for t in saved[2 + 4 * k:2 + 5 * k]]
-    acts = [a if a.numel() else None for a in saved[2 + 5 * k:2 + 6 * k]]
-    dev = x.device
+    plan, form, lay = st.plan, st.form, st.lay
+    if not form.grad:
+        raise RuntimeError("the fused tail's plan was made with grad mode off: its forward kept nothing for a backward")
+    k = len(plan)
+    x, w_head, Ws, Zs, consts, bits, gammas, acts = _Saved.of(saved, k)
+    dev, M = x.device, x.shape[0]
     s = _lib.stream_ptr(dev)
-    M = x.shape[0]
     gvec = _kernels._f32c(g).view(M)
     later = []           # weight-gradient products for ONE launch at the end
-    sizes = [(Zs[i].shape[1] * Ws[i].shape[1], Zs[i].shape[1]) for i in range(k)]
     zeros = st_zeros = st.zeros            # filled by the forward's mask launch; a second backward needs a fresh one
     st.zeros = None
     if zeros is None:
-        zeros = torch.zeros((max(st.zsize, sum(a + b for a, b in sizes)),), dtype=torch.float32, device=dev)
-    stat, R, Rh = st.stat_b, STAT_REPS, HEAD_REPS
-    zoff = [0]
-    for a, b in sizes:
-        zoff.append(zoff[-1] + a + b)
+        zeros = torch.zeros((lay.total,), dtype=torch.float32, device=dev)
+    stat, R, Rh = form.stat_b, form.R, form.Rh
     grads: List[Optional[torch.Tensor]] = [None] * (4 * k + 2)
 
     # ---- head: dy of the last hidden layer, its column sums, dw / db of the head
     N = Zs[-1].shape[1]
-    c = consts[-1]
     DY = None if st.head is not None else torch.empty((M, N), dtype=torch.float32, device=dev)
     if stat:            # sums added into Rh zeroed rows: joined by the next product's prologue, no finalize launch
         nblk = Rh
-        part = zeros[st.hoff: st.hoff + Rh * 2 * N].view(Rh, N, 2)
-        wpart = zeros[st.hoff + Rh * 2 * N: st.hoff + Rh * (3 * N + 4)].view(Rh, N + 4)
+        part, wpart = zeros[lay.head].view(Rh, N, 2), zeros[lay.head_w].view(Rh, N + 4)
     else:
         nblk = int(lib.mi_tail_head_blocks(M))
         part = torch.empty((nblk, N, 2), dtype=torch.float32, device=dev)
@@ -519,12 +548,12 @@ def _tail_backward(st, saved, g, need_x: bool, need_params, need_add: bool, fm=N
         DY = fused_head[1]        # the forward's head launch wrote DY and the sums for exactly this gradient
     else:
         if fused_head is not None and zeros is st_zeros:
-            zeros[st.hoff: st.hoff + Rh * (3 * N + 4)].zero_()      # ... for an upstream gradient of 1: not this one
+            zeros[lay.head.start: lay.head_w.stop].zero_()          # ... for an upstream gradient of 1: not this one
         if DY is None:
             DY = torch.empty((M, N), dtype=torch.float32, device=dev)
-        _lib.check(lib.mi_tail_head_bwd_s(Zs[-1].data_ptr(), N, c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), float(st.ps[-1]),
-                                          _lib.ptr(bits[-1]), gvec.data_ptr(), w_head.data_ptr(), DY.data_ptr(), part.data_ptr(),
-                                          wpart.data_ptr(), Rh if stat else 0, M, N, s), "mi_tail_head_bwd_s")
+        _lib.check(lib.mi_tail_head_bwd_s(*_load(Zs[-1], N, consts[-1], plan[-1].p, bits[-1]), gvec.data_ptr(), w_head.data_ptr(),
+                                          DY.data_ptr(), part.data_ptr(), wpart.data_ptr(), Rh if stat else 0, M, N, s),
+                   "mi_tail_head_bwd_s")
     dw_head = torch.empty((1, N), dtype=torch.float32, device=dev)
     db_head = torch.empty((1,), dtype=torch.float32, device=dev)
     # DeepFM's scalar bias is added to every logit like the head's bias: same gradient, written to a second word by the
@@ -534,83 +563,70 @@ def _tail_backward(st, saved, g, need_x: bool, need_params, need_add: bool, fm=N
     dx = None
     for i in range(k - 1, -1, -1):
         N, K = Zs[i].shape[1], Ws[i].shape[1]
-        L = plan[i]
-        c = consts[i]
+        L, c = plan[i], consts[i]
         dgb = torch.empty((2, N), dtype=torch.float32, device=dev)
         dzc = torch.empty((3, N), dtype=torch.float32, device=dev)         # al, bz, de
         dbias = torch.empty((N,), dtype=torch.float32, device=dev) if (L.fixed and L.lin.bias is not None) else None
-        below = Zs[i - 1] if i > 0 else x
-        bc = consts[i - 1] if i > 0 else None
-        bp = st.ps[i - 1] if i > 0 else 0.0
-        bb = bits[i - 1] if i > 0 else None
+        # the activation below as an operand load: what this layer's product multiplied
+        below = (Zs[i - 1], K, consts[i - 1], plan[i - 1].p, bits[i - 1]) if i > 0 else (x, K, None, 0.0, None)
         runs_dgrad = i > 0 or need_x
         # the column sums behind dz's constants: joined in the input-gradient product's prologue, or (no such product
         # for this layer, or the joined forms off) by the finalize launch
         sums = None
-        if (MERGE_JOINS or stat) and runs_dgrad and part_rows <= 128:     # (256 partial rows of the head keep their finalize launch)
+        head_dw, head_db, twin = (dw_head.data_ptr(), db_head.data_ptr(), _lib.ptr(db_twin)) if wp is not None else (None, None, None)
+        if (form.merge or stat) and runs_dgrad and part_rows <= 128:      # (256 partial rows of the head keep their finalize launch)
             sums = _BnBwd(part.data_ptr(), _lib.ptr(gammas[i]), c[3].data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(),
-                          dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(), _lib.ptr(wp),
-                          dw_head.data_ptr() if wp is not None else None, db_head.data_ptr() if wp is not None else None,
-                          part_rows, nw, _lib.ptr(dbias), _lib.ptr(db_twin) if wp is not None else None, int(L.fixed))
+                          dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(), _lib.ptr(wp), head_dw, head_db,
+                          part_rows, nw, _lib.ptr(dbias), twin, int(L.fixed))
         else:
             _lib.check(lib.mi_tail_bn_finalize_bwd_b(
                 part.data_ptr(), part_rows, M, N, _lib.ptr(gammas[i]), c[3].data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(),
-                dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(), _lib.ptr(wp), nw, dw_head.data_ptr() if wp is not None else None,
-                db_head.data_ptr() if wp is not None else None, int(L.fixed), _lib.ptr(dbias),
-                _lib.ptr(db_twin) if wp is not None else None, s), "mi_tail_bn_finalize_bwd_b")
+                dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(), _lib.ptr(wp), nw, head_dw, head_db, int(L.fixed),
+                _lib.ptr(dbias), twin, s), "mi_tail_bn_finalize_bwd_b")
         wp = None
         if L.bn is not None:
             grads[4 * i + 2], grads[4 * i + 3] = dgb[0], dgb[1]
         if need_params[4 * i + 1] and L.lin.bias is not None:
             # under a training-mode BatchNorm the batch mean is removed: exactly zero; otherwise al * sum dy
-            grads[4 * i + 1] = dbias if L.fixed else zeros[zoff[i] + N * K: zoff[i + 1]]
+            grads[4 * i + 1] = dbias if L.fixed else zeros[lay.b[i]]
         a_in = x if i == 0 else acts[i]
-        defer = need_params[4 * i] and runs_dgrad and a_in is not None and not _kernels.DETERMINISTIC
+        defer = need_params[4 * i] and runs_dgrad and a_in is not None and not form.det
         dz_keep = torch.empty((M, N), dtype=torch.float32, device=dev) if defer else None
-        layer_DY = DY
+        # (dy, z and the constants that turn them into dz: the first operand of both products of this layer)
+        dz = (DY.data_ptr(), Zs[i].data_ptr(), N, c[0].data_ptr(), dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr())
         if runs_dgrad:
             OUT = torch.empty((M, K), dtype=torch.float32, device=dev)
             if i > 0 and stat:             # the layer below's column sums: added into R zeroed rows (float atomics)
-                npart = zeros[st.boff[i - 1]: st.boff[i - 1] + R * 2 * K]
+                npart = zeros[lay.bsum[i - 1]]
             else:
                 npart = torch.empty(int(lib.mi_tail_part_elems(M, K)), dtype=torch.float32, device=dev) if i > 0 else None
             if i == 0 and fm is not None and len(fm) == 5:      # the sharded step: rows go back into the receive buffer's gradient
                 emb_sum, _, D, slot, gbuf = fm
                 OUT = gbuf
                 _lib.check(lib.mi_tail_dgrad_gemm_fm_slot(
-                    DY.data_ptr(), Zs[i].data_ptr(), N, c[0].data_ptr(), dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(),
-                    Ws[i].data_ptr(), K, gbuf.data_ptr(), _lib.ptr(dz_keep), M, N, K,
-                    ctypes.byref(sums) if sums is not None else None, x.data_ptr(), emb_sum.data_ptr(), gvec.data_ptr(),
-                    slot.data_ptr(), D, s), "mi_tail_dgrad_gemm_fm_slot")
+                    *dz, Ws[i].data_ptr(), K, gbuf.data_ptr(), _lib.ptr(dz_keep), M, N, K, _ref(sums), x.data_ptr(),
+                    emb_sum.data_ptr(), gvec.data_ptr(), slot.data_ptr(), D, s), "mi_tail_dgrad_gemm_fm_slot")
             elif i == 0 and fm is not None:
                 emb_sum, g1vals, D = fm
                 _lib.check(lib.mi_tail_dgrad_gemm_fm(
-                    DY.data_ptr(), Zs[i].data_ptr(), N, c[0].data_ptr(), dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(),
-                    Ws[i].data_ptr(), K, OUT.data_ptr(), _lib.ptr(dz_keep), M, N, K,
-                    ctypes.byref(sums) if sums is not None else None, x.data_ptr(), emb_sum.data_ptr(), gvec.data_ptr(),
-                    _lib.ptr(g1vals), D, s), "mi_tail_dgrad_gemm_fm")
-            else:
+                    *dz, Ws[i].data_ptr(), K, OUT.data_ptr(), _lib.ptr(dz_keep), M, N, K, _ref(sums), x.data_ptr(),
+                    emb_sum.data_ptr(), gvec.data_ptr(), _lib.ptr(g1vals), D, s), "mi_tail_dgrad_gemm_fm")
+            else:                          # (layer 0 has no layer below whose dy the epilogue would make: no load)
                 _lib.check(lib.mi_tail_dgrad_gemm_s(
-                    DY.data_ptr(), Zs[i].data_ptr(), N, c[0].data_ptr(), dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(),
-                    Ws[i].data_ptr(), K, below.data_ptr() if i > 0 else None, K, _lib.ptr(bc[0]) if bc is not None else None,
-                    _lib.ptr(bc[1]) if bc is not None else None, _lib.ptr(bc[2]) if bc is not None else None, float(bp), _lib.ptr(bb),
-                    OUT.data_ptr(), K, _lib.ptr(npart), R if (stat and i > 0) else 0, _lib.ptr(dz_keep), M, N, K,
-                    ctypes.byref(sums) if sums is not None else None, s), "mi_tail_dgrad_gemm_s")
+                    *dz, Ws[i].data_ptr(), K, *(_load(*below) if i > 0 else _load(None, K, None, 0.0, None)), OUT.data_ptr(), K,
+                    _lib.ptr(npart), R if (stat and i > 0) else 0, _lib.ptr(dz_keep), M, N, K, _ref(sums), s),
+                    "mi_tail_dgrad_gemm_s")
         # the weight gradient comes AFTER the input-gradient product: in the joined form that product's workgroup 0 is
         # what writes al / bz / de
         if defer:
-            dW = zeros[zoff[i]: zoff[i] + N * K].view(N, K)               # split-K slices meet in atomics
+            dW = zeros[lay.w[i]].view(N, K)                               # split-K slices meet in atomics
             later.append(dict(A=dz_keep, B=a_in, C=dW, M=N, N=K, K=M, lda=N, ldb=K, ldc=K))   # dW = dz^T a_in
             grads[4 * i] = dW
         elif need_params[4 * i]:
             splits = int(lib.mi_tail_wgrad_splits(M, N, K))
             slab = torch.empty((splits, N, K), dtype=torch.float32, device=dev)
             dW = torch.empty((N, K), dtype=torch.float32, device=dev)
-            _lib.check(lib.mi_tail_wgrad_gemm(
-                layer_DY.data_ptr(), Zs[i].data_ptr(), N, c[0].data_ptr(), dzc[0].data_ptr(), dzc[1].data_ptr(), dzc[2].data_ptr(),
-                below.data_ptr(), K, _lib.ptr(bc[0]) if bc is not None else None, _lib.ptr(bc[1]) if bc is not None else None,
-                _lib.ptr(bc[2]) if bc is not None else None, float(bp), _lib.ptr(bb), slab.data_ptr(), dW.data_ptr(), M, N, K, s),
-                "mi_tail_wgrad_gemm")
+            _lib.check(lib.mi_tail_wgrad_gemm(*dz, *_load(*below), slab.data_ptr(), dW.data_ptr(), M, N, K, s), "mi_tail_wgrad_gemm")
             grads[4 * i] = dW
         if runs_dgrad:
             if i > 0:
@@ -635,12 +651,7 @@ class FusedTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, head, seed, x, last_add, labels, loss_seed, *params):
-        k = len(plan)
-        x = _kernels._f32c(x)
-        Ws = [_kernels._f32c(params[4 * i]) for i in range(k)]
-        w_head = _kernels._f32c(params[4 * k]).view(-1)
-        out, saved, st = _tail_forward(plan, seed, x, last_add, Ws, w_head, params[4 * k + 1], labels=labels, loss_seed=loss_seed)
-        ctx.st = st
+        out, saved, ctx.st = _tail_forward(plan, seed, _kernels._f32c(x), last_add, params, labels=labels, loss_seed=loss_seed)
         ctx.save_for_backward(*saved)
         return out
 
@@ -675,6 +686,26 @@ def _next_batch_prefetch(dev, offsets, Wc, ldw, w1c, ldw1, F, N):
     return job, (nxt, offsets, Wc, w1c)
 
 
+def _fm_lead(dev, ids, offsets, W, ldw, w1, ldw1, bias, rows, D, N, extra_zero=0):
+    """The _Lead of DeepFM's lookup, gather + FM + first-order term (mi_gather_fm_fwd_ride), and the emb_sum[B, D] it leaves
+    for the backward.  Table form: ids[B, F] + offsets[F] address rows of W / w1 (pointers, with their row strides), the
+    global rows are written to `rows`; slot form (offsets and rows None): ids are rows of the receive buffer itself."""
+    lib = _lib.load()
+    B, F = ids.shape
+    emb = torch.empty((B, F * D), dtype=torch.float32, device=dev)
+    yfm = torch.empty((B,), dtype=torch.float32, device=dev)
+    esum = torch.empty((B, D), dtype=torch.float32, device=dev)
+
+    def gather(job):      # (job: the tail's mask work, carried in extra workgroups of this launch)
+        _lib.check(lib.mi_gather_fm_fwd_ride(ids.data_ptr(), _lib.ptr(offsets), W, ldw, w1, ldw1, _lib.ptr(bias), emb.data_ptr(),
+                                             yfm.data_ptr(), _lib.ptr(rows), esum.data_ptr(), B, F, D, N,
+                                             _lib.err_word(dev).data_ptr(), _ref(job), _lib.stream_ptr(dev)),
+                   "mi_gather_fm_fwd_ride")
+        return emb, yfm
+
+    return _Lead(B, dev, gather, extra_zero), esum
+
+
 class DeepFMFusedFn(torch.autograd.Function):
     """DeepFM's whole forward as ONE autograd node (src/models/deepfm.py:79-105): gather + FM + first-order term
     (mi_gather_fm_fwd_sum) feeding the fused tail, so that the backward of the lookup runs in the EPILOGUE of the first
@@ -689,31 +720,14 @@ class DeepFMFusedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, head, seed, idx, offsets, W, w1, bias, sparse_W: bool, sparse_w1: bool, labels, *params):
         dev = _lib.require_gpu(idx, offsets, W, w1, bias)
-        lib = _lib.load()
         Wc, ldw = _kernels._row_strided(W)
         N, D = Wc.shape
         idx, offsets, w1c, ldw1, _ = _kernels._lookup_operands(idx, offsets, w1, N)
         B, F = idx.shape
-        emb = torch.empty((B, F * D), dtype=torch.float32, device=dev)
-        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
         rows = torch.empty((B, F), dtype=torch.int64, device=dev)
-        esum = torch.empty((B, D), dtype=torch.float32, device=dev)
-
-        def gather(job):      # (job: the tail's mask work, carried in extra workgroups of this launch)
-            _lib.check(lib.mi_gather_fm_fwd_ride(idx.data_ptr(), offsets.data_ptr(), Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1,
-                                                 _lib.ptr(bias), emb.data_ptr(), yfm.data_ptr(), rows.data_ptr(), esum.data_ptr(),
-                                                 B, F, D, N, _lib.err_word(dev).data_ptr(),
-                                                 ctypes.byref(job) if job is not None else None, _lib.stream_ptr(dev)),
-                       "mi_gather_fm_fwd_ride")
-            return emb, yfm
-
+        lead, esum = _fm_lead(dev, idx, offsets, Wc.data_ptr(), ldw, w1c.data_ptr(), ldw1, bias, rows, D, N)
         _kernels.note_field_layout(rows, offsets, N)
-        k = len(plan)
-        Ws = [_kernels._f32c(params[4 * i]) for i in range(k)]
-        w_head = _kernels._f32c(params[4 * k]).view(-1)
-        out, saved, st = _tail_forward(plan, seed, None, None, Ws, w_head, params[4 * k + 1], lead=_Lead(B, dev, gather),
-                                       labels=labels)
-        ctx.st = st
+        out, saved, ctx.st = _tail_forward(plan, seed, None, None, params, lead=lead, labels=labels)
         ctx.prefetch = _next_batch_prefetch(dev, offsets, Wc, ldw, w1c, ldw1, F, N)
         ctx.meta = (B, F, D, N, tuple(W.shape), tuple(w1.shape), bool(sparse_W), bool(sparse_w1), bias is not None)
         ctx.save_for_backward(*saved, rows, esum)
@@ -728,8 +742,8 @@ class DeepFMFusedFn(torch.autograd.Function):
         need_W, need_w1, need_b = need[5], need[6], need[7]
         dev = rows.device
         g1vals = torch.empty((B * F,), dtype=torch.float32, device=dev) if need_w1 else None
-        gvals, _, grads, db_head = _tail_backward(ctx.st, saved[:ctx.st.n_saved], g, True, need[11:], False,
-                                                  fm=(esum, g1vals, D), beside_wgrad=ctx.prefetch)
+        gvals, _, grads, db_head = _tail_backward(ctx.st, saved, g, True, need[11:], False, fm=(esum, g1vals, D),
+                                                  beside_wgrad=ctx.prefetch)
         gW, gw1 = _kernels._table_grads(rows, gvals.view(B * F, D), g1vals, N, D, Wshape, w1shape, sparse_W, sparse_w1,
                                         need_W, need_w1, _lib.stream_ptr(dev))
         # the scalar bias is added to every logit, like the head's bias: the same gradient, sum_m g[m]
@@ -747,30 +761,14 @@ class SlotDeepFMFusedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, head, seed, recv, slot, bias, labels, loss_seed, *params):
         dev = _lib.require_gpu(recv, slot)
-        lib = _lib.load()
         if recv.dtype != torch.float32 or not recv.is_contiguous() or recv.dim() != 2:
             raise ValueError("recv must be a contiguous fp32 [rows, D + 4] buffer")
         slot = _kernels._i64c(slot)
         B, F = slot.shape
         rows, D = recv.shape[0], recv.shape[1] - 4
-        emb = torch.empty((B, F * D), dtype=torch.float32, device=dev)
-        yfm = torch.empty((B,), dtype=torch.float32, device=dev)
-        esum = torch.empty((B, D), dtype=torch.float32, device=dev)
-
-        def gather(job):
-            _lib.check(lib.mi_gather_fm_fwd_ride(slot.data_ptr(), None, recv.data_ptr(), D + 4, recv.data_ptr() + 4 * D, D + 4,
-                                                 _lib.ptr(bias), emb.data_ptr(), yfm.data_ptr(), None, esum.data_ptr(),
-                                                 B, F, D, rows, _lib.err_word(dev).data_ptr(),
-                                                 ctypes.byref(job) if job is not None else None, _lib.stream_ptr(dev)),
-                       "mi_gather_fm_fwd_ride")
-            return emb, yfm
-
-        k = len(plan)
-        Ws = [_kernels._f32c(params[4 * i]) for i in range(k)]
-        w_head = _kernels._f32c(params[4 * k]).view(-1)
-        out, saved, st = _tail_forward(plan, seed, None, None, Ws, w_head, params[4 * k + 1],
-                                       lead=_Lead(B, dev, gather, extra_zero=rows * (D + 4)), labels=labels, loss_seed=loss_seed)
-        ctx.st = st
+        lead, esum = _fm_lead(dev, slot, None, recv.data_ptr(), D + 4, recv.data_ptr() + 4 * D, D + 4, bias, None, D, rows,
+                              extra_zero=rows * (D + 4))
+        out, saved, ctx.st = _tail_forward(plan, seed, None, None, params, lead=lead, labels=labels, loss_seed=loss_seed)
         ctx.meta = (B, F, D, rows, bias is not None)
         ctx.save_for_backward(*saved, slot, esum)
         return out
@@ -786,7 +784,7 @@ class SlotDeepFMFusedFn(torch.autograd.Function):
         if gbuf is None:                   # a second backward through the same graph: a fresh zero fill
             gbuf = torch.zeros((rows * (D + 4),), dtype=torch.float32, device=slot.device)
         gbuf = gbuf.view(rows, D + 4)
-        _, _, grads, db_head = _tail_backward(st, saved[:st.n_saved], g, True, need[8:], False, fm=(esum, None, D, slot, gbuf))
+        _, _, grads, db_head = _tail_backward(st, saved, g, True, need[8:], False, fm=(esum, None, D, slot, gbuf))
         gb = db_head if (has_bias and need[5]) else None
         return (None, None, None, gbuf if need[3] else None, None, gb, None, None, *grads)
 
@@ -820,3 +818,5 @@ def run_fused_deepfm(plan: List[_Layer], head: nn.Linear, seed: torch.Tensor, id
 def run_fused_slot_deepfm(plan: List[_Layer], head: nn.Linear, seed: torch.Tensor, recv, slot, bias,
                           labels: Optional[torch.Tensor] = None, loss_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
     return SlotDeepFMFusedFn.apply(plan, head, seed, recv, slot, bias, labels, loss_seed, *_plan_params(plan, head))
+
+

@@ -264,6 +264,40 @@ def test_criterion_in_the_head_launch_on_mixed_plans(name, seed_scale):
     assert err_f <= max(8.0 * err_s, 1e-6), f"loss: fused {err_f:.3e} vs stock {err_s:.3e} from float64"
 
 
+def test_backward_runs_the_form_its_forward_ran(monkeypatch):
+    """The replica counts are lowered between forward and backward (HEAD_REPS 8 -> 2, STAT_REPS 4 -> 1; never raised: every
+    extent stays inside what the forward allocated).  With labels the head launch has already written the head's sums into 8
+    replica rows; a backward that read the knobs again would join 2 of them.  Held like the labels case above: against the
+    same step with the labels withheld and the knobs left alone, at its tolerances."""
+    from recsys_benchmark_amd.losses import BCEWithLogitsLoss, unit_scalar
+
+    seq, x, add, G, seed_value = _inputs("stats_then_fixed")
+    M = x.shape[0]
+    y = (torch.rand(M, generator=torch.Generator().manual_seed(M)) < 0.4).float()
+    dev = torch.device(DEV, 0)
+    res = {}
+    for with_labels in (False, True):
+        monkeypatch.setattr(_tail_mod, "HEAD_REPS", 8)
+        monkeypatch.setattr(_tail_mod, "STAT_REPS", 4)
+        fs = copy.deepcopy(seq).to(DEV)
+        xd, ad, yd = x.to(DEV).requires_grad_(True), add.to(DEV).requires_grad_(True), y.to(DEV)
+        _mlp._seed_word(dev).fill_(seed_value)
+        out = run_tail(fs, xd, last_add=ad, labels=yd if with_labels else None)
+        loss = BCEWithLogitsLoss()(out.squeeze(-1), yd)
+        if with_labels:
+            monkeypatch.setattr(_tail_mod, "HEAD_REPS", 2)
+            monkeypatch.setattr(_tail_mod, "STAT_REPS", 1)
+        loss.backward(unit_scalar(dev))
+        res[with_labels] = (out.detach(), loss.detach(), xd.grad, ad.grad, [q.grad for q in fs.parameters()])
+    a, b = res[True], res[False]
+    assert_close(a[0], b[0], 1e-5, 1e-6, "logits")
+    assert_close(a[1], b[1], 1e-5, 1e-6, "loss")
+    assert_close(a[2], b[2], 2e-4, 1e-7, "dx")
+    assert_close(a[3], b[3], 1e-5, 1e-9, "d last_add")
+    for u, v, (pname, _) in zip(a[4], b[4], seq.named_parameters()):
+        assert_close(u, v, 2e-4, 1e-6 + 2e-8 * M, pname)
+
+
 def test_ill_conditioned_statistics():
     """Pre-activation columns up to ~150 sigma from zero under running means far from the batch means (a checkpoint loaded
     onto new data): the shifted sums (s_c = running_mean - bias, M2 = t2 - t1^2 / M) and the tile merges must hold the same
