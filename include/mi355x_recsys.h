@@ -829,7 +829,10 @@ MI_API int mi_gemm_f32(const float *A, const float *B, float *C, int32_t M, int3
  * general kernel).
  * mi_gemm_f32_multi_plan: the cut that call would make, by host arithmetic only (nothing launched, no GPU needed):
  * *kind = 1 (the LDS-DMA kernel) or 0 (the general one), splitk[j] = K-slices of problem j (n entries; 0 for an empty
- * problem), *workgroups = the launch's size. */
+ * problem), *workgroups = the launch's size.
+ * mi_gemm_f32_multi_slots: likewise host arithmetic only — *slots = the depth of the LDS ring the LDS-DMA kernel would run
+ * that launch with: 3 (loads two slices ahead, three workgroups per CU) when all its workgroups are resident at three per
+ * CU, else 2 (five per CU); MI_GEMM_TN_SLOTS=2|3 in the environment forces one; 0 when the general kernel takes the launch. */
 typedef struct mi_gemm_problem {
   const float *A, *B;
   float *C;
@@ -850,6 +853,7 @@ MI_API int mi_gemm_f32_multi_ride(const mi_gemm_problem *probs, int32_t n, int32
                                   const mi_prefetch_rows_job *ride, void *stream);
 MI_API int mi_gemm_f32_multi_plan(const mi_gemm_problem *probs, int32_t n, int32_t transA, int32_t transB, int32_t *kind,
                                   int64_t *workgroups, int32_t *splitk);
+MI_API int mi_gemm_f32_multi_slots(const mi_gemm_problem *probs, int32_t n, int32_t transA, int32_t transB, int32_t *slots);
 
 /* The same contraction on a second tiling, for the large products of a DCN_MixHead layer (layer_dcn.py:90-115 and their
  * gradients): C[M,N] = epi(A[M,K] . B), A row-major.  A workgroup owns a 64-row panel of A by one of nt equal column ranges

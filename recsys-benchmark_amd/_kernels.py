@@ -2762,3 +2762,13 @@ def ctr_metric_append(logits: torch.Tensor, labels: torch.Tensor, at: int, score
                                                 b, int(at), score_buf.data_ptr(), label_buf.data_ptr(), score_buf.numel(),
                                                 loss_sum.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)),
                "mi_ctr_metric_append")
+
+
+def gemm_multi_slots(problems, transA=False, transB=False):
+    """LDS ring slots the LDS-DMA kernel would run that launch with (mi_gemm_f32_multi_slots: host arithmetic, no GPU
+    work): 3 when all its workgroups are resident at three per CU, else 2; 0 when the general kernel takes the launch."""
+    arr = _multi_problem_array(problems)
+    slots = _ctypes.c_int32()
+    _lib.check(_lib.load().mi_gemm_f32_multi_slots(_ctypes.addressof(arr), len(problems), int(transA), int(transB),
+                                                   _ctypes.addressof(slots)), "mi_gemm_f32_multi_slots")
+    return slots.value

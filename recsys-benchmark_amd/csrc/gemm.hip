@@ -487,36 +487,69 @@ __global__ __launch_bounds__(256) void k_gemm_f32_multi(MultiArgs m) {
 // transposition at all when the LDS tile keeps the memory layout: lane (i, kh) of a 32x32x2 MFMA wants A[k = kh][m = i],
 // which in a [k][64 rows] tile is 32 consecutive floats of one k-row per half-wave — a conflict-free ds_read_b32.  So the
 // tiles go global -> LDS with global_load_lds_dwordx4 (16 B per lane, 1 KiB = four k-rows per wave-instruction, lane-linear
-// on the LDS side, which IS this layout): no VGPR staging, no ds_write, no VALU in the loop except the pointer bumps.
+// on the LDS side, which IS this layout): no VGPR staging, no ds_write, no address arithmetic on the vector ALU in the loop.
 // (k_gemm_f32_multi<1,1> pays 16 scalar transposing ds_write_b32 + their address math per thread and k-tile.)
-// Two slots of (A tile, B tile) = 32 KB per workgroup: five workgroups fit a CU, which matters more than a deeper ring —
-// with 4 slots (two workgroups per CU) the same loop took 78 us instead of 58 for the C2 tail's gradients, with or
-// without the DMA: a lone wave per SIMD cannot keep the MFMA pipe fed.  Every wave issues its quarter of a slice (2 + 2
-// instructions) and counts its own DMA by hand (s_waitcnt vmcnt), one barrier per slice.  Waves whose 32x32 block lies
-// outside the matrix skip the MFMAs (M = 400 is 12.5 blocks: the 64-row tiles' second half is empty there).
-// Knock-outs at the C2 tail's shape (4 slices per tile, 588 workgroups): full 58 us; without the epilogue's atomics 58;
+// Every wave issues its quarter of a slice (2 + 2 instructions) and counts its own DMA by hand (s_waitcnt vmcnt), one
+// barrier per slice.  Waves whose 32x32 block lies outside the matrix skip the MFMAs (M = 400 is 12.5 blocks: the 64-row
+// tiles' second half is empty there).
+// The issue block is scalar code behind the trip's first two MFMAs (profiles/wgrad_ring_isa.txt).  It used to stand between
+// the barrier and the first fragment read — 45 instructions, 16 of them vector (a generic-pointer cast with its null check
+// and readfirstlanes per DMA, 64-bit vector adds for the addresses) — and every wave of the workgroup paid it before its
+// first MFMA of every k-tile: THAT was the wait at the slice boundary, not the DMA's latency.  With LDS positions as
+// scalar byte offsets, sources as SGPR base + constant 32-bit lane offset and the block moved behind the chain's start:
+// 47.5 -> 42.8 us for the C2 tail's gradients alone (47.8 -> 43.2 in the step), 1-8 us at every K-slice count 2 .. 16
+// (profiles/wgrad_ring_sweep.txt).
+// Ring depth S (slots of (A tile, B tile) = 16 KB):
+//   S = 2, 32 KB, five workgroups per CU: slice s + 1 is issued in trip s, vmcnt(0) at the top of every trip.
+//   S = 3, 48 KB, three per CU: slices 0 and 1 in the prologue, slice s + 2 in trip s into the slot of slice s - 1 (every
+//     wave read it before it came to this trip's barrier); the wave waits for its own four DMAs of slice s only —
+//     vmcnt(4) with slice s + 1's four behind them, vmcnt(0) in the last trip.  Still one barrier per slice.
+//   Measured, same build, form forced (MI_GEMM_TN_SLOTS): ALONE the third slot buys nothing — 735 workgroups 42.83 vs
+//   42.82 us, and 0.3-1.3 us slower at 294-588 workgroups: once the issue block is out of the way one compute phase covers
+//   the DMA's round trip.  IN THE STEP three slots are 1.2-1.6 us ahead (0.2139-0.2144 vs 0.2155-0.2156 ms, three
+//   alternations, profiles/wgrad_ring_ab.txt): with three per CU the riders start as the products leave instead of
+//   sharing their CUs (riders' cost 0.39 -> 0.03 us, the gather behind them 5.79 -> 5.55 us) — the rest is not isolated.
+//   So a launch takes three slots when all its product workgroups are resident at three per CU (tn_slots below), else two.
+//   4 slots (64 KB, two workgroups per CU) took 78 us instead of 58 in the first form of this loop, with or without
+//   the DMA: a lone wave per SIMD cannot keep the MFMA pipe fed.
+// Knock-outs at the C2 tail's shape (4 slices per tile, 588 workgroups), on the first form of the loop (that launch takes
+// 51 us today): full 58 us; without the epilogue's atomics 58;
 // LDS reads replaced by registers 58; two accumulators 58; DMA + barriers + atomics without MFMAs 24; the MFMAs alone (no
 // DMA, barriers, LDS) 45 — the product is bound by how evenly the MFMA work lands on the 1024 SIMDs, which is the
 // K-slice count's business (auto_splitk below: 5 slices, 49 us).  A 16-wave workgroup on 128 x 128 tiles with one
 // workgroup per CU was built and measured too: 76-95 us (16-wave barriers and a DMA round trip per k-tile on the critical
 // path of sparse edge tiles); removed.
 // Needs: K % 32 == 0, M % 4 == 0, N % 4 == 0, 16-byte aligned operands (else the general kernel).
-constexpr int TN_S = 2, TN_TILE = BK * 64;
+constexpr int TN_TILE = BK * 64, TN_SLOT = 2 * TN_TILE;      // a slot = (A tile, B tile) = 16 KB
 
-__device__ __forceinline__ void tn_dma(const float *src, float *lds_dst) {
+// A wave's share of one slice: four DMAs — two groups of four k-rows of the A tile, two of the B tile.  ga / gb: the
+// slice's first k-row of the problem's operands (wave-uniform, SGPRs); oa / ob: this lane's byte offsets from there (they
+// never change); lds: the byte address of the wave's first kilobyte in the slot's A tile (wave-uniform).
+__device__ __forceinline__ void tn_issue(const float *ga, const float *gb, uint32_t oa0, uint32_t oa1, uint32_t ob0,
+                                         uint32_t ob1, uint32_t lds) {
   // (inline asm, not __builtin_amdgcn_global_load_lds: after the builtin hipcc treats every later LDS read as possibly
   //  out of order with it and waits lgkmcnt(0) in front of each MFMA.  The asm writes M0, which hipcc does not let an asm
-  //  declare as clobbered ("reserved register"), so the block SAVES and RESTORES it itself: M0 is read when the DMA
-  //  issues, the restore right behind the issue is safe, and code the compiler may one day place around this — LDS-direct
-  //  loads, indexed registers — finds M0 as it left it.  Two scalar moves per DMA; the loop is not SALU-bound.)
-  const uint32_t off = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds_dst);
+  //  declare as clobbered ("reserved register"), so the block SAVES and RESTORES it itself: M0 is read when a DMA
+  //  issues, the restore right behind the last issue is safe, and code the compiler may one day place around this —
+  //  LDS-direct loads, indexed registers — finds M0 as it left it.)
   uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(off) : "memory");
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
+      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
+      "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %10\n\t"
+      "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %10\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(oa0), "v"(oa1), "v"(ob0), "v"(ob1), "s"(lds), "s"(lds + 1024u), "s"(lds + 4u * TN_TILE),
+        "s"(lds + 4u * TN_TILE + 1024u), "s"(ga), "s"(gb)
+      : "memory");
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void k_gemm_tn_multi(MultiArgs m) {
-  __shared__ __attribute__((aligned(16))) float tn_lds[TN_S * 2 * TN_TILE];
+  static_assert(S == 2 || S == 3, "two slots (five workgroups per CU) or three (three per CU, loads two slices ahead)");
+  __shared__ __attribute__((aligned(16))) float tn_lds[S * TN_SLOT];
   const int per_xcd = (m.total + 7) >> 3;
   if ((int)blockIdx.x >= 8 * per_xcd) {      // (riders sit at the END of the grid: the product's workgroups are dispatched first)
     mi::prefetch_rows_blocks(m.pf, (int)blockIdx.x - 8 * per_xcd, m.ride_blocks, nullptr);
@@ -539,53 +572,77 @@ __global__ __launch_bounds__(256) void k_gemm_tn_multi(MultiArgs m) {
   if (nst <= 0) return;
 
   const int m0 = by * 64, n0 = bx * BN;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // (block of wave w rotated by the workgroup's id: the empty blocks of edge tiles do not always idle the same SIMDs)
   const int wb = (w + id) & 3;
   const int wr = wb >> 1, wc = wb & 1, i = lane & 31, kh = lane >> 5;
   const bool active = (m0 + wr * 32 < q.M) && (n0 + wc * 32 < q.N);
 
   // this lane's share of a slice: k-rows 8w + (lane >> 4) and + 4 of both tiles, float4 column lane & 15 (column groups
-  // past the matrix re-read its last group: they only feed outputs that are never stored)
-  const int dr = 8 * w + (lane >> 4), dc = (lane & 15) * 4;
+  // past the matrix re-read its last group: they only feed outputs that are never stored).  The slice's first k-row is a
+  // uniform 64-bit address bumped on the scalar unit; the lane adds a 32-bit byte offset that never changes (plan_multi
+  // admits only pitches that keep it below 2^32): the loop carries no vector address arithmetic.
+  const int dc = (lane & 15) * 4;
   const int ca = min(m0 + dc, q.M - 4), cb = min(n0 + dc, q.N - 4);
-  const float *pa = q.A + z * q.sA + (long long)(first * BK + dr) * q.lda + ca;
-  const float *pb = q.B + z * q.sB + (long long)(first * BK + dr) * q.ldb + cb;
-  const long long a4 = 4ll * q.lda, b4 = 4ll * q.ldb, astep = (long long)BK * q.lda, bstep = (long long)BK * q.ldb;
-  auto issue = [&](int s) {
-    float *sa = tn_lds + (s % TN_S) * (2 * TN_TILE) + w * 512;
-    tn_dma(pa, sa);
-    tn_dma(pa + a4, sa + 256);
-    tn_dma(pb, sa + TN_TILE);
-    tn_dma(pb + b4, sa + TN_TILE + 256);
-    pa += astep;
-    pb += bstep;
+  const uint32_t dr = 8 * w + (lane >> 4);
+  const uint32_t oa0 = (dr * (uint32_t)q.lda + ca) * 4u, oa1 = oa0 + 16u * q.lda;
+  const uint32_t ob0 = (dr * (uint32_t)q.ldb + cb) * 4u, ob1 = ob0 + 16u * q.ldb;
+  const float *ga = q.A + z * q.sA + (long long)first * BK * q.lda;
+  const float *gb = q.B + z * q.sB + (long long)first * BK * q.ldb;
+  const long long astep = (long long)BK * q.lda, bstep = (long long)BK * q.ldb;
+  // LDS positions as byte offsets (the array's base once; slot and wave offsets are scalar arithmetic)
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)tn_lds + w * 2048u;
+  uint32_t fill = 0;      // byte offset of the slot the next issue fills
+  auto issue = [&]() {
+    tn_issue(ga, gb, oa0, oa1, ob0, ob1, lds0 + fill);
+    ga += astep;
+    gb += bstep;
+    fill = fill + 4u * TN_SLOT == 4u * S * TN_SLOT ? 0u : fill + 4u * TN_SLOT;
   };
 
   floatx16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  issue(0);
+  issue();
+  if (S == 3 && nst > 1) issue();
   const int fa = kh * 64 + wr * 32 + i, fb = TN_TILE + kh * 64 + wc * 32 + i;
+  int rd = 0;             // first float of the slot slice s is read from
   for (int s = 0; s < nst; ++s) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of slice s has landed
-    __builtin_amdgcn_s_barrier();                          // everybody's has; everybody is done with the other slot
-    if (s + 1 < nst) issue(s + 1);
+    // This wave's share of slice s has landed: its DMAs retire in order, so with the four of slice s + 1 behind them
+    // (three slots, not the last slice) the count to wait for is 4.
+    if (S == 3 && s + 1 < nst) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // everybody's share has; everybody has finished reading the slot of slice s - 1, which is the one the issue below
+    // fills (two slots: slice s + 1; three slots: slice s + 2)
+    __builtin_amdgcn_s_barrier();
+    const bool more = s + S - 1 < nst;
     if (active) {
-      const float *t = tn_lds + (s % TN_S) * (2 * TN_TILE);
+      const float *t = tn_lds + rd;
+      // The issue goes BEHIND the first MFMAs: the fragments of two MFMA pairs are read, the first pair starts the
+      // chain, and the scalar block with the four DMAs runs in its shadow instead of in front of the first MFMA.
+      float a[4], b[4];
 #pragma unroll
-      for (int c = 0; c < BK / 2; ++c)
+      for (int c = 0; c < 4; ++c) a[c] = t[fa + c * 128], b[c] = t[fb + c * 128];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], b[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], b[1], acc, 0, 0, 0);
+      if (more) issue();
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b[2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], b[3], acc, 0, 0, 0);
+#pragma unroll
+      for (int c = 4; c < BK / 2; ++c)
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t[fa + c * 128], t[fb + c * 128], acc, 0, 0, 0);
       // order: the fragment reads of MFMA pair p + 1 go out before the MFMAs of pair p (the scheduler's own order is
       // read, wait, MFMA, MFMA on one register set)
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
       for (int p = 0; p < BK / 4 - 2; ++p) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    } else if (more) {
+      issue();
     }
+    rd = rd + TN_SLOT == S * TN_SLOT ? 0 : rd + TN_SLOT;
   }
   if (!active) return;
 
@@ -734,6 +791,19 @@ static bool tn_enabled() {      // MI_GEMM_TN_DMA=0: the reduction-major form st
   return v;
 }
 
+// Ring depth of the LDS-DMA kernel for a launch of `total` product workgroups.  Three slots (48 KB: three workgroups per
+// CU) when the whole launch is resident at that rate — then nothing is won by room for a fourth and fifth workgroup, and
+// the loads run two slices ahead; two slots (32 KB: five per CU) for a launch that runs in rounds.  Riders do not count:
+// they take the slots the products leave.  MI_GEMM_TN_SLOTS=2|3 forces a form (A/B on one build).
+static int tn_slots(long long total) {
+  static const int forced = []() {
+    const char *e = getenv("MI_GEMM_TN_SLOTS");
+    return e && (e[0] == '2' || e[0] == '3') && !e[1] ? e[0] - '0' : 0;
+  }();
+  if (forced) return forced;
+  return total <= 3ll * cu_count() ? 3 : 2;
+}
+
 // Validates and cuts a launch: fills m (splitk chosen where a problem leaves it 0) and says whether the LDS-DMA kernel takes it.
 static int plan_multi(const mi_gemm_problem *probs, int n, int transA, int transB, MultiArgs &m, bool *tn) {
   m.n = 0;
@@ -769,6 +839,8 @@ static int plan_multi(const mi_gemm_problem *probs, int n, int transA, int trans
     a.gy = (q.M + 63) / 64;
     a.pad_ = 0;
     fits = fits && a.alignedA && a.alignedB && a.K >= BK && a.K % BK == 0 && a.M >= 4 && a.M % 4 == 0 && a.N >= 4 && a.N % 4 == 0;
+    // (a lane's byte offset inside a slice — up to BK + 4 k-rows and a row's width — is a 32-bit number there)
+    fits = fits && q.lda >= 0 && q.ldb >= 0 && 4ll * ((BK + 4ll) * q.lda + q.M) < (1ll << 32) && 4ll * ((BK + 4ll) * q.ldb + q.N) < (1ll << 32);
     wgs += (long long)a.gx * a.gy * q.batch * a.splitk;
     if (wgs > 0x7fffffffLL) return MI_ERR_UNSUPPORTED;
     a.end = (int)wgs;
@@ -796,6 +868,18 @@ int mi_gemm_f32_multi_plan(const mi_gemm_problem *probs, int32_t n, int32_t tran
     const bool empty = probs[j].M == 0 || probs[j].N == 0 || probs[j].batch == 0;
     splitk[j] = empty ? 0 : m.p[k++].splitk;
   }
+  return MI_OK;
+}
+
+// LDS ring slots of the LDS-DMA kernel that launch would run with (host arithmetic only): 2 or 3, 0 when the general kernel
+// takes it or nothing is launched.
+int mi_gemm_f32_multi_slots(const mi_gemm_problem *probs, int32_t n, int32_t transA, int32_t transB, int32_t *slots) {
+  if (!slots) return MI_ERR_INVALID_ARG;
+  MultiArgs m;
+  bool tn;
+  const int rc = plan_multi(probs, n, transA, transB, m, &tn);
+  if (rc != MI_OK) return rc;
+  *slots = tn && m.n > 0 ? tn_slots(m.total) : 0;
   return MI_OK;
 }
 
@@ -832,8 +916,13 @@ int mi_gemm_f32_multi_ride(const mi_gemm_problem *probs, int32_t n, int32_t tran
   const dim3 grid((unsigned)((m.total + 7) / 8 * 8 + m.ride_blocks));
   if (tn) {      // A^T B, both operands reduction-major, every problem of the launch fits: the LDS-DMA kernel
     const bool prof = mi::prof_acquire("gemm_tn_multi", &ea, &eb);
-    if (prof) hipExtLaunchKernelGGL(k_gemm_tn_multi, grid, dim3(256), 0, (hipStream_t)stream, ea, eb, 0, m);
-    else hipLaunchKernelGGL(k_gemm_tn_multi, grid, dim3(256), 0, (hipStream_t)stream, m);
+    if (tn_slots(m.total) == 3) {
+      if (prof) hipExtLaunchKernelGGL(k_gemm_tn_multi<3>, grid, dim3(256), 0, (hipStream_t)stream, ea, eb, 0, m);
+      else hipLaunchKernelGGL(k_gemm_tn_multi<3>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    } else {
+      if (prof) hipExtLaunchKernelGGL(k_gemm_tn_multi<2>, grid, dim3(256), 0, (hipStream_t)stream, ea, eb, 0, m);
+      else hipLaunchKernelGGL(k_gemm_tn_multi<2>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    }
     return launch_status();
   }
   const bool prof = mi::prof_acquire("gemm_f32_multi", &ea, &eb);
