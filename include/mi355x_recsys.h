@@ -1620,6 +1620,45 @@ MI_API int mi_ctr_metric_append(const float *logits, const void *labels, int32_t
                                 float *score_buf, uint8_t *label_buf, int64_t cap, double *loss_sum, void *workspace,
                                 void *stream);
 
+/* ---- device-resident CTR data (src/dataset/criteo/criteo_torchfm.py: `__get_feat_mapper`, `__yield_buffer`,
+ * `__getitems__` and the DataLoader's collate) --------------------------------------------------------------------------
+ * mi_ctr_vocab_field: the vocabulary rule over ONE column whose keys the caller has sorted.
+ *   sorted_keys int64[n] ascending, perm int64[n]: sorted_keys[i] is the key of row perm[i] (a stable sort's output).
+ *   A key seen at least `threshold` (>= 1) times is kept; kept keys get the ids 0 .. kept-1 in ASCENDING KEY ORDER, every
+ *   other key gets the id `kept`:  out[perm[i] * stride] = id of sorted_keys[i]  (out uint32, `stride` in elements: a
+ *   column of the [n, 1 + F] record array has stride 1 + F),  *num_kept = kept  (a device int64; the field's dimension is
+ *   kept + 1).  The reference numbers the kept features in set-iteration order; this rule agrees with it up to a renaming
+ *   of the kept ids per field, and exactly on the field's dimension and on which positions are out-of-vocabulary.
+ *   Three launches on `stream` (mark run heads and kept runs; scan the tiles' counts; scatter), integer adds only, plain
+ *   stores: reruns give the same bits.  Nothing is read back.  A perm entry outside [0, n) writes nothing and ORs
+ *   MI_IDX_OUT_OF_RANGE into *err.
+ *   workspace: mi_ctr_vocab_workspace_bytes(n) bytes (about n + n / 64), 16-byte aligned, no state between calls, nothing
+ *   in it needs zeroing.  n == 0: *num_kept = 0.  n > 2^31 - 1 or stride > 2^31 - 1: MI_ERR_UNSUPPORTED.
+ * mi_ctr_batch: samples [first, first + count) of epoch `epoch` in ONE launch, one lane per output element.
+ *   records uint32[n_records, 1 + F]: column 0 the label, column 1 + f field f's id.  index int64[n] (NULL: n must equal
+ *   n_records): the record rows the epoch runs over.  The sample at epoch position j is record row index[p(j)] (p(j)
+ *   without an index);  x[s, f] = (int64) records[row, 1 + f],  y[s] = (float) records[row, 0]  for s = j - first;
+ *   x int64[count, F], y float[count].  p is the identity when shuffle == 0, else this bijection of [0, n) (all
+ *   arithmetic modulo 2^64; mix64 as under mi_cf_sample_triples):
+ *     mix64      = the splitmix64 finaliser of cf_data.hip; kGold = 0x9E3779B97F4A7C15, kSalt = 0xD1B54A32D192ED03
+ *     bits       = max(2, bit_length(n - 1));  k = (bits + 1) / 2;  mask = (1 << k) - 1
+ *     base       = mix64(seed + kGold * (epoch + 1))                       (mod 2^64 throughout)
+ *     K[r]       = mix64(base + kSalt * (r + 1)),  r = 0..5
+ *     step(x):   L = x >> k; R = x & mask; six times: (L, R) = (R, L ^ (mix64(K[r] + R) & mask)); return (L << k) | R
+ *     p(j):      x = j; do x = step(x) while x >= n
+ *   step is a Feistel network, hence a bijection of [0, 2^(2k)), and 2^(2k) < 4 n for n >= 2; walking until the value is
+ *   below n restricts it to a bijection of [0, n) (the cycle through j returns to j at the latest, so the walk ends).
+ *   Stateless: a sub-range of an epoch holds the bits the whole epoch holds there, for any grid.  A cheap keyed shuffle
+ *   for SGD; no cryptographic claim.
+ *   A row outside [0, n_records) writes -1 to its x and NaN to its y and ORs MI_IDX_OUT_OF_RANGE into *err.
+ *   first + count > n (or a negative size, or F < 1): MI_ERR_INVALID_ARG.  count == 0: MI_OK, no launch.                */
+MI_API int64_t mi_ctr_vocab_workspace_bytes(int64_t n);
+MI_API int mi_ctr_vocab_field(const int64_t *sorted_keys, const int64_t *perm, int64_t n, int64_t threshold, uint32_t *out,
+                              int64_t stride, int64_t *num_kept, void *workspace, int *err, void *stream);
+MI_API int mi_ctr_batch(const uint32_t *records, int64_t n_records, int32_t F, const int64_t *index, int64_t n,
+                        int32_t shuffle, int64_t seed, int64_t epoch, int64_t first, int64_t count, int64_t *x, float *y,
+                        int *err, void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.
