@@ -1659,6 +1659,52 @@ MI_API int mi_ctr_batch(const uint32_t *records, int64_t n_records, int32_t F, c
                         int32_t shuffle, int64_t seed, int64_t epoch, int64_t first, int64_t count, int64_t *x, float *y,
                         int *err, void *stream);
 
+/* ---- the Criteo text format on the device (src/dataset/criteo/criteo_torchfm.py: `__yield_buffer`,
+ * `convert_numeric_feature`; the host reader is `read_criteo_text` of ctr_data.py) ---------------------------------------
+ * A chunk of the file's bytes in; keys int64[n, F], labels uint8[n] and 0-based line numbers int64[n] of the n kept lines
+ * out, F = n_int + n_cat, equal element for element to the host reader's on every file both accept.  The grammar, which
+ * the device enforces strictly:
+ *   lines     a line is a run of bytes ended by '\n'; a non-empty run after the file's last '\n' is a line too.  Lines are
+ *             numbered from 0 over the whole file, skipped ones included.  A line whose number of '\t' bytes is not F is
+ *             skipped and its content ignored.  A '\r' byte anywhere is refused.
+ *   label     column 0: exactly the byte '0' or '1'.
+ *   integer   columns 1 .. n_int: empty gives the key -2^63; otherwise an optional '-' and 1 to 18 decimal digits (leading
+ *             zeros and "-0" included) giving v; the key is v - 2 for v <= 2, else the number of entries <= v of
+ *             `thresholds`, int64[n_thresholds] ascending.  With thresholds[k - 1] = the smallest v whose
+ *             int(math.log(v) ** 2) is at least k (ctr_data.numeric_thresholds builds it from the host reader's own
+ *             function) that number IS int(math.log(v) ** 2): no logarithm is evaluated on the device.
+ *   category  columns n_int + 1 .. F: empty gives the key -1; otherwise 1 to 15 hexadecimal digits of either case.
+ *   refused   anything else in a kept line ("+5", a space, "1_0", "0x1f", 19 digits, 16 hex digits, a label "2", an
+ *             empty label ...).  A refusal lowers *err_record (a device uint64, all ones when there is none) to
+ *             (line number << 16) | column by a 64-bit atomic minimum: the LOWEST offending (line, column) stays, whatever
+ *             the order of arrival.  Outputs of a refused field are zero; the caller discards the chunk.
+ * mi_ctr_text_index: six launches on `stream` (count separators per 4096-byte tile; scan; scatter their positions in order;
+ *   count the lines with exactly F tabs per 256-line tile; scan; number the kept lines).
+ *   text uint8[nbytes], any alignment, nbytes <= 2^31 - 1 (else MI_ERR_UNSUPPORTED).  is_final != 0: the chunk ends the
+ *   file, and a last line without '\n' counts; is_final == 0: the bytes after the chunk's last '\n' belong to the next
+ *   chunk and are ignored (a '\r' among them too).  first_line_no: the file's line number of the chunk's first line.
+ *   record int64[3] (device) = {lines in the chunk, kept lines, bytes consumed (the offset after the last line)}.
+ *   A '\r' in any line of the chunk, kept or not, lowers *err_record to (its line << 16) | min(its column, 65535).
+ *   workspace: mi_ctr_text_workspace_bytes(nbytes, n_int, n_cat) bytes (about 8 nbytes), 16-byte aligned, nothing in it
+ *   needs zeroing; mi_ctr_text_parse reads what this call left in it.
+ * mi_ctr_text_parse: ONE launch, one lane per (kept line, column), each converting its own field (at most 19 bytes) from
+ *   the two separator positions around it; the same text, nbytes, n_int, n_cat, first_line_no and workspace as the
+ *   mi_ctr_text_index call before it, n_kept = record[1].  Every element of keys_out[n_kept, F], labels_out[n_kept] and
+ *   line_no_out[n_kept] is written, nothing beyond.  n_kept == 0: MI_OK, no launch.
+ * Integer arithmetic and plain stores; no arrival order enters any value.  The only atomics are on the error path:
+ * *err_record, the workspace's own minimum over the '\r' bytes, and MI_IDX_OUT_OF_RANGE ORed into *err (NULL is fine) by
+ * a workspace subscript that fails its check, which a workspace left by mi_ctr_text_index never does.  Every byte
+ * subscript is checked against nbytes before it is used.  n_int + n_cat > 65534 or first_line_no > 2^46:
+ * MI_ERR_UNSUPPORTED.                                                                                                       */
+MI_API int64_t mi_ctr_text_workspace_bytes(int64_t nbytes, int32_t n_int, int32_t n_cat);
+MI_API int mi_ctr_text_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int32_t n_int, int32_t n_cat,
+                             int64_t first_line_no, void *workspace, int64_t *record, uint64_t *err_record, int *err,
+                             void *stream);
+MI_API int mi_ctr_text_parse(const uint8_t *text, int64_t nbytes, int32_t n_int, int32_t n_cat, const void *workspace,
+                             int64_t n_kept, int64_t first_line_no, const int64_t *thresholds, int32_t n_thresholds,
+                             int64_t *keys_out, uint8_t *labels_out, int64_t *line_no_out, uint64_t *err_record, int *err,
+                             void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.

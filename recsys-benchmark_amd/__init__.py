@@ -6,7 +6,8 @@ C-ABI HIP library libmi355x_recsys.so (include/mi355x_recsys.h).  See DESIGN.md.
 from . import _lib
 from ._lib import MI355XLibraryError, check_index_errors
 from .cf_data import (DeviceCFGraphDataset, DeviceCFLoader, DeviceCFTestDataset, DeviceCFTestLoader, DeviceTruth)
-from .ctr_data import DeviceCTRDataset, DeviceCTRLoader, encode_ctr_columns, read_criteo_text
+from .ctr_data import (DeviceCTRDataset, DeviceCTRLoader, encode_ctr_columns, numeric_thresholds, parse_criteo_text,
+                       read_criteo_text)
 from .ctr_metric import CTRMetric
 from .deepfm import DeepFM
 from .embeddings import IEmbedding, NAME_TO_CLS, VanillaEmbedding, get_embedding
@@ -57,5 +58,5 @@ __all__ = [
     "DeepFMRetrainOptEmbed", "build_retrain_deepfm", "evol_search_deepfm", "CTRMetric",
     "DeviceCFGraphDataset", "DeviceCFLoader", "DeviceCFTestDataset", "DeviceCFTestLoader", "DeviceTruth",
     "pruned_ctr_checkpoint", "load_pruned_ctr_model",
-    "DeviceCTRDataset", "DeviceCTRLoader", "encode_ctr_columns", "read_criteo_text",
+    "DeviceCTRDataset", "DeviceCTRLoader", "encode_ctr_columns", "read_criteo_text", "parse_criteo_text", "numeric_thresholds",
 ]

@@ -16,6 +16,8 @@ kept ids per field), and the shuffle is the keyed bijection of include/mi355x_re
 """
 import logging
 import math
+import os
+import stat
 from typing import Iterator, Optional, Tuple, Union
 
 import numpy as np
@@ -68,6 +70,231 @@ def read_criteo_text(path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
 def _s64(v: int) -> int:
     """An integer as a two's-complement 64-bit word."""
     return ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+
+
+# ---- the device text reader (csrc/ctr_text.hip; include/mi355x_recsys.h spells the grammar out) ---------------------------
+_thresholds: Optional[np.ndarray] = None
+_text_state = {}               # device index -> the threshold table on that device
+
+
+def numeric_thresholds() -> np.ndarray:
+    """int64 [1906], strictly increasing: entry k - 1 is the smallest v in [3, 2^63) with `_numeric_key(v) >= k`, found by
+    bisection over `_numeric_key` itself (which is non-decreasing in v) and cached.  The number of entries <= v is then
+    `_numeric_key(v)` for every v > 2: what the device evaluates instead of the logarithm."""
+    global _thresholds
+    if _thresholds is None:
+        top = (1 << 63) - 1
+        table, lo = [], 3
+        for k in range(1, _numeric_key(top) + 1):
+            hi = top
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if _numeric_key(mid) >= k:
+                    hi = mid
+                else:
+                    lo = mid + 1
+            table.append(lo)
+        table = np.array(table, dtype=np.int64)
+        table.setflags(write=False)
+        _thresholds = table
+    return _thresholds
+
+
+def _cut_chunks(readinto, chunk_bytes: int, total: Optional[int] = None) -> Iterator[Tuple[memoryview, bool]]:
+    """(chunk, final) pairs of the byte stream behind `readinto(buffer) -> count` (0 at the end; `total`: its length where
+    known): every chunk is at most `chunk_bytes` long and is cut after its last newline, the tail is carried into the
+    next one; a last line without a newline comes alone with final = True.  A line that does not fit a chunk is a
+    ValueError.  The chunks are views of ONE buffer, each valid until the next is asked for: host memory is that buffer."""
+    if chunk_bytes < 1:
+        raise ValueError("chunk_bytes must be at least 1")
+    if total == 0:
+        return
+    buf = bytearray(chunk_bytes if total is None else min(chunk_bytes, total))
+    view, held = memoryview(buf), 0                         # `held` bytes of an unfinished line lie at the front
+    while True:
+        got = readinto(view[held:])
+        if not got:
+            if held:
+                yield view[:held], True
+            return
+        filled = held + got
+        cut = buf.rfind(b"\n", 0, filled) + 1
+        if cut:
+            yield view[:cut], False
+            held = filled - cut
+            buf[:held] = buf[cut:filled]
+        elif filled < len(buf):
+            held = filled
+        elif len(buf) == chunk_bytes and readinto(bytearray(1)):
+            raise ValueError(f"a line is longer than chunk_bytes = {chunk_bytes}")
+        else:                                               # the stream ends with this line
+            yield view[:filled], True
+            return
+
+
+def _thresholds_on(device: torch.device) -> torch.Tensor:
+    """The threshold table resident on `device` (read-only, shared by every call)."""
+    i = device.index if device.index is not None else torch.cuda.current_device()
+    table = _text_state.get(i)
+    if table is None:
+        table = _text_state[i] = torch.from_numpy(numeric_thresholds().copy()).to(torch.device("cuda", i))
+    return table
+
+
+def _new_record(device: torch.device) -> torch.Tensor:
+    """int64 [4] = {lines, kept, consumed, lowest refusal (all ones: none)}; one per call, so calls share no state."""
+    return torch.tensor([0, 0, 0, -1], dtype=torch.int64, device=device)
+
+
+def _raise_refusal(record: torch.Tensor) -> None:
+    """One read-back of the record's refusal word; ValueError if a launch so far lowered it (the word is then cleared)."""
+    word = int(record[3].item())
+    if word != -1:
+        record[3] = -1
+        raise ValueError(f"line {word >> 16} (0-based), column {word & 0xFFFF}: not in the strict Criteo text grammar of "
+                         "the device reader (a label other than 0 or 1, a malformed or over-long number, or a carriage "
+                         "return); read_criteo_text is the lenient reader")
+
+
+def ctr_text_chunk(text: torch.Tensor, final: bool, first_line_no: int = 0, n_int: int = NUM_INT_FEATS,
+                   n_cat: int = NUM_FEATS - NUM_INT_FEATS, out=None, workspace: Optional[torch.Tensor] = None,
+                   record: Optional[torch.Tensor] = None):
+    """One chunk of Criteo text (uint8 [nbytes], contiguous, on the device) through mi_ctr_text_index and
+    mi_ctr_text_parse: (keys int64 [kept, F], labels uint8 [kept], line_no int64 [kept], lines, consumed).  `lines` is
+    the chunk's number of lines and `consumed` the offset after the last of them (without `final` the bytes after the last
+    newline are left to the next chunk).  out=(keys, labels, line_no): contiguous buffers of at least `kept` rows, whose
+    first `kept` rows are written.
+
+    The parse is launched BEFORE any refusal is looked at, so the index's carriage returns and the parse's offences meet in
+    one minimum and the lowest (line, column) of the chunk is the one named.  record=None: the call has a record of its
+    own and raises after the parse (a second read-back of one word).  record=a `_new_record`: the caller chains chunks
+    in file order; the one read-back is the record after the index, which shows the refusals of the chunks before and
+    this chunk's carriage returns (then the parse still runs and the merged word is raised), while a refusal of this
+    chunk's parse alone stays in the record for the next chunk's read-back or the caller's last `_raise_refusal`."""
+    dev = _lib.require_gpu(text)
+    if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+        raise TypeError("text must be a contiguous uint8 vector")
+    F, nbytes = n_int + n_cat, text.numel()
+    lib = _lib.load()
+    thresholds = _thresholds_on(dev)
+    own = record is None
+    if own:
+        record = _new_record(dev)
+    need = int(lib.mi_ctr_text_workspace_bytes(nbytes, n_int, n_cat))
+    if need == 0:
+        raise ValueError(f"a chunk of {nbytes} bytes with {n_int} + {n_cat} columns is outside what the reader supports")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
+    err, stream = _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)
+    _lib.check(lib.mi_ctr_text_index(text.data_ptr(), nbytes, int(bool(final)), n_int, n_cat, int(first_line_no),
+                                     workspace.data_ptr(), record.data_ptr(), record.data_ptr() + 24, err, stream),
+               "mi_ctr_text_index")
+    lines, kept, consumed, word = record.tolist()
+    if out is None:
+        out = (torch.zeros((kept, F), dtype=torch.int64, device=dev), torch.zeros(kept, dtype=torch.uint8, device=dev),
+               torch.zeros(kept, dtype=torch.int64, device=dev))
+    keys, labels, line_no = out
+    _lib.require_gpu(text, keys, labels, line_no)
+    for t, dtype, tail in ((keys, torch.int64, (F,)), (labels, torch.uint8, ()), (line_no, torch.int64, ())):
+        if t.dtype != dtype or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < kept \
+                or not t.is_contiguous():
+            raise ValueError(f"out must be (int64 [>= {kept}, {F}], uint8 [>= {kept}], int64 [>= {kept}]), all contiguous")
+    _lib.check(lib.mi_ctr_text_parse(text.data_ptr(), nbytes, n_int, n_cat, workspace.data_ptr(), kept, int(first_line_no),
+                                     thresholds.data_ptr(), thresholds.numel(), keys.data_ptr(), labels.data_ptr(),
+                                     line_no.data_ptr(), record.data_ptr() + 24, err, stream), "mi_ctr_text_parse")
+    if own or word != -1:
+        _raise_refusal(record)
+    return keys[:kept], labels[:kept], line_no[:kept], lines, consumed
+
+
+def parse_criteo_text(source, device="cuda", chunk_bytes: int = 1 << 28, n_int: int = NUM_INT_FEATS,
+                      n_cat: int = NUM_FEATS - NUM_INT_FEATS) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`read_criteo_text` on the device: (keys int64 [n, n_int + n_cat], labels uint8 [n], line_no int64 [n]), all on
+    `device`, equal element for element to the host reader's on every file both accept.  The device enforces the grammar
+    of include/mi355x_recsys.h strictly and raises ValueError, naming the lowest offending line and column, where
+    `read_criteo_text` would be lenient; it never returns keys that differ from the host's.
+
+    source: a path, a bytes-like object, or a uint8 tensor on the host or the device.  Host sources are read in chunks of
+    at most `chunk_bytes`, each cut after its last newline (host memory stays O(chunk_bytes), no Python object per line);
+    a device tensor is walked in place.  The result does not depend on `chunk_bytes`; a line longer than it is a
+    ValueError.  The only read-back per chunk is the record {lines, kept, consumed, refusal}, plus one word at the end;
+    the record belongs to the call, so concurrent calls share nothing but the read-only threshold table."""
+    device = torch.device(device)
+    if chunk_bytes < 1 or chunk_bytes > 2 ** 31 - 1:
+        raise ValueError("chunk_bytes must lie in [1, 2^31 - 1]")
+    if n_int < 0 or n_cat < 0:
+        raise ValueError("n_int and n_cat must not be negative")
+    F = n_int + n_cat
+    parts, state = [], {"line": 0, "ws": None, "record": None}
+
+    def one(text: torch.Tensor, final: bool) -> int:
+        lib = _lib.load()
+        need = int(lib.mi_ctr_text_workspace_bytes(text.numel(), n_int, n_cat))
+        if state["ws"] is None or state["ws"].numel() < need:
+            state["ws"] = None                                       # (released before the larger one is taken)
+            state["ws"] = torch.zeros(need, dtype=torch.uint8, device=text.device)
+        if state["record"] is None:
+            state["record"] = _new_record(text.device)
+        keys, labels, line_no, lines, consumed = ctr_text_chunk(text, final, state["line"], n_int, n_cat,
+                                                                workspace=state["ws"], record=state["record"])
+        parts.append((keys, labels, line_no))
+        state["line"] += lines
+        return consumed
+
+    if isinstance(source, torch.Tensor) and source.is_cuda:
+        if source.dtype != torch.uint8 or source.dim() != 1:
+            raise TypeError("a tensor source must be a uint8 vector")
+        text, at, total = source.contiguous(), 0, source.numel()
+        device = text.device
+        while at < total:
+            final = at + chunk_bytes >= total
+            consumed = one(text[at:at + chunk_bytes], final)
+            if consumed == 0:
+                raise ValueError(f"a line is longer than chunk_bytes = {chunk_bytes}")
+            at += consumed
+    else:
+        if isinstance(source, (str, os.PathLike)):
+            f = open(source, "rb", buffering=0)
+            status = os.fstat(f.fileno())
+            total = status.st_size if stat.S_ISREG(status.st_mode) else None      # (a pipe's size says nothing)
+        else:
+            if isinstance(source, torch.Tensor):
+                if source.dtype != torch.uint8 or source.dim() != 1:
+                    raise TypeError("a tensor source must be a uint8 vector")
+                source = source.contiguous().numpy()
+            f = _ViewReader(source)
+            total = len(f.view)
+        with f:
+            for chunk, final in _cut_chunks(f.readinto, chunk_bytes, total):
+                one(torch.frombuffer(chunk, dtype=torch.uint8).to(device), final)
+    if parts:
+        _raise_refusal(state["record"])
+    if not parts:
+        keys = torch.zeros((0, F), dtype=torch.int64, device=device)
+        _lib.require_gpu(keys)
+        return keys, torch.zeros(0, dtype=torch.uint8, device=device), torch.zeros(0, dtype=torch.int64, device=device)
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
+
+class _ViewReader:
+    """`readinto` over any bytes-like object."""
+
+    def __init__(self, source):
+        self.view, self.at = memoryview(source).cast("B"), 0
+
+    def readinto(self, buffer) -> int:
+        n = min(len(buffer), len(self.view) - self.at)
+        buffer[:n] = self.view[self.at:self.at + n]
+        self.at += n
+        return n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.view.release()
 
 
 def _records_out(records_i32: torch.Tensor) -> torch.Tensor:
@@ -215,20 +442,34 @@ class DeviceCTRDataset:
 
     @classmethod
     def from_criteo_text(cls, path: str, train_test_info=None, dataset_name: Optional[str] = None, min_threshold: int = 10,
-                         device="cuda") -> "DeviceCTRDataset":
+                         device="cuda", reader: str = "host") -> "DeviceCTRDataset":
         """The whole file encoded (the vocabulary counts every line, as the reference's cache does); with `train_test_info`
         (the reference's `torch.load`-able dict, or the dict itself) the dataset is the view over `dataset_name`'s line
-        numbers, sorted as the reference sorts them."""
-        keys, labels, line_no = read_criteo_text(path)
+        numbers, sorted as the reference sorts them.  reader: "host" reads the text with `read_criteo_text`, "device"
+        with `parse_criteo_text` (the same keys, strict about the grammar), whose tensors never leave the device."""
+        if reader not in ("host", "device"):
+            raise ValueError(f"reader must be 'host' or 'device'; got {reader!r}")
+        if reader == "device":
+            keys, labels, line_no = parse_criteo_text(path, device=device)
+        else:
+            keys, labels, line_no = read_criteo_text(path)
         records, field_dims = encode_ctr_columns(keys, labels, min_threshold, device)
         index = None
         if train_test_info is not None:
             info = train_test_info if isinstance(train_test_info, dict) else torch.load(train_test_info, weights_only=False)
             lines = np.sort(np.asarray(list(info[dataset_name]), dtype=np.int64))
-            index = np.searchsorted(line_no, lines)
-            if lines.size and (index.max() >= line_no.size or not np.array_equal(line_no[index], lines)):
-                raise ValueError(f"{dataset_name!r} names a line the file does not hold (or one that was skipped)")
-            index = torch.from_numpy(index)
+            missing = f"{dataset_name!r} names a line the file does not hold (or one that was skipped)"
+            if reader == "device":
+                wanted = torch.from_numpy(lines).to(line_no.device)
+                index = torch.searchsorted(line_no, wanted)
+                if lines.size and (line_no.numel() == 0 or not torch.equal(
+                        line_no[index.clamp(max=line_no.numel() - 1)], wanted)):
+                    raise ValueError(missing)
+            else:
+                index = np.searchsorted(line_no, lines)
+                if lines.size and (index.max() >= line_no.size or not np.array_equal(line_no[index], lines)):
+                    raise ValueError(missing)
+                index = torch.from_numpy(index)
         return cls(records, field_dims, index=index, device=device)
 
 
