@@ -1031,6 +1031,8 @@ MI_API int mi_adam_tick_multi(float *const *steps, float *const *step_sizes, int
  *   The betas are doubles: 1 - beta is formed in double and then rounded (1.f - 0.999f is off by 1.3e-5).
  *   tickets (nullable): ceil(count/24) device words, zero between calls — the last workgroup of each launch advances the
  *   step counts itself; without them a second one-wave launch does.
+ *   Entries with numels[i] == 0 are skipped (their pointers are not read and their step counts do not advance: the
+ *   caller counts those steps itself); each launch takes the next 24 non-empty entries, so no entry is updated twice.
  */
 MI_API int mi_adam_dense_multi(float *const *params, const float *const *grads, float *const *exp_avgs,
                                float *const *exp_avg_sqs, float *const *steps, const int64_t *numels,

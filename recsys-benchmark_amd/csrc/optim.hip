@@ -381,10 +381,12 @@ int mi_adam_dense_multi(float *const *params, const float *const *grads, float *
   if (count == 0) return MI_OK;
   if (!params || !grads || !exp_avgs || !exp_avg_sqs || !steps || !numels) return MI_ERR_INVALID_ARG;
   int launch = 0;
-  for (int32_t first = 0; first < count; first += kAdamTensors) {
+  // zero-element entries are skipped (nothing to update, their step counts stay), so a launch may consume more than
+  // kAdamTensors entries: the next one starts at the entry where this one stopped
+  for (int32_t i = 0; i < count;) {
     AdamDenseTable t{};
     int64_t chunks = 0;
-    for (int32_t i = first; i < count && t.count < kAdamTensors; ++i) {
+    for (; i < count && t.count < kAdamTensors; ++i) {
       if (numels[i] < 0) return MI_ERR_INVALID_ARG;
       if (numels[i] == 0) continue;
       if (!params[i] || !grads[i] || !exp_avgs[i] || !exp_avg_sqs[i] || !steps[i]) return MI_ERR_INVALID_ARG;

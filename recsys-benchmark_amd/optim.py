@@ -195,6 +195,10 @@ class Adam(torch.optim.Adam):
                                                beta2, group["eps"], group["weight_decay"], self._tickets(dev, n).data_ptr(),
                                                _lib.stream_ptr(dev)),
                        "mi_adam_dense_multi")
+            # the kernel skips zero-element tensors; torch.optim.Adam still counts their steps
+            empty = [s for t, s in zip(params, steps) if t.numel() == 0]
+            if empty:
+                torch._foreach_add_(empty, 1)
         return loss
 
 

@@ -22,8 +22,10 @@ def test_sparse_adam_matches_torch(N, D, n):
     mine = torch.nn.Parameter(W0.clone().to(DEV))
     oref = torch.optim.SparseAdam([ref], lr=0.01)
     omine = SparseAdam([mine], lr=0.01)
+    untouched = torch.ones(N, dtype=torch.bool)
     for step in range(3):
         rows = (N * torch.rand(n, generator=gen).pow(3)).long().clamp_(max=N - 1)    # skewed: many duplicates
+        untouched[rows] = False
         vals = torch.randn(n, D, generator=gen)
         ref.grad = torch.sparse_coo_tensor(rows.view(1, -1), vals, (N, D))
         mine.grad = torch.sparse_coo_tensor(rows.view(1, -1).to(DEV), vals.to(DEV), (N, D), check_invariants=False)
@@ -33,8 +35,10 @@ def test_sparse_adam_matches_torch(N, D, n):
     assert_close(mine, ref, 1e-4, 1e-5, "param")
     assert_close(omine.state[mine]["exp_avg"], oref.state[ref]["exp_avg"], 1e-4, 1e-5, "exp_avg")
     assert_close(omine.state[mine]["exp_avg_sq"], oref.state[ref]["exp_avg_sq"], 1e-4, 1e-6, "exp_avg_sq")
-    untouched = torch.ones(N, dtype=torch.bool)
-    untouched[rows] = False
+    # rows no step touched: the parameter keeps its bits, both moments stay zero
+    assert torch.equal(mine.detach().cpu()[untouched], W0[untouched]), "an untouched parameter row changed"
+    assert not bool(omine.state[mine]["exp_avg"].cpu()[untouched].any()), "an untouched exp_avg row is not zero"
+    assert not bool(omine.state[mine]["exp_avg_sq"].cpu()[untouched].any()), "an untouched exp_avg_sq row is not zero"
     assert omine.state[mine]["step"] == 3
 
 
