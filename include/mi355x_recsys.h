@@ -1707,6 +1707,65 @@ MI_API int mi_ctr_text_parse(const uint8_t *text, int64_t nbytes, int32_t n_int,
                              int64_t *keys_out, uint8_t *labels_out, int64_t *line_no_out, uint64_t *err_record, int *err,
                              void *stream);
 
+/* ---- delimited text by a column spec: Avazu and KDD 2012 track 2 on the device (src/dataset/avazu/avazu_fm.py,
+ * avazu_on_ram.py `_create_binary`, avazu/utils.py, src/dataset/kdd/kdd_dataset.py; the host readers are `read_avazu_text`
+ * and `read_kdd_text` of ctr_data.py) ---------------------------------------------------------------------------------------
+ * A chunk of the file's bytes in; keys int64[n, F_out], labels uint8[n] and 0-based line numbers int64[n] of the n kept
+ * lines out, equal element for element to the host reader's on every file both accept.  The index kernels are the ones of
+ * the Criteo reader above (ONE body), given the separator byte and the header count.  The grammar, enforced strictly:
+ *   lines     a line is a run of bytes ended by '\n'; a non-empty run after the file's last '\n' is a line too.  The first
+ *             n_header (0 or 1) lines of THE CHUNK are a header: never kept and never counted (the caller passes 1 for a
+ *             file's first chunk only).  The other lines are numbered from first_line_no, skipped ones included: numbering
+ *             starts at the line after the header.  A line is kept when it has exactly n_cols - 1 bytes equal to sep_byte
+ *             (',' or '\t'; any byte but 0, '\n' and '\r' is taken).  A skipped line's content is ignored.  A '\r' byte
+ *             anywhere, the header included, is refused (one in the header is named as line first_line_no).
+ *   columns   spec int32[n_cols] on the device: entry c = kind | (output column << 8) for file column c.  The key kinds
+ *             (TOKEN8, DEC64, TIME) must name the output columns 0 .. F - 1 once each, F being their number; other kinds'
+ *             output column is ignored.  One column should be a label kind and at most one a TIME.
+ *   SKIP         anything without '\r'; nothing of the field is read.
+ *   LABEL01      exactly the byte '0' or '1': the label.
+ *   LABEL_COUNT  1 to 18 decimal digits, no sign (leading zeros are fine): label = (value >= 1).
+ *   TOKEN8       0 to 8 bytes, each in 0x21 .. 0x7E.  The key is the bytes big-endian in a 64-bit word, zero-padded at the
+ *                low end, as int64; an empty field gives key 0.  Injective on accepted strings because NUL is not accepted.
+ *                Refused: longer than 8 bytes, or any other byte (a space, 0x7F, 0x80 .., NUL).
+ *   DEC64        1 to 20 decimal digits, no sign, no leading zero except "0" itself, value <= 2^64 - 1: the key is the
+ *                value's 64-bit pattern as int64.  Refused: an empty field, '+', a leading zero, 21 or more digits, a value
+ *                above 2^64 - 1.
+ *   TIME         with derive_time == 0 a plain TOKEN8.  With derive_time != 0 (and a TIME column in the spec, F_out = F + 3,
+ *                else F_out = F): exactly 8 digits yymmddHH; the key is the TOKEN8 key of those bytes, and three derived
+ *                keys go to output columns F, F + 1 and F + 2: hour, weekday with Monday as 0, and weekday >= 5.  The year
+ *                is 2000 + yy for yy <= 68, else 1900 + yy (Python's %y).  The weekday comes from a days-from-civil
+ *                computation in integers.  Month 1 to 12, a day valid for the month with leap years, and hour 0 to 23;
+ *                otherwise, or when the field is not exactly 8 digits, the field is refused.
+ *   refused   a field longer than 20 bytes in any column but a SKIP one, an unknown kind, and everything the kinds refuse.
+ *             A refusal lowers *err_record to (line number << 16) | file column by a 64-bit atomic minimum, exactly as the
+ *             Criteo reader does: the LOWEST offending (line, column) stays.  Outputs of a refused field are zero.
+ * mi_ctr_table_index: the six launches of mi_ctr_text_index; record int64[3] = {lines counted (the header is not), kept
+ *   lines, bytes consumed}.  workspace: mi_ctr_table_workspace_bytes(nbytes, n_cols) bytes (about 8 nbytes), 16-byte
+ *   aligned, nothing in it needs zeroing.  n_cols in [1, 256] (above: MI_ERR_UNSUPPORTED; 0 from the size function).
+ * mi_ctr_table_parse: ONE launch, one lane per (kept line, file column): the lane reads the two separator positions around
+ *   its field, loads at most 20 bytes with predicated loads that do not depend on one another, and converts them; the same
+ *   text, nbytes, sep_byte, n_cols, first_line_no and workspace as the index call before it (the header count is read from
+ *   the workspace), n_kept = record[1].  Every element of keys_out[n_kept, F_out], labels_out[n_kept] and
+ *   line_no_out[n_kept] is written (by a spec as described above), nothing beyond.  n_kept == 0: MI_OK, no launch.
+ * Integer arithmetic and plain vector stores; no arrival order enters any value, so reruns give the same bits.  Atomics
+ * appear only on the error path: *err_record and MI_IDX_OUT_OF_RANGE ORed into *err (NULL is fine) by a workspace
+ * subscript or an output column that fails its check.  Every byte and workspace subscript is checked before use.        */
+#define MI_CTR_COL_SKIP 0
+#define MI_CTR_COL_LABEL01 1
+#define MI_CTR_COL_LABEL_COUNT 2
+#define MI_CTR_COL_TOKEN8 3
+#define MI_CTR_COL_DEC64 4
+#define MI_CTR_COL_TIME 5
+MI_API int64_t mi_ctr_table_workspace_bytes(int64_t nbytes, int32_t n_cols);
+MI_API int mi_ctr_table_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int32_t sep_byte, int32_t n_cols,
+                              int32_t n_header, int64_t first_line_no, void *workspace, int64_t *record,
+                              uint64_t *err_record, int *err, void *stream);
+MI_API int mi_ctr_table_parse(const uint8_t *text, int64_t nbytes, int32_t sep_byte, int32_t n_cols, const int32_t *spec,
+                              int32_t derive_time, const void *workspace, int64_t n_kept, int64_t first_line_no,
+                              int64_t *keys_out, uint8_t *labels_out, int64_t *line_no_out, uint64_t *err_record, int *err,
+                              void *stream);
+
 /* ---- profiling ring (bench.py's per-kernel HIP-event timing) ---------------
  * When enabled every launcher brackets its kernel with a hipEvent pair on the
  * launch stream.  Not for use under graph capture.

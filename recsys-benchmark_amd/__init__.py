@@ -6,8 +6,8 @@ C-ABI HIP library libmi355x_recsys.so (include/mi355x_recsys.h).  See DESIGN.md.
 from . import _lib
 from ._lib import MI355XLibraryError, check_index_errors
 from .cf_data import (DeviceCFGraphDataset, DeviceCFLoader, DeviceCFTestDataset, DeviceCFTestLoader, DeviceTruth)
-from .ctr_data import (DeviceCTRDataset, DeviceCTRLoader, encode_ctr_columns, numeric_thresholds, parse_criteo_text,
-                       read_criteo_text)
+from .ctr_data import (DeviceCTRDataset, DeviceCTRLoader, encode_ctr_columns, make_train_test_info, numeric_thresholds,
+                       parse_avazu_text, parse_criteo_text, parse_kdd_text, read_avazu_text, read_criteo_text, read_kdd_text)
 from .ctr_metric import CTRMetric
 from .deepfm import DeepFM
 from .embeddings import IEmbedding, NAME_TO_CLS, VanillaEmbedding, get_embedding
@@ -59,4 +59,5 @@ __all__ = [
     "DeviceCFGraphDataset", "DeviceCFLoader", "DeviceCFTestDataset", "DeviceCFTestLoader", "DeviceTruth",
     "pruned_ctr_checkpoint", "load_pruned_ctr_model",
     "DeviceCTRDataset", "DeviceCTRLoader", "encode_ctr_columns", "read_criteo_text", "parse_criteo_text", "numeric_thresholds",
+    "read_avazu_text", "read_kdd_text", "parse_avazu_text", "parse_kdd_text", "make_train_test_info",
 ]

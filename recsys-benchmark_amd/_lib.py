@@ -238,6 +238,9 @@ SIGNATURES = {
     "mi_ctr_text_workspace_bytes": [_i64, _i32, _i32],
     "mi_ctr_text_index": [_p, _i64, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p],
     "mi_ctr_text_parse": [_p, _i64, _i32, _i32, _p, _i64, _i64, _p, _i32, _p, _p, _p, _p, _p, _p],
+    "mi_ctr_table_workspace_bytes": [_i64, _i32],
+    "mi_ctr_table_index": [_p, _i64, _i32, _i32, _i32, _i32, _i64, _p, _p, _p, _p, _p],
+    "mi_ctr_table_parse": [_p, _i64, _i32, _i32, _p, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p],
     "mi_comm_available": [],
     "mi_comm_unique_id": [ctypes.c_char_p],
     "mi_comm_init": [ctypes.c_char_p, _i32, _i32, ctypes.POINTER(ctypes.c_void_p)],
@@ -260,7 +263,8 @@ _RESTYPES = {"mi_strerror": ctypes.c_char_p, "mi_route_workspace_elems": ctypes.
              "mi_ctr_metric_append_workspace_bytes": ctypes.c_int64,
              "mi_cerp_prune_loss_workspace_elems": ctypes.c_int64,
              "mi_gather_fm_qat_bwd_workspace_elems": ctypes.c_int64, "mi_ctr_vocab_workspace_bytes": ctypes.c_int64,
-             "mi_ctr_text_workspace_bytes": ctypes.c_int64}
+             "mi_ctr_text_workspace_bytes": ctypes.c_int64,
+             "mi_ctr_table_workspace_bytes": ctypes.c_int64}
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()

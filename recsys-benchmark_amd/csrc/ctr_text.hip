@@ -21,6 +21,11 @@
 // of `convert_numeric_feature` is not evaluated: the key of v > 2 is the number of entries <= v of the caller's threshold
 // table, one binary search.
 //
+// Other delimited formats (mi_ctr_table_index / mi_ctr_table_parse: Avazu's comma-separated file with a header, KDD 2012
+// track 2's tab-separated one; src/dataset/avazu/avazu_on_ram.py, src/dataset/kdd/kdd_dataset.py) run the SAME six index
+// kernels, which take the separator byte and the number of header lines (never kept, never counted) from their argument
+// record, and one parse kernel that converts a field by the kind its column has in a caller's spec (k_table_parse).
+//
 // Integer arithmetic and plain vector stores only; no arrival order enters any value, so reruns give the same bits.
 // The only atomics are on the error path: the OR into the error word (a subscript that fails its check: never with a
 // workspace this file wrote), the 64-bit minimum that keeps the lowest offending (line, column) in *err_record, and the
@@ -42,13 +47,15 @@ inline int64_t tiles_of(int64_t n) { return (n + kBlock - 1) / kBlock; }
 inline int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 inline int grid_for_tiles(int64_t tiles) { return (int)(tiles < 1 ? 1 : (tiles > kMaxGrid ? kMaxGrid : tiles)); }
 
-// the workspace: totals {separators, lines, lowest '\r' as (line << 32 | separators before it), kept lines}, then the arrays
+// the workspace: totals {separators, lines, lowest '\r' as (line << 32 | separators before it), kept lines, header lines},
+// then the arrays
 struct Text {
   const uint8_t *text;
   int64_t nbytes, first_line_no;
   int64_t cap, kept_cap;                 // entries of sep_pos / nl_sep, of kept_line
   int64_t byte_tiles;
-  int misalign, final, F;
+  int misalign, final, F;              // F: the separators of a kept line
+  int sep, n_header;                     // the field separator byte; leading lines of the chunk never kept nor counted
   unsigned long long *totals;
   uint32_t *tile_seps, *tile_nls, *line_tiles, *sep_pos, *nl_sep, *kept_line;
   int64_t *record;
@@ -63,7 +70,7 @@ int64_t lay_out(Text &t, void *workspace, int64_t nbytes, int F) {
   const int64_t byte_tiles = (nbytes + 1 + (kLaneBytes - 1) + kTileBytes - 1) / kTileBytes, line_tiles = tiles_of(t.cap);
   int64_t at = 0;
   auto take = [&](int64_t bytes) { int64_t here = at; at += align16(bytes); return base + (uintptr_t)here; };
-  t.totals = reinterpret_cast<unsigned long long *>(take(4 * 8));
+  t.totals = reinterpret_cast<unsigned long long *>(take(5 * 8));
   t.tile_seps = reinterpret_cast<uint32_t *>(take(byte_tiles * 4));
   t.tile_nls = reinterpret_cast<uint32_t *>(take(byte_tiles * 4));
   t.line_tiles = reinterpret_cast<uint32_t *>(take(line_tiles * 4));
@@ -100,7 +107,7 @@ __device__ __forceinline__ Masks classify(const Text &a, int64_t b0, bool virt) 
   for (int j = 0; j < kLaneBytes; ++j) {
     const uint32_t ch = (w[j >> 2] >> (8 * (j & 3))) & 255u;
     m.nl |= (uint32_t)(ch == '\n') << j;
-    m.sep |= (uint32_t)(ch == '\n' || ch == '\t') << j;
+    m.sep |= (uint32_t)(ch == '\n' || ch == (uint32_t)a.sep) << j;
     m.cr |= (uint32_t)(ch == '\r') << j;
   }
   if (virt && b0 <= a.nbytes && a.nbytes < b0 + kLaneBytes) {
@@ -187,10 +194,15 @@ __global__ __launch_bounds__(kBlock) void k_text_scatter(Text a) {
   }
 }
 
-// line l of the chunk has exactly F tabs; l < n_lines <= cap
+// line l of the chunk is past the header and has exactly F field separators; l < n_lines <= cap
 __device__ __forceinline__ bool line_kept(const Text &a, int64_t l) {
   const int64_t first = l ? (int64_t)a.nl_sep[l - 1] + 1 : 0;
-  return (int64_t)a.nl_sep[l] - first == a.F;
+  return l >= a.n_header && (int64_t)a.nl_sep[l] - first == a.F;
+}
+
+// the file's number of line l of the chunk: the header is not counted (an offence in it is named as the line after it)
+__device__ __forceinline__ int64_t line_number(const Text &a, int64_t header, int64_t l) {
+  return a.first_line_no + (l > header ? l - header : 0);
 }
 
 __global__ __launch_bounds__(kBlock) void k_text_count_lines(Text a) {
@@ -220,7 +232,8 @@ __global__ __launch_bounds__(kBlock) void k_text_scan_lines(Text a) {
   }
   if (threadIdx.x == 0) {
     a.totals[3] = carry;
-    a.record[0] = n_lines;
+    a.totals[4] = (unsigned long long)a.n_header;
+    a.record[0] = n_lines - (n_lines < a.n_header ? n_lines : a.n_header);
     a.record[1] = (int64_t)carry;
     const unsigned long long cr = a.totals[2];
     if (cr != kNoError) {
@@ -228,7 +241,7 @@ __global__ __launch_bounds__(kBlock) void k_text_scan_lines(Text a) {
       if (line < n_lines) {
         int64_t col = seps - (line ? (int64_t)a.nl_sep[line - 1] + 1 : 0);
         col = col < 0 ? 0 : (col > (1 << kColBits) - 1 ? (1 << kColBits) - 1 : col);
-        atomicMin(a.err_record, ((unsigned long long)(a.first_line_no + line) << kColBits) | (unsigned long long)col);
+        atomicMin(a.err_record, ((unsigned long long)line_number(a, a.n_header, line) << kColBits) | (unsigned long long)col);
       }
     }
   }
@@ -387,15 +400,160 @@ __global__ __launch_bounds__(kBlock) void k_text_parse(Parse a) {
   }
 }
 
-// the checks both entry points share; fills everything of `t` but record / err_record / err
-int set_up(Text &t, const uint8_t *text, int64_t nbytes, int32_t n_int, int32_t n_cat, int64_t first_line_no, void *workspace) {
-  if (nbytes < 0 || n_int < 0 || n_cat < 0 || first_line_no < 0 || !workspace || (nbytes > 0 && !text)) return MI_ERR_INVALID_ARG;
-  if (nbytes > (int64_t)INT32_MAX || (int64_t)n_int + n_cat + 1 >= (1 << kColBits) || first_line_no > ((int64_t)1 << 46))
+// ---- the column-spec reader (mi_ctr_table_parse): the grammar of a column is a kind, not a position ---------------------
+constexpr int kTableBytes = 20, kTokenBytes = 8, kLabelDigits = 18, kMaxCols = 256;
+constexpr unsigned long long kMaxTenth = 1844674407370955161ull;         // (2^64 - 1) / 10; 2^64 - 1 ends in 5
+
+struct TableParse {
+  Text t;
+  int64_t n_kept;
+  const int32_t *spec;
+  int derive_time;
+  int64_t *keys;
+  uint8_t *labels;
+  int64_t *line_no;
+};
+
+// Monday = 0.  Days since 1970-01-01 (a Thursday) by the days-from-civil count over 400-year eras; y >= 1
+__device__ __forceinline__ int weekday_of(int y, int m, int d) {
+  y -= m <= 2;
+  const int era = y / 400, yoe = y - era * 400;
+  const int doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5 + d - 1;
+  const int doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+  const int days = era * 146097 + doe - 719468;
+  return (days + 3 + 7 * 146097) % 7;
+}
+
+__global__ __launch_bounds__(kBlock) void k_table_parse(TableParse a) {
+  __shared__ uint32_t sm[kWavesPerBlock];
+  const Text &t = a.t;
+  const int64_t w = t.F + 1, total = a.n_kept * w;                        // w file columns, w <= kMaxCols = kBlock
+  // F = the spec's number of key columns (low half), its number of TIME columns (high half): every workgroup counts them
+  uint32_t mine = 0, counts;
+  if ((int64_t)threadIdx.x < w) {
+    const int kind = a.spec[threadIdx.x] & 255;
+    mine = (uint32_t)(kind == MI_CTR_COL_TOKEN8 || kind == MI_CTR_COL_DEC64 || kind == MI_CTR_COL_TIME) |
+           ((uint32_t)(kind == MI_CTR_COL_TIME) << 16);
+  }
+  block_excl_scan(mine, sm, &counts);
+  const int F = (int)(counts & 0xFFFFu);
+  const bool timed = a.derive_time != 0 && (counts >> 16) != 0;
+  const int64_t F_out = F + (timed ? 3 : 0);
+  const bool narrow = total <= (int64_t)UINT32_MAX;
+  const int64_t n_seps = (int64_t)t.totals[0] < t.cap ? (int64_t)t.totals[0] : t.cap;
+  const int64_t n_lines = (int64_t)t.totals[1] < t.cap ? (int64_t)t.totals[1] : t.cap;
+  const int64_t kept = (int64_t)t.totals[3] < t.kept_cap ? (int64_t)t.totals[3] : t.kept_cap;
+  const int64_t header = t.totals[4] ? 1 : 0;                             // what the index call was given
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += stride) {
+    int64_t k;
+    int c;
+    if (narrow) {
+      const uint32_t q = (uint32_t)e / (uint32_t)w;
+      k = q;
+      c = (int)((uint32_t)e - q * (uint32_t)w);
+    } else {
+      k = e / w;
+      c = (int)(e - k * w);
+    }
+    const int32_t entry = a.spec[c];                                      // c < w
+    const int kind = entry & 255;
+    const int64_t oc = entry >> 8;
+    const bool reads = kind != MI_CTR_COL_SKIP;
+    // field c of kept line k lies between separators si - 1 and si
+    bool ok = k < kept;
+    const int64_t line = ok ? (int64_t)t.kept_line[k] : 0;
+    ok = ok && line < n_lines;
+    const int64_t si = (ok && line ? (int64_t)t.nl_sep[line - 1] + 1 : 0) + c;
+    ok = ok && si < n_seps;
+    const int64_t end = ok && reads ? (int64_t)(t.sep_pos[si] & kPosMask) : 0;
+    const int64_t begin = ok && reads && si ? (int64_t)(t.sep_pos[si - 1] & kPosMask) + 1 : 0;
+    ok = ok && begin <= end && end <= t.nbytes;
+    const bool fits = end - begin <= kTableBytes;                         // a longer field is refused unread
+    const int len = ok && reads && fits ? (int)(end - begin) : 0;
+    uint32_t ch[kTableBytes];
+#pragma unroll
+    for (int i = 0; i < kTableBytes; ++i) ch[i] = i < len ? (uint32_t)t.text[begin + i] : 0u;     // begin + len <= nbytes
+    // every reading of the bytes, whatever the kind: the kind picks among them below
+    bool digits = true, printable = true;
+    unsigned long long v = 0, token = 0;
+    bool over = false;
+#pragma unroll
+    for (int i = 0; i < kTableBytes; ++i) {
+      if (i < len) {
+        const uint32_t d = ch[i] - '0';
+        digits = digits && d <= 9u;
+        if (i == kTableBytes - 1) over = v > kMaxTenth || (v == kMaxTenth && (d & 15u) > 5u);
+        v = v * 10ull + (d & 15u);                                        // 19 digits: < 16 * 10^19 / 9 < 2^64
+        if (i < kTokenBytes) {
+          printable = printable && ch[i] - 0x21u <= 0x5Du;
+          token |= (unsigned long long)ch[i] << (56 - 8 * i);
+        }
+      }
+    }
+    bool good = true;
+    int64_t key = 0;
+    int label = 0, hour = 0, weekday = 0;
+    if (kind == MI_CTR_COL_LABEL01) {
+      good = len == 1 && (ch[0] == '0' || ch[0] == '1');
+      label = ch[0] == '1';
+    } else if (kind == MI_CTR_COL_LABEL_COUNT) {
+      good = len >= 1 && len <= kLabelDigits && digits;
+      label = v >= 1ull;
+    } else if (kind == MI_CTR_COL_TOKEN8 || kind == MI_CTR_COL_TIME) {
+      good = len <= kTokenBytes && printable;
+      key = (int64_t)token;
+      if (kind == MI_CTR_COL_TIME && timed) {
+        const int yy = (int)((ch[0] - '0') * 10 + (ch[1] - '0')), mm = (int)((ch[2] - '0') * 10 + (ch[3] - '0'));
+        const int dd = (int)((ch[4] - '0') * 10 + (ch[5] - '0'));
+        hour = (int)((ch[6] - '0') * 10 + (ch[7] - '0'));
+        const int year = yy <= 68 ? 2000 + yy : 1900 + yy;
+        const bool leap = (year % 4 == 0 && year % 100 != 0) || year % 400 == 0;
+        const int month_days = mm == 2 ? 28 + (int)leap : 30 + ((mm + (mm >> 3)) & 1);
+        good = len == 8 && digits && mm >= 1 && mm <= 12 && dd >= 1 && dd <= month_days && hour <= 23;
+        weekday = good ? weekday_of(year, mm, dd) : 0;
+      }
+    } else if (kind == MI_CTR_COL_DEC64) {
+      good = len >= 1 && digits && !(len > 1 && ch[0] == '0') && !over;
+      key = (int64_t)v;
+    } else if (kind != MI_CTR_COL_SKIP) {
+      good = false;                                                       // no such kind: the column is refused
+    }
+    good = good && (fits || !reads);
+    if (ok && !good) atomicMin(t.err_record, ((unsigned long long)line_number(t, header, line) << kColBits) | (unsigned long long)c);
+    if (!ok && t.err) atomicOr(t.err, MI_IDX_OUT_OF_RANGE);
+    if (!ok || !good) key = 0, label = 0, hour = 0, weekday = 0;
+    if (c == 0) a.line_no[k] = ok ? line_number(t, header, line) : -1;
+    if (kind == MI_CTR_COL_LABEL01 || kind == MI_CTR_COL_LABEL_COUNT) a.labels[k] = (uint8_t)label;
+    if (kind == MI_CTR_COL_TOKEN8 || kind == MI_CTR_COL_DEC64 || kind == MI_CTR_COL_TIME) {
+      if (oc >= 0 && oc < F) {
+        a.keys[k * F_out + oc] = key;
+      } else if (t.err) {
+        atomicOr(t.err, MI_IDX_OUT_OF_RANGE);
+      }
+      if (kind == MI_CTR_COL_TIME && timed) {
+        a.keys[k * F_out + F] = hour;
+        a.keys[k * F_out + F + 1] = weekday;
+        a.keys[k * F_out + F + 2] = weekday >= 5;
+      }
+    }
+  }
+}
+
+// the checks the entry points share; fills everything of `t` but record / err_record / err.  A kept line has F separators
+int set_up(Text &t, const uint8_t *text, int64_t nbytes, int64_t F, int32_t sep_byte, int32_t n_header, int64_t first_line_no,
+           void *workspace) {
+  if (nbytes < 0 || F < 0 || first_line_no < 0 || !workspace || (nbytes > 0 && !text)) return MI_ERR_INVALID_ARG;
+  if (sep_byte < 1 || sep_byte > 255 || sep_byte == '\n' || sep_byte == '\r' || n_header < 0 || n_header > 1)
+    return MI_ERR_INVALID_ARG;
+  if (nbytes > (int64_t)INT32_MAX || F + 1 >= (1 << kColBits) || first_line_no > ((int64_t)1 << 46))
     return MI_ERR_UNSUPPORTED;                         // offsets stay below bit 31, (line, column) packs into 64 bits
   t.text = text;
   t.nbytes = nbytes;
   t.first_line_no = first_line_no;
-  t.F = n_int + n_cat;
+  t.F = (int)F;
+  t.sep = sep_byte;
+  t.n_header = n_header;
   t.misalign = (int)(reinterpret_cast<uintptr_t>(text) & (kLaneBytes - 1));
   t.byte_tiles = (nbytes + 1 + t.misalign + kTileBytes - 1) / kTileBytes;
   t.final = 0;
@@ -406,21 +564,8 @@ int set_up(Text &t, const uint8_t *text, int64_t nbytes, int32_t n_int, int32_t 
   return MI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t mi_ctr_text_workspace_bytes(int64_t nbytes, int32_t n_int, int32_t n_cat) {
-  if (nbytes < 0 || nbytes > (int64_t)INT32_MAX || n_int < 0 || n_cat < 0) return 0;
-  Text t;
-  return lay_out(t, nullptr, nbytes, n_int + n_cat);
-}
-
-int mi_ctr_text_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int32_t n_int, int32_t n_cat,
-                      int64_t first_line_no, void *workspace, int64_t *record, uint64_t *err_record, int *err, void *stream) {
-  Text t;
-  const int rc = set_up(t, text, nbytes, n_int, n_cat, first_line_no, workspace);
-  if (rc != MI_OK) return rc;
+// the six index launches over a chunk that set_up described
+int launch_index(Text &t, int32_t is_final, int64_t *record, uint64_t *err_record, int *err, void *stream) {
   if (!record || !err_record) return MI_ERR_INVALID_ARG;
   t.final = is_final != 0;
   t.record = record;
@@ -436,11 +581,31 @@ int mi_ctr_text_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int
   return launch_status();
 }
 
+}  // namespace
+
+extern "C" {
+
+int64_t mi_ctr_text_workspace_bytes(int64_t nbytes, int32_t n_int, int32_t n_cat) {
+  if (nbytes < 0 || nbytes > (int64_t)INT32_MAX || n_int < 0 || n_cat < 0) return 0;
+  Text t;
+  return lay_out(t, nullptr, nbytes, n_int + n_cat);
+}
+
+int mi_ctr_text_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int32_t n_int, int32_t n_cat,
+                      int64_t first_line_no, void *workspace, int64_t *record, uint64_t *err_record, int *err, void *stream) {
+  if (n_int < 0 || n_cat < 0) return MI_ERR_INVALID_ARG;
+  Text t;
+  const int rc = set_up(t, text, nbytes, (int64_t)n_int + n_cat, '\t', 0, first_line_no, workspace);
+  if (rc != MI_OK) return rc;
+  return launch_index(t, is_final, record, err_record, err, stream);
+}
+
 int mi_ctr_text_parse(const uint8_t *text, int64_t nbytes, int32_t n_int, int32_t n_cat, const void *workspace, int64_t n_kept,
                       int64_t first_line_no, const int64_t *thresholds, int32_t n_thresholds, int64_t *keys_out,
                       uint8_t *labels_out, int64_t *line_no_out, uint64_t *err_record, int *err, void *stream) {
+  if (n_int < 0 || n_cat < 0) return MI_ERR_INVALID_ARG;
   Parse a;
-  const int rc = set_up(a.t, text, nbytes, n_int, n_cat, first_line_no, const_cast<void *>(workspace));
+  const int rc = set_up(a.t, text, nbytes, (int64_t)n_int + n_cat, '\t', 0, first_line_no, const_cast<void *>(workspace));
   if (rc != MI_OK) return rc;
   if (n_kept < 0 || n_thresholds < 0 || !err_record || (n_thresholds > 0 && !thresholds)) return MI_ERR_INVALID_ARG;
   if (n_kept > a.t.kept_cap) return MI_ERR_INVALID_ARG;
@@ -457,6 +622,48 @@ int mi_ctr_text_parse(const uint8_t *text, int64_t nbytes, int32_t n_int, int32_
   a.line_no = line_no_out;
   const int64_t blocks = (n_kept * (a.t.F + 1) + kBlock - 1) / kBlock;
   MI_LAUNCH("ctr_text_parse", k_text_parse, (int)(blocks > kMaxGrid ? kMaxGrid : blocks), kBlock, stream, a);
+  return launch_status();
+}
+
+int64_t mi_ctr_table_workspace_bytes(int64_t nbytes, int32_t n_cols) {
+  if (nbytes < 0 || nbytes > (int64_t)INT32_MAX || n_cols < 1 || n_cols > kMaxCols) return 0;
+  Text t;
+  return lay_out(t, nullptr, nbytes, n_cols - 1);
+}
+
+int mi_ctr_table_index(const uint8_t *text, int64_t nbytes, int32_t is_final, int32_t sep_byte, int32_t n_cols,
+                       int32_t n_header, int64_t first_line_no, void *workspace, int64_t *record, uint64_t *err_record,
+                       int *err, void *stream) {
+  if (n_cols < 1) return MI_ERR_INVALID_ARG;
+  if (n_cols > kMaxCols) return MI_ERR_UNSUPPORTED;
+  Text t;
+  const int rc = set_up(t, text, nbytes, n_cols - 1, sep_byte, n_header, first_line_no, workspace);
+  if (rc != MI_OK) return rc;
+  return launch_index(t, is_final, record, err_record, err, stream);
+}
+
+int mi_ctr_table_parse(const uint8_t *text, int64_t nbytes, int32_t sep_byte, int32_t n_cols, const int32_t *spec,
+                       int32_t derive_time, const void *workspace, int64_t n_kept, int64_t first_line_no, int64_t *keys_out,
+                       uint8_t *labels_out, int64_t *line_no_out, uint64_t *err_record, int *err, void *stream) {
+  if (n_cols < 1 || !spec) return MI_ERR_INVALID_ARG;
+  if (n_cols > kMaxCols) return MI_ERR_UNSUPPORTED;
+  TableParse a;
+  // (the header count, which only moves line numbers here, is read from the workspace the index call left)
+  const int rc = set_up(a.t, text, nbytes, n_cols - 1, sep_byte, 0, first_line_no, const_cast<void *>(workspace));
+  if (rc != MI_OK) return rc;
+  if (n_kept < 0 || !err_record || n_kept > a.t.kept_cap) return MI_ERR_INVALID_ARG;
+  if (n_kept == 0) return MI_OK;
+  if (!labels_out || !line_no_out || !keys_out) return MI_ERR_INVALID_ARG;
+  a.t.err_record = reinterpret_cast<unsigned long long *>(err_record);
+  a.t.err = err;
+  a.n_kept = n_kept;
+  a.spec = spec;
+  a.derive_time = derive_time;
+  a.keys = keys_out;
+  a.labels = labels_out;
+  a.line_no = line_no_out;
+  const int64_t blocks = (n_kept * (int64_t)n_cols + kBlock - 1) / kBlock;
+  MI_LAUNCH("ctr_table_parse", k_table_parse, (int)(blocks > kMaxGrid ? kMaxGrid : blocks), kBlock, stream, a);
   return launch_status();
 }
 

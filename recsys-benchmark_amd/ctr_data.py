@@ -13,6 +13,11 @@ What is kept from the reference: the text format (lines with another column coun
 `kept`, the record layout (label first).  What differs, on purpose: kept features are numbered in ascending key order
 (the reference numbers them in set-iteration order, which no run can reproduce; the two agree up to a renaming of the
 kept ids per field), and the shuffle is the keyed bijection of include/mi355x_recsys.h, not `torch.randperm`.
+
+Avazu (src/dataset/avazu/avazu_on_ram.py `_create_binary`, avazu/utils.py) and KDD 2012 track 2
+(src/dataset/kdd/kdd_dataset.py) are read the same way: `read_avazu_text` / `read_kdd_text` on the host,
+`parse_avazu_text` / `parse_kdd_text` on the device (one column-spec reader, mi_ctr_table_*), their feature strings as
+int64 keys that are equal exactly when the strings are; `make_train_test_info` is the reference's Avazu split.
 """
 import logging
 import math
@@ -31,6 +36,7 @@ NUM_INT_FEATS = 13
 NUM_FEATS = 39
 NULL_KEY = -(1 << 63)          # an empty integer field (the reference's "NULL")
 EMPTY_KEY = -1                 # an empty categorical field (the reference's "")
+NUM_AVAZU_FEATS, NUM_KDD_FEATS = 22, 11
 
 
 def _numeric_key(val: str) -> int:
@@ -70,6 +76,99 @@ def read_criteo_text(path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
 def _s64(v: int) -> int:
     """An integer as a two's-complement 64-bit word."""
     return ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+
+
+def _token_key(s: str) -> int:
+    """A feature string as the int64 whose big-endian bytes are the string's, zero-padded at the low end: equal exactly
+    when the strings are equal, for strings of at most 8 bytes that hold no NUL."""
+    b = s.encode()
+    if len(b) > 8 or 0 in b:
+        raise ValueError(f"no int64 key for the feature string {s!r}: more than 8 bytes, or a NUL among them")
+    return _s64(int.from_bytes(b.ljust(8, b"\0"), "big"))
+
+
+def _decimal_key(s: str) -> int:
+    """A canonical decimal id below 2^64 as the int64 with its bit pattern ("01" and "1" are different strings with one
+    value, so only the canonical form has a key)."""
+    if not (s.isascii() and s.isdigit()) or (len(s) > 1 and s[0] == "0") or len(s) > 20 or int(s) >= 1 << 64:
+        raise ValueError(f"no int64 key for the feature string {s!r}: not a canonical decimal below 2^64")
+    return _s64(int(s))
+
+
+def _host_result(rows, labels, line_no, F):
+    return (np.array(rows, dtype=np.int64).reshape(len(rows), F), np.array(labels, dtype=np.uint8),
+            np.array(line_no, dtype=np.int64))
+
+
+def read_avazu_text(path: str, preprocess_timestamp: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(keys int64 [n, 22 or 25], labels uint8 [n], line_no int64 [n]) of Avazu's comma-separated file (id, click, 22
+    feature strings, the first of them the hour as yymmddHH).  The header line is dropped; a line without 24 values is
+    skipped as the reference skips it; line_no holds the kept lines' indices after the header, skipped ones counted (the
+    reference's `train_test_info` lists).  A feature string's key is `_token_key`; with `preprocess_timestamp` three
+    more columns hold the hour, the weekday (Monday 0) and whether it is 5 or 6, from `datetime.strptime` as in the
+    reference (whose strings are these integers' decimal forms, and "True" / "False")."""
+    import datetime
+
+    token, rows, labels, line_no = {}, [], [], []
+    with open(path) as f:
+        f.readline()
+        for idx, line in enumerate(f):
+            values = line.rstrip("\n").split(",")
+            if len(values) != NUM_AVAZU_FEATS + 2:
+                continue
+            row = []
+            for s in values[2:]:
+                key = token.get(s)
+                if key is None:
+                    key = token[s] = _token_key(s)
+                row.append(key)
+            if preprocess_timestamp:
+                date = datetime.datetime.strptime(values[2], "%y%m%d%H")
+                row.extend((date.hour, date.weekday(), int(date.weekday() in [5, 6])))
+            rows.append(row)
+            labels.append(int(values[1]))
+            line_no.append(idx)
+    return _host_result(rows, labels, line_no, NUM_AVAZU_FEATS + (3 if preprocess_timestamp else 0))
+
+
+def read_kdd_text(path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(keys int64 [n, 11], labels uint8 [n], line_no int64 [n]) of KDD 2012 track 2's tab-separated file (a click count,
+    then 11 decimal ids, some above 2^63: a key is the id's 64-bit pattern).  The label is `int(values[0]) >= 1`; a line
+    without 12 values is a ValueError (the reference asserts the count)."""
+    decimal, rows, labels, line_no = {}, [], [], []
+    with open(path) as f:
+        for idx, line in enumerate(f):
+            values = line.rstrip("\n").split("\t")
+            if len(values) != NUM_KDD_FEATS + 1:
+                raise ValueError(f"line {idx} (0-based) does not hold {NUM_KDD_FEATS + 1} tab-separated values")
+            row = []
+            for s in values[1:]:
+                key = decimal.get(s)
+                if key is None:
+                    key = decimal[s] = _decimal_key(s)
+                row.append(key)
+            rows.append(row)
+            labels.append(int(int(values[0]) >= 1))
+            line_no.append(idx)
+    return _host_result(rows, labels, line_no, NUM_KDD_FEATS)
+
+
+def make_train_test_info(line_no, seed: int = 2023, split_strategy: int = 1, metadata: Optional[dict] = None) -> dict:
+    """The reference's Avazu split (`_create_binary`) of the kept lines `line_no`: {"train", "val", "test"} (lists of line
+    numbers: int(0.8 n), int(0.1 n) and the rest) and "metadata".  split_strategy 1 cuts
+    `torch.randperm(n, generator=torch.Generator().manual_seed(seed))`, which is what `random_split` draws; 0 cuts in
+    file order."""
+    if split_strategy not in (0, 1):
+        raise ValueError(f"split_strategy must be 0 (file order) or 1 (random); got {split_strategy!r}")
+    lines = (line_no.cpu() if isinstance(line_no, torch.Tensor) else torch.as_tensor(np.asarray(line_no))).reshape(-1).tolist()
+    n = len(lines)
+    num_train, num_val = int(0.8 * n), int(0.1 * n)
+    if split_strategy == 1:
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed))).tolist()
+        lines = [lines[i] for i in order]
+    info = {"train": lines[:num_train], "val": lines[num_train:num_train + num_val], "test": lines[num_train + num_val:]}
+    info["metadata"] = dict(metadata or {}, seed=seed, split_strategy=split_strategy)
+    return info
 
 
 # ---- the device text reader (csrc/ctr_text.hip; include/mi355x_recsys.h spells the grammar out) ---------------------------
@@ -146,14 +245,46 @@ def _new_record(device: torch.device) -> torch.Tensor:
     return torch.tensor([0, 0, 0, -1], dtype=torch.int64, device=device)
 
 
-def _raise_refusal(record: torch.Tensor) -> None:
+_CRITEO_REFUSAL = ("not in the strict Criteo text grammar of the device reader (a label other than 0 or 1, a malformed or "
+                   "over-long number, or a carriage return); read_criteo_text is the lenient reader")
+
+
+def _raise_refusal(record: torch.Tensor, what: str = _CRITEO_REFUSAL) -> None:
     """One read-back of the record's refusal word; ValueError if a launch so far lowered it (the word is then cleared)."""
     word = int(record[3].item())
     if word != -1:
         record[3] = -1
-        raise ValueError(f"line {word >> 16} (0-based), column {word & 0xFFFF}: not in the strict Criteo text grammar of "
-                         "the device reader (a label other than 0 or 1, a malformed or over-long number, or a carriage "
-                         "return); read_criteo_text is the lenient reader")
+        raise ValueError(f"line {word >> 16} (0-based), column {word & 0xFFFF}: {what}")
+
+
+def _run_chunk(text: torch.Tensor, final: bool, F: int, need: int, index, parse, what: str, out, workspace, record):
+    """One chunk (uint8 [nbytes], contiguous, on the device) through a format's index and parse entry points; what
+    `ctr_text_chunk` documents.  index(ws, record_ptr, err, stream) and parse(ws, kept, keys, labels, line_no, record_ptr,
+    err, stream) make the two library calls; `need` is the workspace size the format asks for."""
+    dev = _lib.require_gpu(text)
+    if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
+        raise TypeError("text must be a contiguous uint8 vector")
+    own = record is None
+    if own:
+        record = _new_record(dev)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
+    err, stream = _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)
+    index(workspace.data_ptr(), record.data_ptr(), err, stream)
+    lines, kept, consumed, word = record.tolist()
+    if out is None:
+        out = (torch.zeros((kept, F), dtype=torch.int64, device=dev), torch.zeros(kept, dtype=torch.uint8, device=dev),
+               torch.zeros(kept, dtype=torch.int64, device=dev))
+    keys, labels, line_no = out
+    _lib.require_gpu(text, keys, labels, line_no)
+    for t, dtype, tail in ((keys, torch.int64, (F,)), (labels, torch.uint8, ()), (line_no, torch.int64, ())):
+        if t.dtype != dtype or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < kept \
+                or not t.is_contiguous():
+            raise ValueError(f"out must be (int64 [>= {kept}, {F}], uint8 [>= {kept}], int64 [>= {kept}]), all contiguous")
+    parse(workspace.data_ptr(), kept, keys.data_ptr(), labels.data_ptr(), line_no.data_ptr(), record.data_ptr(), err, stream)
+    if own or word != -1:
+        _raise_refusal(record, what)
+    return keys[:kept], labels[:kept], line_no[:kept], lines, consumed
 
 
 def ctr_text_chunk(text: torch.Tensor, final: bool, first_line_no: int = 0, n_int: int = NUM_INT_FEATS,
@@ -172,73 +303,116 @@ def ctr_text_chunk(text: torch.Tensor, final: bool, first_line_no: int = 0, n_in
     this chunk's carriage returns (then the parse still runs and the merged word is raised), while a refusal of this
     chunk's parse alone stays in the record for the next chunk's read-back or the caller's last `_raise_refusal`."""
     dev = _lib.require_gpu(text)
-    if text.dtype != torch.uint8 or text.dim() != 1 or not text.is_contiguous():
-        raise TypeError("text must be a contiguous uint8 vector")
-    F, nbytes = n_int + n_cat, text.numel()
+    nbytes = text.numel()
     lib = _lib.load()
     thresholds = _thresholds_on(dev)
-    own = record is None
-    if own:
-        record = _new_record(dev)
     need = int(lib.mi_ctr_text_workspace_bytes(nbytes, n_int, n_cat))
     if need == 0:
         raise ValueError(f"a chunk of {nbytes} bytes with {n_int} + {n_cat} columns is outside what the reader supports")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
-    err, stream = _lib.err_word(dev).data_ptr(), _lib.stream_ptr(dev)
-    _lib.check(lib.mi_ctr_text_index(text.data_ptr(), nbytes, int(bool(final)), n_int, n_cat, int(first_line_no),
-                                     workspace.data_ptr(), record.data_ptr(), record.data_ptr() + 24, err, stream),
-               "mi_ctr_text_index")
-    lines, kept, consumed, word = record.tolist()
-    if out is None:
-        out = (torch.zeros((kept, F), dtype=torch.int64, device=dev), torch.zeros(kept, dtype=torch.uint8, device=dev),
-               torch.zeros(kept, dtype=torch.int64, device=dev))
-    keys, labels, line_no = out
-    _lib.require_gpu(text, keys, labels, line_no)
-    for t, dtype, tail in ((keys, torch.int64, (F,)), (labels, torch.uint8, ()), (line_no, torch.int64, ())):
-        if t.dtype != dtype or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.shape[0] < kept \
-                or not t.is_contiguous():
-            raise ValueError(f"out must be (int64 [>= {kept}, {F}], uint8 [>= {kept}], int64 [>= {kept}]), all contiguous")
-    _lib.check(lib.mi_ctr_text_parse(text.data_ptr(), nbytes, n_int, n_cat, workspace.data_ptr(), kept, int(first_line_no),
-                                     thresholds.data_ptr(), thresholds.numel(), keys.data_ptr(), labels.data_ptr(),
-                                     line_no.data_ptr(), record.data_ptr() + 24, err, stream), "mi_ctr_text_parse")
-    if own or word != -1:
-        _raise_refusal(record)
-    return keys[:kept], labels[:kept], line_no[:kept], lines, consumed
+
+    def index(ws, rec, err, stream):
+        _lib.check(lib.mi_ctr_text_index(text.data_ptr(), nbytes, int(bool(final)), n_int, n_cat, int(first_line_no), ws, rec,
+                                         rec + 24, err, stream), "mi_ctr_text_index")
+
+    def parse(ws, kept, keys, labels, line_no, rec, err, stream):
+        _lib.check(lib.mi_ctr_text_parse(text.data_ptr(), nbytes, n_int, n_cat, ws, kept, int(first_line_no),
+                                         thresholds.data_ptr(), thresholds.numel(), keys, labels, line_no, rec + 24, err,
+                                         stream), "mi_ctr_text_parse")
+
+    return _run_chunk(text, final, n_int + n_cat, need, index, parse, _CRITEO_REFUSAL, out, workspace, record)
 
 
-def parse_criteo_text(source, device="cuda", chunk_bytes: int = 1 << 28, n_int: int = NUM_INT_FEATS,
-                      n_cat: int = NUM_FEATS - NUM_INT_FEATS) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """`read_criteo_text` on the device: (keys int64 [n, n_int + n_cat], labels uint8 [n], line_no int64 [n]), all on
-    `device`, equal element for element to the host reader's on every file both accept.  The device enforces the grammar
-    of include/mi355x_recsys.h strictly and raises ValueError, naming the lowest offending line and column, where
-    `read_criteo_text` would be lenient; it never returns keys that differ from the host's.
+# ---- delimited text by a column spec (mi_ctr_table_*; include/mi355x_recsys.h spells the kinds out) ----------------------
+COL_SKIP, COL_LABEL01, COL_LABEL_COUNT, COL_TOKEN8, COL_DEC64, COL_TIME = range(6)
+_KEY_KINDS = (COL_TOKEN8, COL_DEC64, COL_TIME)
 
-    source: a path, a bytes-like object, or a uint8 tensor on the host or the device.  Host sources are read in chunks of
-    at most `chunk_bytes`, each cut after its last newline (host memory stays O(chunk_bytes), no Python object per line);
-    a device tensor is walked in place.  The result does not depend on `chunk_bytes`; a line longer than it is a
-    ValueError.  The only read-back per chunk is the record {lines, kept, consumed, refusal}, plus one word at the end;
-    the record belongs to the call, so concurrent calls share nothing but the read-only threshold table."""
+
+class TableFormat:
+    """A delimited text format: the separator, whether the file starts with a header line, one kind per file column (the
+    key kinds take the output columns 0, 1, ... in file order), whether the TIME column also gives hour / weekday /
+    weekend keys, and the host reader a refusal's message points at."""
+
+    def __init__(self, sep: str, header: bool, kinds, derive_time: bool = False, host_reader: str = "the host reader"):
+        self.sep, self.header, self.kinds, self.host_reader = ord(sep), bool(header), tuple(int(k) for k in kinds), host_reader
+        self.derive_time = bool(derive_time) and COL_TIME in self.kinds
+        self.n_cols = len(self.kinds)
+        self.F = sum(k in _KEY_KINDS for k in self.kinds)
+        self.F_out = self.F + (3 if self.derive_time else 0)
+        spec, at = [], 0
+        for k in self.kinds:
+            spec.append(k | (at << 8) if k in _KEY_KINDS else k)
+            at += k in _KEY_KINDS
+        self.spec = np.array(spec, dtype=np.int32)
+        self._on = {}
+        self.refusal = (f"not in the strict grammar of the device reader (a label, token, number or timestamp its column's "
+                        f"kind does not take, or a carriage return); {host_reader} is the lenient reader")
+
+    def spec_on(self, device: torch.device) -> torch.Tensor:
+        i = device.index if device.index is not None else torch.cuda.current_device()
+        if i not in self._on:
+            self._on[i] = torch.from_numpy(self.spec.copy()).to(torch.device("cuda", i))
+        return self._on[i]
+
+
+
+def avazu_format(preprocess_timestamp: bool = False) -> TableFormat:
+    """id (never read), click, hour as yymmddHH, 21 more feature strings; a header line; comma-separated."""
+    return TableFormat(",", True, [COL_SKIP, COL_LABEL01, COL_TIME] + [COL_TOKEN8] * (NUM_AVAZU_FEATS - 1),
+                       preprocess_timestamp, "read_avazu_text")
+
+
+def kdd_format() -> TableFormat:
+    """click count, then 11 decimal ids (some above 2^63); no header; tab-separated."""
+    return TableFormat("\t", False, [COL_LABEL_COUNT] + [COL_DEC64] * NUM_KDD_FEATS, False, "read_kdd_text")
+
+
+def ctr_table_chunk(text: torch.Tensor, final: bool, fmt: TableFormat, first_line_no: int = 0, n_header: int = 0, out=None,
+                    workspace: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None):
+    """`ctr_text_chunk` for a TableFormat, through mi_ctr_table_index and mi_ctr_table_parse: (keys int64 [kept, F_out],
+    labels uint8 [kept], line_no int64 [kept], lines, consumed).  n_header: 1 when the chunk starts with the file's header
+    line, which is neither kept nor counted in `lines`."""
+    dev = _lib.require_gpu(text)
+    nbytes = text.numel()
+    lib = _lib.load()
+    spec = fmt.spec_on(dev)
+    need = int(lib.mi_ctr_table_workspace_bytes(nbytes, fmt.n_cols))
+    if need == 0:
+        raise ValueError(f"a chunk of {nbytes} bytes with {fmt.n_cols} columns is outside what the reader supports")
+
+    def index(ws, rec, err, stream):
+        _lib.check(lib.mi_ctr_table_index(text.data_ptr(), nbytes, int(bool(final)), fmt.sep, fmt.n_cols, int(n_header),
+                                          int(first_line_no), ws, rec, rec + 24, err, stream), "mi_ctr_table_index")
+
+    def parse(ws, kept, keys, labels, line_no, rec, err, stream):
+        _lib.check(lib.mi_ctr_table_parse(text.data_ptr(), nbytes, fmt.sep, fmt.n_cols, spec.data_ptr(), int(fmt.derive_time),
+                                          ws, kept, int(first_line_no), keys, labels, line_no, rec + 24, err, stream),
+                   "mi_ctr_table_parse")
+
+    return _run_chunk(text, final, fmt.F_out, need, index, parse, fmt.refusal, out, workspace, record)
+
+
+def _parse_chunks(source, device, chunk_bytes: int, F: int, need, chunk, what: str):
+    """The chunk loop every device reader shares.  need(nbytes) -> workspace bytes; chunk(text, final, first_line_no,
+    first, workspace, record) -> what `_run_chunk` returns (`first`: the chunk starts the file).  Returns (keys, labels,
+    line_no, lines of the file)."""
     device = torch.device(device)
     if chunk_bytes < 1 or chunk_bytes > 2 ** 31 - 1:
         raise ValueError("chunk_bytes must lie in [1, 2^31 - 1]")
-    if n_int < 0 or n_cat < 0:
-        raise ValueError("n_int and n_cat must not be negative")
-    F = n_int + n_cat
-    parts, state = [], {"line": 0, "ws": None, "record": None}
+    parts, state = [], {"line": 0, "ws": None, "record": None, "first": True}
 
     def one(text: torch.Tensor, final: bool) -> int:
-        lib = _lib.load()
-        need = int(lib.mi_ctr_text_workspace_bytes(text.numel(), n_int, n_cat))
-        if state["ws"] is None or state["ws"].numel() < need:
+        size = need(text.numel())
+        if state["ws"] is None or state["ws"].numel() < size:
             state["ws"] = None                                       # (released before the larger one is taken)
-            state["ws"] = torch.zeros(need, dtype=torch.uint8, device=text.device)
+            state["ws"] = torch.zeros(size, dtype=torch.uint8, device=text.device)
         if state["record"] is None:
             state["record"] = _new_record(text.device)
-        keys, labels, line_no, lines, consumed = ctr_text_chunk(text, final, state["line"], n_int, n_cat,
-                                                                workspace=state["ws"], record=state["record"])
+        keys, labels, line_no, lines, consumed = chunk(text, final, state["line"], state["first"], state["ws"],
+                                                       state["record"])
         parts.append((keys, labels, line_no))
         state["line"] += lines
+        if consumed:
+            state["first"] = False
         return consumed
 
     if isinstance(source, torch.Tensor) and source.is_cuda:
@@ -265,17 +439,78 @@ def parse_criteo_text(source, device="cuda", chunk_bytes: int = 1 << 28, n_int: 
             f = _ViewReader(source)
             total = len(f.view)
         with f:
-            for chunk, final in _cut_chunks(f.readinto, chunk_bytes, total):
-                one(torch.frombuffer(chunk, dtype=torch.uint8).to(device), final)
+            for chunk_view, final in _cut_chunks(f.readinto, chunk_bytes, total):
+                one(torch.frombuffer(chunk_view, dtype=torch.uint8).to(device), final)
     if parts:
-        _raise_refusal(state["record"])
+        _raise_refusal(state["record"], what)
     if not parts:
         keys = torch.zeros((0, F), dtype=torch.int64, device=device)
         _lib.require_gpu(keys)
-        return keys, torch.zeros(0, dtype=torch.uint8, device=device), torch.zeros(0, dtype=torch.int64, device=device)
+        return (keys, torch.zeros(0, dtype=torch.uint8, device=device), torch.zeros(0, dtype=torch.int64, device=device),
+                state["line"])
     if len(parts) == 1:
-        return parts[0]
-    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+        return parts[0] + (state["line"],)
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3)) + (state["line"],)
+
+
+def parse_criteo_text(source, device="cuda", chunk_bytes: int = 1 << 28, n_int: int = NUM_INT_FEATS,
+                      n_cat: int = NUM_FEATS - NUM_INT_FEATS) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`read_criteo_text` on the device: (keys int64 [n, n_int + n_cat], labels uint8 [n], line_no int64 [n]), all on
+    `device`, equal element for element to the host reader's on every file both accept.  The device enforces the grammar
+    of include/mi355x_recsys.h strictly and raises ValueError, naming the lowest offending line and column, where
+    `read_criteo_text` would be lenient; it never returns keys that differ from the host's.
+
+    source: a path, a bytes-like object, or a uint8 tensor on the host or the device.  Host sources are read in chunks of
+    at most `chunk_bytes`, each cut after its last newline (host memory stays O(chunk_bytes), no Python object per line);
+    a device tensor is walked in place.  The result does not depend on `chunk_bytes`; a line longer than it is a
+    ValueError.  The only read-back per chunk is the record {lines, kept, consumed, refusal}, plus one word at the end;
+    the record belongs to the call, so concurrent calls share nothing but the read-only threshold table."""
+    if n_int < 0 or n_cat < 0:
+        raise ValueError("n_int and n_cat must not be negative")
+
+    def need(nbytes):
+        return int(_lib.load().mi_ctr_text_workspace_bytes(nbytes, n_int, n_cat))
+
+    def chunk(text, final, line, first, ws, record):
+        return ctr_text_chunk(text, final, line, n_int, n_cat, workspace=ws, record=record)
+
+    return _parse_chunks(source, device, chunk_bytes, n_int + n_cat, need, chunk, _CRITEO_REFUSAL)[:3]
+
+
+def parse_table_text(source, fmt: TableFormat, device="cuda", chunk_bytes: int = 1 << 28):
+    """A TableFormat's text through the chunk loop of `parse_criteo_text` (the same sources, chunking and refusal rule):
+    (keys int64 [n, F_out], labels uint8 [n], line_no int64 [n], the file's number of lines after the header)."""
+
+    def need(nbytes):
+        return int(_lib.load().mi_ctr_table_workspace_bytes(nbytes, fmt.n_cols))
+
+    def chunk(text, final, line, first, ws, record):
+        return ctr_table_chunk(text, final, fmt, line, int(fmt.header and first), workspace=ws, record=record)
+
+    return _parse_chunks(source, device, chunk_bytes, fmt.F_out, need, chunk, fmt.refusal)
+
+
+def parse_avazu_text(source, device="cuda", chunk_bytes: int = 1 << 28,
+                     preprocess_timestamp: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`read_avazu_text` on the device: (keys int64 [n, 22 or 25], labels uint8 [n], line_no int64 [n]) of Avazu's
+    comma-separated text, equal element for element to the host reader's on every file both accept; sources, chunking and
+    refusals as `parse_criteo_text`.  The header is dropped, a line without 24 values is skipped yet numbered, the `id`
+    column is never read.  With `preprocess_timestamp` the hour column must be 8 digits of a real date and hour."""
+    return parse_table_text(source, avazu_format(preprocess_timestamp), device, chunk_bytes)[:3]
+
+
+def parse_kdd_text(source, device="cuda", chunk_bytes: int = 1 << 28) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`read_kdd_text` on the device: (keys int64 [n, 11], labels uint8 [n], line_no int64 [n]) of KDD 2012 track 2's
+    tab-separated text; sources, chunking and refusals as `parse_criteo_text`.  A line without 12 values is a ValueError
+    naming it (the reference asserts the count)."""
+    keys, labels, line_no, lines = parse_table_text(source, kdd_format(), device, chunk_bytes)
+    n = line_no.numel()
+    if n != lines:                                          # the first position whose line number is not its own index
+        own = torch.arange(n, dtype=torch.int64, device=line_no.device)
+        first = int(torch.where(line_no != own, own, n).min().item()) if n else 0
+        raise ValueError(f"line {first} (0-based) does not hold {NUM_KDD_FEATS + 1} tab-separated values; "
+                         "read_kdd_text refuses it too")
+    return keys, labels, line_no
 
 
 class _ViewReader:
@@ -447,19 +682,52 @@ class DeviceCTRDataset:
         (the reference's `torch.load`-able dict, or the dict itself) the dataset is the view over `dataset_name`'s line
         numbers, sorted as the reference sorts them.  reader: "host" reads the text with `read_criteo_text`, "device"
         with `parse_criteo_text` (the same keys, strict about the grammar), whose tensors never leave the device."""
-        if reader not in ("host", "device"):
-            raise ValueError(f"reader must be 'host' or 'device'; got {reader!r}")
+        _check_reader(reader)
         if reader == "device":
             keys, labels, line_no = parse_criteo_text(path, device=device)
         else:
             keys, labels, line_no = read_criteo_text(path)
+        return cls._from_keys(keys, labels, line_no, train_test_info, dataset_name, min_threshold, device)
+
+    @classmethod
+    def from_avazu_text(cls, path: str, train_test_info=None, dataset_name: Optional[str] = None, min_threshold: int = 2,
+                        device="cuda", reader: str = "device",
+                        preprocess_timestamp: Optional[bool] = None) -> "DeviceCTRDataset":
+        """`from_criteo_text` for Avazu's file (`parse_avazu_text` / `read_avazu_text`; 22 fields, 25 with the timestamp
+        features).  train_test_info: the reference's `train_test_info.bin` (a path, or the dict) or what
+        `make_train_test_info` returns.  preprocess_timestamp=None takes the info's metadata entry, else False."""
+        _check_reader(reader)
+        info = _load_info(train_test_info)
+        if preprocess_timestamp is None:
+            preprocess_timestamp = bool((info or {}).get("metadata", {}).get("preprocess_timestamp", False))
+        if reader == "device":
+            keys, labels, line_no = parse_avazu_text(path, device=device, preprocess_timestamp=preprocess_timestamp)
+        else:
+            keys, labels, line_no = read_avazu_text(path, preprocess_timestamp)
+        return cls._from_keys(keys, labels, line_no, info, dataset_name, min_threshold, device)
+
+    @classmethod
+    def from_kdd_text(cls, path: str, train_test_info=None, dataset_name: Optional[str] = None, min_threshold: int = 10,
+                      device="cuda", reader: str = "device") -> "DeviceCTRDataset":
+        """`from_criteo_text` for KDD 2012 track 2's file (`parse_kdd_text` / `read_kdd_text`; 11 fields)."""
+        _check_reader(reader)
+        if reader == "device":
+            keys, labels, line_no = parse_kdd_text(path, device=device)
+        else:
+            keys, labels, line_no = read_kdd_text(path)
+        return cls._from_keys(keys, labels, line_no, train_test_info, dataset_name, min_threshold, device)
+
+    @classmethod
+    def _from_keys(cls, keys, labels, line_no, train_test_info, dataset_name, min_threshold, device) -> "DeviceCTRDataset":
+        """The tail every `from_*_text` shares: encode the key matrix, resolve `dataset_name`'s line numbers to record rows
+        (on the device when `line_no` is there)."""
         records, field_dims = encode_ctr_columns(keys, labels, min_threshold, device)
         index = None
         if train_test_info is not None:
-            info = train_test_info if isinstance(train_test_info, dict) else torch.load(train_test_info, weights_only=False)
+            info = _load_info(train_test_info)
             lines = np.sort(np.asarray(list(info[dataset_name]), dtype=np.int64))
             missing = f"{dataset_name!r} names a line the file does not hold (or one that was skipped)"
-            if reader == "device":
+            if isinstance(line_no, torch.Tensor):
                 wanted = torch.from_numpy(lines).to(line_no.device)
                 index = torch.searchsorted(line_no, wanted)
                 if lines.size and (line_no.numel() == 0 or not torch.equal(
@@ -471,6 +739,18 @@ class DeviceCTRDataset:
                     raise ValueError(missing)
                 index = torch.from_numpy(index)
         return cls(records, field_dims, index=index, device=device)
+
+
+def _check_reader(reader: str) -> None:
+    if reader not in ("host", "device"):
+        raise ValueError(f"reader must be 'host' or 'device'; got {reader!r}")
+
+
+def _load_info(train_test_info):
+    """The reference's `torch.load`-able split file, or the dict itself (None stays None)."""
+    if train_test_info is None or isinstance(train_test_info, dict):
+        return train_test_info
+    return torch.load(train_test_info, weights_only=False)
 
 
 class DeviceCTRLoader:
