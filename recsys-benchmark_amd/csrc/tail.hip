@@ -1669,6 +1669,8 @@ static int dgrad_launch(const float *DY, const float *Zl, int32_t ld, const floa
   if (p_mu && (!pZ || !p_sc || !p_be)) return MI_ERR_INVALID_ARG;
   if (!vec_ok(DY, ld) || !vec_ok(W, ldw) || !vec_ok(OUT, ldo) || N % 4 || K % 4 || (pZ && !vec_ok(pZ, pld)))
     return MI_ERR_UNSUPPORTED;
+  // W is walked along its rows through one buffer descriptor per column tile: a slice's byte offset is a 32-bit scalar
+  if ((int64_t)N * ldw >= (1ll << 30)) return MI_ERR_UNSUPPORTED;
   a.dz = DzDesc{DY, Zl, ld, mu, al, bz, de};
   a.W = W; a.ldw = ldw;
   if (p_mu && p_p > 0.f && (!p_keep || pld % 8)) return MI_ERR_INVALID_ARG;

@@ -95,21 +95,53 @@ struct NoConsts {};
 // paid by the matrix pipe of its SIMD (measured: +64 VALU per producer phase = +12 us per product; SQ_INSTS_VALU 3.06 M
 // against 0.75 M MFMAs in the fused forward product, profiles/r03_tail_sq_counters.csv).  A producer phase of round 2
 // spent ~94 vector instructions on addresses, clamps and selects per slice.  Lean form: an operand element's address is
-//   UNIFORM base (pointers shifted to the tile's first row and the slice's first reduction index: scalar registers, SALU)
+//   a buffer descriptor per matrix, built once per workgroup (kernel arguments and blockIdx only: four scalar registers),
+//     based at the workgroup's tile and as long as the tile's true extent, (rows - 1) * ld + cols floats
+//   + the slice's byte offset inside the tile: one scalar register, advanced on the scalar unit
 //   + a per-thread 32-bit byte offset that never changes (row inside the tile x pitch + column inside the slice),
-// so a load is `global_load_dwordx4 v, v_off, s[base]` with no vector arithmetic at all; clamps of rows beyond the tile
-// happen once, in the offsets; the zeroing of reduction indices beyond the end exists only in the LAST slice, which takes
-// the general path (uniform branch).  Each loader L provides:
-//   UBase ubase(row, col)            the uniform part for a tile whose element (0, 0) is (row, col); with dropout
-//                                    (row * ld + col) % 8 == 0 is required (callers pass col = 0 or a multiple of 32)
+// so a load is `buffer_load_dwordx4 v, v_off, s[rsrc], s_soff offen` with no vector arithmetic at all (a uniform pointer
+// plus a 32-bit lane offset instead compiles to a v_lshl_add_u64 per access: profiles/tail_addr_isa.txt); clamps of rows
+// beyond the tile happen once, in the offsets; the zeroing of reduction indices beyond the end exists only in the LAST
+// slice, which takes the general path (uniform branch).  The clamps keep every access inside the descriptor's range; the
+// range check behind them only means that a wrong offset would read zeros / store nothing, never touch foreign memory.
+// Each loader L provides:
+//   Win   window(row, col, rows, cols)  the descriptors of a tile whose element (0, 0) is (row, col) and which spans
+//                                    rows x cols elements; with dropout (row * ld + col) % 8 == 0 is required
+//   UBase ubase(win, drow, dcol)     the uniform part for the slice whose element (0, 0) is (drow, dcol) of the tile; with
+//                                    dropout (drow * ld + dcol) % 8 == 0 is required (callers pass multiples of 32)
 //   TC    tconst(r, c)               the thread-constant part of element (r, c) relative to it
 //   Raw   fetch_u(ub, tc)            issue the loads
 //   Consts consts_u(ub, c)           per-column constants of column c relative to ub (KC operands: c = the thread's column
 //                                    inside the slice)
 //   float4 finish_u(raw, k, ub, tc)  form the operand value
-__device__ __forceinline__ float4 vld4u(const float *base, uint32_t boff) {
-  return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + boff);
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
+// raw buffer, 32-bit records, range-checked (DATA_FORMAT = 32 in word 3); `bytes` from `base` on, 0 with a null base
+__device__ __forceinline__ rsrc_t buf_window(const void *base, int64_t bytes) {
+  const int64_t n = !base || bytes < 0 ? 0 : bytes > 0xFFFFFFFFll ? 0xFFFFFFFFll : bytes;
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(uint32_t)n, 0x00020000);
 }
+// elements from (0, 0) to the end of the last row of a rows x cols tile with row pitch ld
+__device__ __forceinline__ int64_t tile_elems(int rows, int cols, int ld) {
+  return rows > 0 && cols > 0 ? (int64_t)(rows - 1) * ld + cols : 0;
+}
+__device__ __forceinline__ float4 bld4(rsrc_t r, uint32_t voff, uint32_t soff) {
+  const uintx4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+  return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+}
+__device__ __forceinline__ void bst4(rsrc_t r, uint32_t voff, uint32_t soff, float4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(uintx4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)}, r,
+                                         voff, soff, 0);
+}
+// bit j of x as a mask, 0 or ~0 (v_bfe_i32: a one-bit field, sign-extended).  As an instruction, because hipcc turns the
+// C++ form (shift left, arithmetic shift right) and the and that uses it back into and / cmp / cndmask.
+template <int J>
+__device__ __forceinline__ uint32_t bit_mask(uint32_t x) {
+  uint32_t m;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(x), "n"(J));
+  return m;
+}
+__device__ __forceinline__ float and_bits(float v, uint32_t m) { return __uint_as_float(__float_as_uint(v) & m); }
 // Plain: the matrix itself (weights, the embedding block, a finished gradient).
 struct LoadPlain {
   static constexpr bool kLateConsts = false;
@@ -118,11 +150,15 @@ struct LoadPlain {
   int ld;
   struct Raw { float4 a; };
   typedef NoConsts Consts;
-  struct UBase { const float *p; };
+  struct Win { rsrc_t p; };
+  struct UBase { rsrc_t p; uint32_t soff; };
   struct TC { uint32_t off; };
-  __device__ __forceinline__ UBase ubase(int row, int col) const { return UBase{P + (int64_t)row * ld + col}; }
+  __device__ __forceinline__ Win window(int row, int col, int rows, int cols) const {
+    return Win{buf_window(P + (int64_t)row * ld + col, tile_elems(rows, cols, ld) * 4)};
+  }
+  __device__ __forceinline__ UBase ubase(const Win &w, int drow, int dcol) const { return UBase{w.p, (uint32_t)(drow * ld + dcol) * 4u}; }
   __device__ __forceinline__ TC tconst(int r, int c) const { return TC{(uint32_t)(r * ld + c) * 4u}; }
-  __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const { return Raw{vld4u(u.p, t.off)}; }
+  __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const { return Raw{bld4(u.p, t.off, u.soff)}; }
   __device__ __forceinline__ Consts consts_u(const UBase &, int) const { return Consts{}; }
   __device__ __forceinline__ float4 finish_u(const Raw &r, const Consts &, const UBase &, const TC &) const { return r.a; }
   __device__ __forceinline__ Raw fetch(int m, int c) const { return Raw{vld4(P + (int64_t)m * ld + c)}; }
@@ -143,27 +179,34 @@ struct LoadActT {
   Drop drop;
   struct Raw { float4 z; uint32_t keep; };
   struct Consts { float4 u, s, b; };
-  struct UBase { const float *z; const uint8_t *bits; CP mu, sc, be; };
+  struct Win { rsrc_t z, bits; CP mu, sc, be; };      // the keep bits of the same elements: one byte per 8
+  struct UBase { rsrc_t z, bits; uint32_t soff, ksoff; CP mu, sc, be; };
   struct TC { uint32_t off, koff, nib; };     // byte offset of z; byte offset and nibble shift (0 / 4) of the keep bits
-  __device__ __forceinline__ UBase ubase(int row, int col) const {
-    const int64_t e = (int64_t)row * ld + col;
-    return UBase{Z + e, drop.bits ? drop.bits + (e >> 3) : nullptr, mu + col, sc + col, be + col};
+  __device__ __forceinline__ Win window(int row, int col, int rows, int cols) const {
+    const int64_t e = (int64_t)row * ld + col, n = tile_elems(rows, cols, ld);
+    return Win{buf_window(Z + e, n * 4), buf_window(drop.bits ? drop.bits + (e >> 3) : nullptr, (n + 7) >> 3), mu + col, sc + col, be + col};
+  }
+  __device__ __forceinline__ UBase ubase(const Win &w, int drow, int dcol) const {
+    const uint32_t e = (uint32_t)(drow * ld + dcol);
+    return UBase{w.z, w.bits, e * 4u, e >> 3, w.mu + dcol, w.sc + dcol, w.be + dcol};
   }
   __device__ __forceinline__ TC tconst(int r, int c) const {
     const uint32_t e = (uint32_t)(r * ld + c);
     return TC{e * 4u, e >> 3, (uint32_t)(c & 4)};
   }
   __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const {
-    return Raw{vld4u(u.z, t.off), u.bits ? (uint32_t)u.bits[t.koff] : 0xFFu};
+    return Raw{bld4(u.z, t.off, u.soff), drop.bits ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(u.bits, t.koff, u.ksoff, 0) : 0xFFu};
   }
   __device__ __forceinline__ Consts consts_u(const UBase &u, int c) const { return Consts{vld4(u.mu + c), vld4(u.sc + c), vld4(u.be + c)}; }
+  // the dropout decision as a MASK: keep bit j of the nibble sign-extended to 0 / ~0 and one `and` of the finished value
+  // (0.0f is all zeros: the same bits as selecting 0.f) — two vector instructions per element where and / cmp / cndmask were three
   __device__ __forceinline__ float4 finish_u(const Raw &r, const Consts &k, const UBase &, const TC &t) const {
     const uint32_t nib = r.keep >> t.nib;
     float4 a;
-    a.x = (nib & 1u) ? fmaxf(fmaf(r.z.x - k.u.x, k.s.x, k.b.x), 0.f) * drop.inv_keep : 0.f;
-    a.y = (nib & 2u) ? fmaxf(fmaf(r.z.y - k.u.y, k.s.y, k.b.y), 0.f) * drop.inv_keep : 0.f;
-    a.z = (nib & 4u) ? fmaxf(fmaf(r.z.z - k.u.z, k.s.z, k.b.z), 0.f) * drop.inv_keep : 0.f;
-    a.w = (nib & 8u) ? fmaxf(fmaf(r.z.w - k.u.w, k.s.w, k.b.w), 0.f) * drop.inv_keep : 0.f;
+    a.x = and_bits(fmaxf(fmaf(r.z.x - k.u.x, k.s.x, k.b.x), 0.f) * drop.inv_keep, bit_mask<0>(nib));
+    a.y = and_bits(fmaxf(fmaf(r.z.y - k.u.y, k.s.y, k.b.y), 0.f) * drop.inv_keep, bit_mask<1>(nib));
+    a.z = and_bits(fmaxf(fmaf(r.z.z - k.u.z, k.s.z, k.b.z), 0.f) * drop.inv_keep, bit_mask<2>(nib));
+    a.w = and_bits(fmaxf(fmaf(r.z.w - k.u.w, k.s.w, k.b.w), 0.f) * drop.inv_keep, bit_mask<3>(nib));
     return a;
   }
   __device__ __forceinline__ Raw fetch(int m, int c) const { return Raw{vld4(Z + (int64_t)m * ld + c), drop.fetch(m, c)}; }
@@ -193,17 +236,23 @@ struct LoadDzT {
   CP mu, al, bz, de;
   struct Raw { float4 dy, z; };
   struct Consts { float4 u, a, b, d; };
-  struct UBase { const float *dy, *z; CP mu, al, bz, de; };
+  struct Win { rsrc_t dy, z; CP mu, al, bz, de; };
+  struct UBase { rsrc_t dy, z; uint32_t soff; CP mu, al, bz, de; };
   struct TC { uint32_t off; };
-  __device__ __forceinline__ UBase ubase(int row, int col) const {
-    const int64_t e = (int64_t)row * ld + col;
-    return UBase{DY + e, Z + e, mu + col, al + col, bz + col, de + col};
+  __device__ __forceinline__ Win window(int row, int col, int rows, int cols) const {
+    const int64_t e = (int64_t)row * ld + col, n = tile_elems(rows, cols, ld);
+    return Win{buf_window(DY + e, n * 4), buf_window(Z + e, n * 4), mu + col, al + col, bz + col, de + col};
+  }
+  __device__ __forceinline__ UBase ubase(const Win &w, int drow, int dcol) const {
+    return UBase{w.dy, w.z, (uint32_t)(drow * ld + dcol) * 4u, w.mu + dcol, w.al + dcol, w.bz + dcol, w.de + dcol};
   }
   __device__ __forceinline__ TC tconst(int r, int c) const { return TC{(uint32_t)(r * ld + c) * 4u}; }
-  __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const { return Raw{vld4u(u.dy, t.off), vld4u(u.z, t.off)}; }
+  __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const { return Raw{bld4(u.dy, t.off, u.soff), bld4(u.z, t.off, u.soff)}; }
   __device__ __forceinline__ Consts consts_u(const UBase &u, int c) const {
     return Consts{vld4(u.mu + c), vld4(u.al + c), vld4(u.bz + c), vld4(u.de + c)};
   }
+  // (v_pk_*_f32 stay: hipcc SLP-packs these into 12 packed instructions per phase; the same arithmetic as 24 one-instruction
+  // helpers measured +2 us per step, profiles/tail_addr_ab.txt)
   __device__ __forceinline__ float4 finish_u(const Raw &r, const Consts &k, const UBase &, const TC &) const { return finish(r, k, 0, 0); }
   __device__ __forceinline__ Raw fetch(int m, int c) const {
     return Raw{vld4(DY + (int64_t)m * ld + c), vld4(Z + (int64_t)m * ld + c)};
@@ -224,7 +273,8 @@ typedef LoadDzT<lds_cfp> LoadDzL;
 // Tee: the operand value also goes to memory as it passes (out[m][c], row pitch the loader's own), so that a LATER product
 // on other kernels can read the transformed matrix (the tail's weight gradients take a(z) and dz from here).  One column
 // tile of the grid is given a non-null `out`; rows / reduction indices that were clamped store a duplicate of the same
-// value at its own (valid) address.
+// value at its own (valid) address.  Lean form: the tiles without a destination hold a descriptor of ZERO records — every
+// store through it is out of range and dropped by the range check, so the producers' loop has no branch around the store.
 template <class L>
 struct Tee {
   static constexpr bool kLateConsts = L::kLateConsts;
@@ -234,17 +284,22 @@ struct Tee {
   int ld;
   typedef typename L::Raw Raw;
   typedef typename L::Consts Consts;
-  struct UBase { typename L::UBase in; float *out; };
+  struct Win { typename L::Win in; rsrc_t out; };
+  struct UBase { typename L::UBase in; rsrc_t out; uint32_t soff; };
   struct TC { typename L::TC in; uint32_t off; };
-  __device__ __forceinline__ UBase ubase(int row, int col) const {
-    return UBase{in.ubase(row, col), out ? out + (int64_t)row * ld + col : nullptr};
+  __device__ __forceinline__ Win window(int row, int col, int rows, int cols) const {
+    return Win{in.window(row, col, rows, cols), buf_window(out ? out + (int64_t)row * ld + col : nullptr, tile_elems(rows, cols, ld) * 4)};
+  }
+  __device__ __forceinline__ UBase ubase(const Win &w, int drow, int dcol) const {
+    // (no destination: the scalar offset stays 0 too, so that "out of range" does not hang on how it enters the check)
+    return UBase{in.ubase(w.in, drow, dcol), w.out, out ? (uint32_t)(drow * ld + dcol) * 4u : 0u};
   }
   __device__ __forceinline__ TC tconst(int r, int c) const { return TC{in.tconst(r, c), (uint32_t)(r * ld + c) * 4u}; }
   __device__ __forceinline__ Raw fetch_u(const UBase &u, const TC &t) const { return in.fetch_u(u.in, t.in); }
   __device__ __forceinline__ Consts consts_u(const UBase &u, int c) const { return in.consts_u(u.in, c); }
   __device__ __forceinline__ float4 finish_u(const Raw &r, const Consts &k, const UBase &u, const TC &t) const {
     const float4 v = in.finish_u(r, k, u.in, t.in);
-    if (u.out) *reinterpret_cast<float4 *>(reinterpret_cast<char *>(u.out) + t.off) = v;
+    bst4(u.out, t.off, u.soff, v);
     return v;
   }
   __device__ __forceinline__ Raw fetch(int m, int c) const { return in.fetch(m, c); }
@@ -256,8 +311,8 @@ struct Tee {
   }
 };
 
-template <class L, bool LEAN = L::kLean> struct LeanTypes { struct TC {}; struct UBase {}; };
-template <class L> struct LeanTypes<L, true> { typedef typename L::TC TC; typedef typename L::UBase UBase; };
+template <class L, bool LEAN = L::kLean> struct LeanTypes { struct TC {}; struct Win {}; };
+template <class L> struct LeanTypes<L, true> { typedef typename L::TC TC; typedef typename L::Win Win; };
 
 __device__ __forceinline__ int ptid() { return (int)threadIdx.x - (kThreads - kProd); }
 
@@ -378,8 +433,10 @@ template <int ROWS, class L>
 struct OtMap {
   typename L::Consts k;
   typename LeanTypes<L>::TC tc[4];   // thread-constant address parts of the block's 4 reduction rows (lean loaders)
+  typename LeanTypes<L>::Win win;    // the descriptors of the workgroup's tile (lean loaders; uniform)
   int col;          // first output column (global), clamped
   int ob, rb;       // output block, reduction block; ob < 0: this thread has no block
+  int lofs[2];      // LDS float offsets of the block's rows 0 and 2 (lean form; rows 1 and 3 lie BK floats behind them)
 };
 template <int ROWS, class L>
 struct OtStage {
@@ -450,28 +507,33 @@ struct OtOperand {
     const int o = (bc % OB) << 2;
     m.col = out0 + (o < out_valid ? o : out_valid - 4);
     m.k = ld.consts(m.col);
+    m.win = ld.window(0, out0, red_end, out_valid);      // the tile: every reduction row of the workgroup's columns
 #pragma unroll
-    for (int j = 0; j < 4; ++j) m.tc[j] = ld.tconst(4 * m.rb + j, m.col);      // relative to ubase(red0, 0)
+    for (int j = 0; j < 4; ++j) m.tc[j] = ld.tconst(4 * m.rb + j, m.col - out0);      // relative to ubase(win, red0, 0)
+    // rows 4 ob and 4 ob + 1 share their swizzle ((row >> 1) & 7), rows 4 ob + 2 and + 3 the next one: two positions per
+    // thread, not a constant apart (the swizzle XORs the chunk index), the odd rows BK floats behind them
+    m.lofs[0] = kc_off(4 * (bc % OB), m.rb);
+    m.lofs[1] = kc_off(4 * (bc % OB) + 2, m.rb);
     return m;
   }
   __device__ __forceinline__ void store_block(float *T, const OtMap<ROWS, L> &m, const float4 (&v)[4]) const {
-    const int row = 4 * m.ob;
-    vst4(T + kc_off(row + 0, m.rb), make_float4(v[0].x, v[1].x, v[2].x, v[3].x));
-    vst4(T + kc_off(row + 1, m.rb), make_float4(v[0].y, v[1].y, v[2].y, v[3].y));
-    vst4(T + kc_off(row + 2, m.rb), make_float4(v[0].z, v[1].z, v[2].z, v[3].z));
-    vst4(T + kc_off(row + 3, m.rb), make_float4(v[0].w, v[1].w, v[2].w, v[3].w));
+    float *t0 = T + m.lofs[0], *t1 = T + m.lofs[1];
+    vst4(t0, make_float4(v[0].x, v[1].x, v[2].x, v[3].x));
+    vst4(t0 + BK, make_float4(v[0].y, v[1].y, v[2].y, v[3].y));
+    vst4(t1, make_float4(v[0].z, v[1].z, v[2].z, v[3].z));
+    vst4(t1 + BK, make_float4(v[0].w, v[1].w, v[2].w, v[3].w));
   }
   // full slices (see KcOperand)
   __device__ __forceinline__ OtStage<ROWS, L> fetch(const OtMap<ROWS, L> &m, int red0) const {
     OtStage<ROWS, L> st;
-    const auto ub = ld.ubase(red0, 0);
+    const auto ub = ld.ubase(m.win, red0, 0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) st.raw[j] = ld.fetch_u(ub, m.tc[j]);
     return st;
   }
   __device__ __forceinline__ void finish(float *T, const OtStage<ROWS, L> &st, const OtMap<ROWS, L> &m, int red0) const {
     if (m.ob < 0) return;
-    const auto ub = ld.ubase(red0, 0);
+    const auto ub = ld.ubase(m.win, red0, 0);
     float4 v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = ld.finish_u(st.raw[j], m.k, ub, m.tc[j]);
@@ -480,18 +542,18 @@ struct OtOperand {
   // a slice that may be partial: rows beyond the end re-aimed at the last valid one, their values zeroed
   __device__ __forceinline__ OtStage<ROWS, L> fetch_any(const OtMap<ROWS, L> &m, int red0) const {
     OtStage<ROWS, L> st;
-    const auto ub = ld.ubase(red0, 0);
+    const auto ub = ld.ubase(m.win, red0, 0);
     const int rem = red_end - red0;
-    const typename L::TC last = ld.tconst(rem - 1, m.col);
+    const typename L::TC last = ld.tconst(rem - 1, m.col - out0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) st.raw[j] = ld.fetch_u(ub, 4 * m.rb + j >= rem ? last : m.tc[j]);
     return st;
   }
   __device__ __forceinline__ void finish_any(float *T, const OtStage<ROWS, L> &st, const OtMap<ROWS, L> &m, int red0) const {
     if (m.ob < 0) return;
-    const auto ub = ld.ubase(red0, 0);
+    const auto ub = ld.ubase(m.win, red0, 0);
     const int rem = red_end - red0;
-    const typename L::TC last = ld.tconst(rem - 1, m.col);
+    const typename L::TC last = ld.tconst(rem - 1, m.col - out0);
     float4 v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -526,13 +588,19 @@ template <int ROWS, class L, int NP = kProd>
 struct KcPrep {
   static constexpr int NV = (ROWS * 8 + NP - 1) / NP;
   typename L::TC tc[NV];
-  int lofs[NV];                         // LDS float offset of the chunk, -1: the chunk does not exist
+  typename L::Win win;                  // the descriptors of the workgroup's tile (uniform)
+  int lofs;                             // LDS float offset of the thread's first chunk; chunk i lies i * kChunkStep behind it
+  bool last;                            // the thread's last chunk exists (ROWS * 8 not a multiple of NP: some have one less)
   int cc;                               // first column of the thread's chunk inside a slice
 };
 template <int ROWS, class L, int NP = kProd>
 struct KcOperand {
   static_assert(L::kLean, "KcOperand needs a loader with the lean interface (else KcOperandG)");
   static constexpr int NV = KcPrep<ROWS, L, NP>::NV;
+  // a thread's chunks are NP / 8 rows apart: a multiple of 16 rows leaves the swizzle ((row >> 1) & 7) alone, so they lie a
+  // CONSTANT NP / 8 * BK floats apart and one LDS address serves them all (ds_write_b128 offset:)
+  static_assert((NP / 8) % 16 == 0, "the chunks of a thread must share their swizzle");
+  static constexpr int kChunkStep = (NP / 8) * BK;
   L ld;
   int row0, rows_valid, red_end;
   __device__ __forceinline__ int row_of(int i) const {
@@ -542,12 +610,11 @@ struct KcOperand {
   __device__ __forceinline__ KcPrep<ROWS, L, NP> prep() const {
     KcPrep<ROWS, L, NP> p;
     p.cc = (ptid() & 7) << 2;
+    p.win = ld.window(row0, 0, rows_valid, red_end);
+    p.lofs = kc_off(ptid() >> 3, ptid() & 7);
+    p.last = (ptid() >> 3) + (NV - 1) * (NP / 8) < ROWS;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int trow = (ptid() >> 3) + i * (NP / 8);
-      p.lofs[i] = trow < ROWS ? kc_off(trow, ptid() & 7) : -1;
-      p.tc[i] = ld.tconst(row_of(i), p.cc);
-    }
+    for (int i = 0; i < NV; ++i) p.tc[i] = ld.tconst(row_of(i), p.cc);
     return p;
   }
   // fetch / finish: a FULL slice (red0 + BK <= red_end) — no clamps, no selects, no address arithmetic.
@@ -558,23 +625,23 @@ struct KcOperand {
   // around them made hipcc join the register stages with s_waitcnt vmcnt(0).
   __device__ __forceinline__ KcStage<ROWS, L, NP> fetch(const KcPrep<ROWS, L, NP> &p, int red0) const {
     KcStage<ROWS, L, NP> st;
-    const auto ub = ld.ubase(row0, red0);
+    const auto ub = ld.ubase(p.win, 0, red0);
     if constexpr (!L::kLateConsts) st.k = ld.consts_u(ub, p.cc);
 #pragma unroll
     for (int i = 0; i < NV; ++i) st.raw[i] = ld.fetch_u(ub, p.tc[i]);
     return st;
   }
   __device__ __forceinline__ void finish(float *T, const KcStage<ROWS, L, NP> &st, const KcPrep<ROWS, L, NP> &p, int red0) const {
-    const auto ub = ld.ubase(row0, red0);
+    const auto ub = ld.ubase(p.win, 0, red0);
     typename L::Consts k = st.k;
     if constexpr (L::kLateConsts) k = ld.consts_u(ub, p.cc);
 #pragma unroll
     for (int i = 0; i < NV; ++i)
-      if ((ROWS * 8) % NP == 0 || i + 1 < NV || p.lofs[i] >= 0) vst4(T + p.lofs[i], ld.finish_u(st.raw[i], k, ub, p.tc[i]));
+      if ((ROWS * 8) % NP == 0 || i + 1 < NV || p.last) vst4(T + p.lofs + i * kChunkStep, ld.finish_u(st.raw[i], k, ub, p.tc[i]));
   }
   __device__ __forceinline__ KcStage<ROWS, L, NP> fetch_any(const KcPrep<ROWS, L, NP> &p, int red0) const {
     KcStage<ROWS, L, NP> st;
-    const auto ub = ld.ubase(row0, red0);
+    const auto ub = ld.ubase(p.win, 0, red0);
     const int rem = red_end - red0;
     const bool dead = p.cc >= rem;
     if constexpr (!L::kLateConsts) st.k = ld.consts_u(ub, dead ? rem - 4 : p.cc);
@@ -586,18 +653,18 @@ struct KcOperand {
     return st;
   }
   __device__ __forceinline__ void finish_any(float *T, const KcStage<ROWS, L, NP> &st, const KcPrep<ROWS, L, NP> &p, int red0) const {
-    const auto ub = ld.ubase(row0, red0);
+    const auto ub = ld.ubase(p.win, 0, red0);
     const int rem = red_end - red0;
     const bool dead = p.cc >= rem;
     typename L::Consts k = st.k;
     if constexpr (L::kLateConsts) k = ld.consts_u(ub, dead ? rem - 4 : p.cc);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      if ((ROWS * 8) % NP == 0 || i + 1 < NV || p.lofs[i] >= 0) {
+      if ((ROWS * 8) % NP == 0 || i + 1 < NV || p.last) {
         const typename L::TC re = ld.tconst(row_of(i), rem - 4);
         float4 v = ld.finish_u(st.raw[i], k, ub, dead ? re : p.tc[i]);      // (a Tee stores the re-aimed value at its own address)
         if (dead) v = zero4();
-        vst4(T + p.lofs[i], v);
+        vst4(T + p.lofs + i * kChunkStep, v);
       }
     }
   }
