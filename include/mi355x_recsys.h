@@ -1041,6 +1041,45 @@ MI_API int mi_adam_dense_multi(float *const *params, const float *const *grads, 
 MI_API int mi_scatter_axpy_rows(const int64_t *idx, const float *g, float alpha, float *W,
                                 int64_t n, int32_t D, int64_t N, void *stream);
 
+/* ---- Adagrad and exact row-wise Adagrad on row-form gradients; dense Adagrad ----------------------------------------
+ * The sparse steps run on the sorted-segment walker of mi_sparse_adam_sorted_ld and take its leading arguments:
+ *   rows_sorted int64[n] ascending, perm int64[n] (sorted position -> entry of vals fp32[n,D]), W with row stride ldw >= D,
+ *   acc fp32[n,D] scratch (contents irrelevant before and after), N rows; ids outside [0, N) are skipped.
+ * G below is a row's COALESCED gradient: all its duplicates summed first, in the walker's fixed order (inside a pass of
+ * 64 / LPR sorted positions a segmented suffix sum by shuffles; the pieces of a run that spans passes are added by a
+ * second kernel, lane group r taking pieces r, r + RS, .. in that order and the groups joined by an xor tree).  The rule
+ * is applied to that total only, once per row — never to a piece — so these are the EXACT forms, (sum_i g_i)^2.
+ * No atomics anywhere: a rerun from the same state gives the same bits.
+ *
+ * mi_sparse_adagrad_sorted_ld: state_sum fp32[N,D] contiguous.  For every row that occurs, every d:
+ *     s = state_sum[row,d] + G_d*G_d;  state_sum[row,d] = s;  W[row,d] -= clr * (G_d / (sqrtf(s) + eps))
+ *   i.e. torch.optim.Adagrad on a sparse gradient (coalesce, touched rows only), clr = lr / (1 + (t-1)*lr_decay) formed
+ *   by the host.
+ * mi_rowwise_adagrad_sorted_ld: row_sum fp32[N], one accumulator per table row.  For every row that occurs:
+ *     s = row_sum[row] + (sum_d G_d*G_d) / D;  row_sum[row] = s;  W[row,d] -= clr * (G_d / (sqrtf(s) + eps))  for every d
+ *   sum_d runs in a fixed order: a lane adds the squares of its own VW consecutive elements in index order (VW = 4 for
+ *   the float4 widths, 1 for D = 1 and 2), then the LPR = D / VW lanes of the row are joined by an xor tree over lane
+ *   masks 1, 2, .. LPR/2.  In the any-D kernel lane l adds d = l, l + 64, .. in that order and the 64 lanes are joined by
+ *   an xor tree over masks 32, 16, .. 1.  One lane of the group stores row_sum.
+ * Width dispatch (both): D = 1 and D = 2 scalar forms; D/4 a power of two up to 64 the float4 forms when vals, W, acc
+ *   (and state_sum) are 16-byte aligned — ldw % 4 != 0 at such a width is MI_ERR_UNSUPPORTED; anything else the any-D
+ *   kernel.  ldw < D, negative sizes or a null pointer with n > 0: MI_ERR_INVALID_ARG; n == 0 returns MI_OK and writes
+ *   nothing.
+ */
+MI_API int mi_sparse_adagrad_sorted_ld(const int64_t *rows_sorted, const int64_t *perm, const float *vals, float *W,
+                                       int64_t ldw, float *state_sum, float *acc, int64_t n, int32_t D, int64_t N,
+                                       float clr, float eps, void *stream);
+MI_API int mi_rowwise_adagrad_sorted_ld(const int64_t *rows_sorted, const int64_t *perm, const float *vals, float *W,
+                                        int64_t ldw, float *row_sum, float *acc, int64_t n, int32_t D, int64_t N,
+                                        float clr, float eps, void *stream);
+/* mi_adagrad_dense_multi: torch.optim.Adagrad (L2 weight decay, lr_decay = 0) over `count` dense fp32 tensors, 24 per
+ *   launch; the three pointer arrays and numels live in HOST memory:
+ *     g += wd*p;  s += g*g;  p -= lr * (g / (sqrtf(s) + eps)).
+ *   No step count enters the rule, so there is no counter and no ticket.  Entries with numels[i] == 0 are skipped. */
+MI_API int mi_adagrad_dense_multi(float *const *params, const float *const *grads, float *const *state_sums,
+                                  const int64_t *numels, int32_t count, float lr, float eps, float weight_decay,
+                                  void *stream);
+
 /* ---- §8f rank 3: the LightGCN step either side of the propagation -------------------------------
  * mi_bpr_fwd/bwd: src/losses.py:6-22 on rows picked from the propagated tables
  *   (torch.index_select x3, src/trainer/lightgcn.py:395-399): x_b = u_b.(p_b - n_b) with

@@ -5,7 +5,9 @@ SURVEY.md §8f rank 1.  `SparseAdam` has torch.optim.SparseAdam's constructor, s
 lookup kernels emit directly: one torch.sort of the row ids (no host sync) + ONE fused HIP kernel
 (mi_sparse_adam_sorted) instead of coalesce + ~10 sparse tensor ops.  `SparseSGD` is
 `p[rows] -= lr * g` as float-atomic adds (linear, so duplicates need no coalescing).
-`get_optimizers(model, config)` mirrors src/models/deepfm.py:155-219.
+`SparseAdagrad` (torch.optim.Adagrad's sparse rule) and `RowwiseAdagrad` (one accumulator per table row, the exact
+form) are two more rules on SparseAdam's sorted-segment kernels; `Adagrad` is the dense rule in one launch per 24 tensors.
+`get_optimizers(model, config)` mirrors src/models/deepfm.py:155-219, plus `optimizer: adagrad | rowwise_adagrad`.
 """
 import ctypes
 import math
@@ -32,6 +34,26 @@ def sort_rows(rows: torch.Tensor, N: int):
     _lib.require_gpu(rows)
     found = _kernels.sort_field_rows(rows, N)
     return found if found is not None else tuple(torch.sort(rows))
+
+
+def _row_step_operands(opt, p, rows, vals, sorted_ids, dev):
+    """What every sorted-row step (mi_*_sorted_ld) takes besides its own state: (rows_sorted, perm, acc, ldw, N, D).
+    `sorted_ids` is the step's cache — parameters that receive gradients over the same id tensor (both DeepFM tables) share
+    one sort; `acc` is the kernels' scratch, kept in opt._workspace (not optimizer state); `ldw` is the row stride of a
+    packed-table view (DeepFM.pack_tables())."""
+    N = p.shape[0]
+    D = p.numel() // N
+    key = (rows.data_ptr(), rows.numel(), N)
+    if key not in sorted_ids:
+        sorted_ids[key] = sort_rows(rows, N) if rows.numel() else (rows, rows)
+    rows_sorted, perm = sorted_ids[key]
+    acc = opt._workspace.get(p)           # scratch, not optimizer state
+    if acc is None or acc.numel() < vals.numel():
+        acc = opt._workspace[p] = torch.empty(vals.numel(), dtype=torch.float32, device=dev)
+    ldw = D if p.is_contiguous() else _kernels._row_strided(p.view(N, D), align=4 if D >= 4 else 1)[1]
+    if not p.is_contiguous() and (p.dim() != 2 or p.stride(0) != ldw):
+        raise RuntimeError(f"{type(opt).__name__}: a non-contiguous parameter must be a row-strided 2-D view (packed table)")
+    return rows_sorted, perm, acc, ldw, N, D
 
 
 class SparseAdam(torch.optim.Optimizer):
@@ -87,18 +109,7 @@ class SparseAdam(torch.optim.Optimizer):
                     state["step"] += 1
                     t = state["step"]
                     step_size, step_size_dev = group["lr"] * math.sqrt(1 - beta2 ** t) / (1 - beta1 ** t), None
-                N = p.shape[0]
-                D = p.numel() // N
-                key = (rows.data_ptr(), rows.numel(), N)
-                if key not in sorted_ids:
-                    sorted_ids[key] = sort_rows(rows, N) if rows.numel() else (rows, rows)
-                rows_sorted, perm = sorted_ids[key]
-                acc = self._workspace.get(p)           # scratch, not optimizer state
-                if acc is None or acc.numel() < vals.numel():
-                    acc = self._workspace[p] = torch.empty(vals.numel(), dtype=torch.float32, device=dev)
-                ldw = D if p.is_contiguous() else _kernels._row_strided(p.view(N, D), align=4 if D >= 4 else 1)[1]
-                if not p.is_contiguous() and (p.dim() != 2 or p.stride(0) != ldw):
-                    raise RuntimeError("SparseAdam: a non-contiguous parameter must be a row-strided 2-D view (packed table)")
+                rows_sorted, perm, acc, ldw, N, D = _row_step_operands(self, p, rows, vals, sorted_ids, dev)
                 _lib.check(
                     lib.mi_sparse_adam_sorted_ld(rows_sorted.data_ptr(), perm.data_ptr(), vals.data_ptr(), p.data_ptr(), ldw,
                                                  state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
@@ -133,6 +144,109 @@ class SparseSGD(torch.optim.Optimizer):
                 _lib.check(lib.mi_scatter_axpy_rows(rows.data_ptr(), vals.data_ptr(), -group["lr"], p.data_ptr(),
                                                     rows.numel(), p.numel() // N, N, _lib.stream_ptr(dev)),
                            "mi_scatter_axpy_rows")
+        return loss
+
+
+class SparseAdagrad(torch.optim.Optimizer):
+    """torch.optim.Adagrad's arguments and state (`step`, `sum`) on row-form gradients: the uncoalesced COO gradient the
+    lookup kernels emit is sorted once per distinct id tensor and stepped by ONE fused kernel pair
+    (mi_sparse_adagrad_sorted_ld) on the sorted-segment walker of SparseAdam.  Per touched row, G its coalesced gradient:
+        sum += G*G;  p -= clr * G / (sqrt(sum) + eps),   clr = lr / (1 + (step - 1) * lr_decay)
+    — torch.optim.Adagrad's sparse rule, and the exact form (duplicates summed before squaring).  state_dict() loads into a
+    torch.optim.Adagrad over the same parameters and back.  `step` is a host count, needed for lr_decay only: the group
+    carries `capturable = (lr_decay == 0)` for trainer.GraphedTrainStep."""
+
+    def __init__(self, params, lr=1e-2, lr_decay=0, eps=1e-10, initial_accumulator_value=0):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= lr_decay:
+            raise ValueError(f"Invalid lr_decay value: {lr_decay}")
+        if not 0.0 <= initial_accumulator_value:
+            raise ValueError(f"Invalid initial_accumulator_value value: {initial_accumulator_value}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        # the keys torch.optim.Adagrad's step reads (so that a loaded state_dict leaves it a complete group) + capturable
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=0,
+                                      initial_accumulator_value=initial_accumulator_value, foreach=None, maximize=False,
+                                      differentiable=False, fused=None, capturable=lr_decay == 0))
+        self._workspace = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                state = self.state[p]
+                state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                # contiguous [N, D] also for a parameter that is a view of a packed table (DeepFM.pack_tables())
+                state["sum"] = torch.full(p.shape, float(initial_accumulator_value), dtype=p.dtype, device=p.device)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:        # (a torch.optim.Adagrad state_dict has no such key)
+            group["capturable"] = group["lr_decay"] == 0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        lib = _lib.load()
+        sorted_ids = {}
+        for group in self.param_groups:
+            if group["weight_decay"] != 0:
+                raise RuntimeError("weight_decay option is not compatible with sparse gradients")
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                dev = _lib.require_gpu(p)
+                rows, vals = _coo_parts(p.grad)
+                state = self.state[p]
+                state["step"] += 1
+                clr = group["lr"] if group["lr_decay"] == 0 else \
+                    group["lr"] / (1 + (float(state["step"]) - 1) * group["lr_decay"])
+                rows_sorted, perm, acc, ldw, N, D = _row_step_operands(self, p, rows, vals, sorted_ids, dev)
+                _lib.check(
+                    lib.mi_sparse_adagrad_sorted_ld(rows_sorted.data_ptr(), perm.data_ptr(), vals.data_ptr(), p.data_ptr(), ldw,
+                                                    state["sum"].data_ptr(), acc.data_ptr(), rows.numel(), D, N, clr,
+                                                    group["eps"], _lib.stream_ptr(dev)),
+                    "mi_sparse_adagrad_sorted_ld",
+                )
+        return loss
+
+
+class RowwiseAdagrad(torch.optim.Optimizer):
+    """Exact row-wise Adagrad on row-form gradients: ONE fp32 accumulator per table row (state `sum` of shape [N]) — N*4
+    bytes of state against Adagrad's N*D*4 and Adam's 2*N*D*4.  Per touched row, G its coalesced gradient (all duplicates
+    summed first, in a fixed order):
+        sum[row] += mean_d(G_d * G_d);  p[row, :] -= lr * G / (sqrt(sum[row]) + eps)
+    This is the exact form: duplicates are summed BEFORE squaring ((sum_i g_i)^2, what FBGEMM calls EXACT_ROWWISE_ADAGRAD),
+    not the sum of g_i^2 of the "approx" form an atomic scatter gives.  One fused kernel pair
+    (mi_rowwise_adagrad_sorted_ld), no atomics, equal bits on a rerun; no host-side state, so it is always capturable."""
+
+    def __init__(self, params, lr=1e-2, eps=1e-8):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        super().__init__(params, dict(lr=lr, eps=eps, capturable=True))
+        self._workspace = {}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        lib = _lib.load()
+        sorted_ids = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                dev = _lib.require_gpu(p)
+                rows, vals = _coo_parts(p.grad)
+                state = self.state[p]
+                if not state:
+                    state["sum"] = torch.zeros(p.shape[0], dtype=torch.float32, device=dev)
+                rows_sorted, perm, acc, ldw, N, D = _row_step_operands(self, p, rows, vals, sorted_ids, dev)
+                _lib.check(
+                    lib.mi_rowwise_adagrad_sorted_ld(rows_sorted.data_ptr(), perm.data_ptr(), vals.data_ptr(), p.data_ptr(), ldw,
+                                                     state["sum"].data_ptr(), acc.data_ptr(), rows.numel(), D, N, group["lr"],
+                                                     group["eps"], _lib.stream_ptr(dev)),
+                    "mi_rowwise_adagrad_sorted_ld",
+                )
         return loss
 
 
@@ -210,6 +324,56 @@ def _dense_adam(params, lr, weight_decay):
     return torch.optim.Adam(params, lr=lr, weight_decay=weight_decay)
 
 
+class Adagrad(torch.optim.Adagrad):
+    """torch.optim.Adagrad (same constructor, param_groups and state_dict) whose step over fp32 contiguous GPU parameters
+    with dense gradients and lr_decay == 0 is mi_adagrad_dense_multi: one launch per 24 tensors, one read and one write of
+    p and sum.  The rule has no step count in it then, so the step is capturable; `step` stays torch's host count.
+    Anything else (lr_decay, maximize, differentiable, fused, a tensor lr, sparse gradients, non-fp32 or CPU parameters)
+    takes torch's own step."""
+
+    def _kernel_ok(self, group) -> bool:
+        if group["lr_decay"] != 0 or group["maximize"] or group["differentiable"] or group["fused"]:
+            return False
+        if isinstance(group["lr"], torch.Tensor):
+            return False
+        return all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not (p.grad is not None and p.grad.is_sparse)
+                   for p in group["params"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if not all(self._kernel_ok(g) for g in self.param_groups):
+            return super().step(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        for group in self.param_groups:
+            params, grads, sums, steps = [], [], [], []
+            self._init_group(group, params, grads, sums, steps)          # torch's own state layout
+            if not params:
+                continue
+            dev = _lib.require_gpu(*params)
+            grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
+            for s in steps:                                              # (host counts, as in torch's own step)
+                s += 1
+            n = len(params)
+            arr = ctypes.c_void_p * n
+            _lib.check(lib.mi_adagrad_dense_multi(arr(*[t.data_ptr() for t in params]), arr(*[t.data_ptr() for t in grads]),
+                                                  arr(*[t.data_ptr() for t in sums]),
+                                                  (ctypes.c_int64 * n)(*[t.numel() for t in params]), n, group["lr"],
+                                                  group["eps"], group["weight_decay"], _lib.stream_ptr(dev)),
+                       "mi_adagrad_dense_multi")
+        return loss
+
+
+def _dense_adagrad(params, lr, weight_decay):
+    """`torch.optim.Adagrad(params, lr=..., weight_decay=...)`: on the GPU the subclass above, otherwise torch's own."""
+    if len(params) > 0 and all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        return Adagrad(params, lr=lr, weight_decay=weight_decay)
+    return torch.optim.Adagrad(params, lr=lr, weight_decay=weight_decay)
+
+
 def get_optimizers(model, config: Dict) -> List[torch.optim.Optimizer]:
     """src/models/deepfm.py:155-219 with the sparse branches on the fused row-sparse steps."""
     sparse: bool = config.get("sparse", False)
@@ -233,4 +397,15 @@ def get_optimizers(model, config: Dict) -> List[torch.optim.Optimizer]:
             return [torch.optim.SGD(model.parameters(), lr=config["learning_rate"], weight_decay=config["weight_decay"])]
         return [SparseSGD(no_decay_param, lr=lr_emb),
                 torch.optim.SGD(decay_param, lr=config["learning_rate"], weight_decay=config["weight_decay"])]
+    elif optimizer_name == "adagrad":
+        if not sparse:
+            return [_dense_adagrad(list(model.parameters()), lr=config["learning_rate"], weight_decay=config["weight_decay"])]
+        return [SparseAdagrad(no_decay_param, lr=lr_emb),
+                _dense_adagrad(decay_param, lr=config["learning_rate"], weight_decay=config["weight_decay"])]
+    elif optimizer_name == "rowwise_adagrad":
+        if not sparse:
+            raise ValueError("optimizer 'rowwise_adagrad' keeps one accumulator per table row and needs row-form gradients: "
+                             "build the embedding with sparse=True")
+        return [RowwiseAdagrad(no_decay_param, lr=lr_emb),
+                _dense_adagrad(decay_param, lr=config["learning_rate"], weight_decay=config["weight_decay"])]
     raise ValueError(f"{optimizer_name=} is not recognized")

@@ -70,6 +70,40 @@ def one(seed):
         a1.step(), a2.step()
     for a, b in zip(ps, pd):
         close(b, a, 5e-6, 1e-7, f"dense adam {tuple(a.shape)}", seed)
+    # ---- sparse Adagrad against torch's on the CPU, row-wise Adagrad against its restatement, at the width drawn above
+    decay = 0.01 * (seed & 1)
+    p, q, pr = (torch.nn.Parameter(W0.clone().to(DEV)), torch.nn.Parameter(W0.clone()), torch.nn.Parameter(W0.clone().to(DEV)))
+    o1 = optim.SparseAdagrad([p], lr=0.01, lr_decay=decay, initial_accumulator_value=0.1)
+    o2 = torch.optim.Adagrad([q], lr=0.01, lr_decay=decay, initial_accumulator_value=0.1)
+    o3 = optim.RowwiseAdagrad([pr], lr=0.01)
+    qr, sr = W0.clone().double(), torch.zeros(Nr, dtype=torch.float64)
+    for _ in range(2):
+        r = (Nr * torch.rand(n, generator=g).pow(ri(1, 3))).long().clamp_(max=Nr - 1)
+        v = torch.randn(n, D, generator=g)
+        p.grad = torch.sparse_coo_tensor(r.view(1, -1).to(DEV), v.to(DEV), (Nr, D), check_invariants=False)
+        pr.grad = p.grad
+        q.grad = torch.sparse_coo_tensor(r.view(1, -1), v, (Nr, D))
+        o1.step(), o2.step(), o3.step()
+        g64 = torch.zeros(Nr, D, dtype=torch.float64).index_add_(0, r, v.double())
+        touched = torch.zeros(Nr, dtype=torch.bool).index_fill_(0, r, True)
+        sr = torch.where(touched, sr + (g64 * g64).mean(1), sr)
+        qr = torch.where(touched[:, None], qr - 0.01 * g64 / (sr.sqrt()[:, None] + 1e-8), qr)
+    # (the accumulator starts at 0.1 / the row mean is not small: no ill-conditioned elements to leave out)
+    close(p, q, 1e-5, 1e-6, f"sparse adagrad D={D} n={n} N={Nr}", seed)
+    close(o1.state[p]["sum"], o2.state[q]["sum"], 1e-5, 1e-7, f"sparse adagrad sum D={D}", seed)
+    close(pr, qr, 1e-5, 1e-5, f"row-wise adagrad D={D} n={n} N={Nr}", seed)
+    close(o3.state[pr]["sum"], sr, 1e-5, 1e-7, f"row-wise adagrad sum D={D}", seed)
+    # ---- dense Adagrad over the same odd tensors
+    ps = [torch.nn.Parameter(t.detach().clone()) for t in ps]
+    pd = [torch.nn.Parameter(t.detach().clone().to(DEV)) for t in ps]
+    a1, a2 = optim.Adagrad(pd, lr=1e-2, weight_decay=1e-3), torch.optim.Adagrad(ps, lr=1e-2, weight_decay=1e-3)
+    for _ in range(2):
+        for a, b in zip(ps, pd):
+            gr = torch.randn(a.shape, generator=g)
+            a.grad, b.grad = gr, gr.to(DEV)
+        a1.step(), a2.step()
+    for a, b in zip(ps, pd):
+        close(b, a, 5e-6, 1e-7, f"dense adagrad {tuple(a.shape)}", seed)
     # ---- masked InfoNCE
     m, Dn = ri(2, 300), [8, 16, 64][ri(0, 2)]
     v = torch.randn(m, Dn, generator=g)

@@ -12,6 +12,13 @@ Kernels are matched by their DEMANGLED name (an empty template parameter pack ch
 that the second build turned into a template on one bool flag is matched with its `<false>` instantiation ("AS" line).  Prints
 every kernel of the first build whose VGPR, SGPR, AGPR, scratch, LDS or occupancy figure moved or that is gone, then a
 count per kernel family; exit status 1 if anything moved.
+
+`--as OLD=NEW` (repeatable) follows a kernel family that was renamed and gained trailing template parameters — a walker
+moved into a header and parametrised by a policy: every kernel of the first build in family OLD is compared with EVERY
+kernel of the second build in family NEW whose template arguments begin with OLD's (one line per policy).
+
+    python tools/kernel_resource_diff.py parent.txt this.txt --as k_sparse_adam=mi::k_rows_pass \
+        --as k_sparse_adam_long=mi::k_rows_join --as k_sparse_adam_anyD=mi::k_rows_any
 """
 import re
 import subprocess
@@ -52,12 +59,44 @@ def renamed(name, b):
     return hits[0] if len(hits) == 1 else None
 
 
+def template_args(name):
+    m = re.match(r"^(?:void )?[\w:]+<(.*)>\(", name)
+    return m.group(1) if m else ""
+
+
+def followed(name, b, renames):
+    """The second build's kernels of the family `--as` maps this kernel's family to, with its template arguments in front."""
+    new = renames.get(family(name))
+    if new is None:
+        return []
+    args = template_args(name)
+    return [n for n in sorted(b) if family(n) == new and (not args or template_args(n).startswith(args + ", "))]
+
+
 def main():
-    a, b = parse(sys.argv[1]), parse(sys.argv[2])
+    argv, renames = [], {}
+    it = iter(sys.argv[1:])
+    for arg in it:
+        if arg == "--as":
+            old, new = next(it).split("=", 1)
+            renames[old] = new
+        else:
+            argv.append(arg)
+    a, b = parse(argv[0]), parse(argv[1])
     fam, moved = {}, 0
     for name in sorted(a):
         f = fam.setdefault(family(name), [0, 0])
         f[0] += 1
+        others = [] if name in b else followed(name, b, renames)
+        if others:
+            any_moved = False
+            for other in others:
+                d = [(k, a[name].get(k), b[other].get(k)) for k in KEYS if a[name].get(k) != b[other].get(k)]
+                print("AS   ", name, "->", other, d if d else "unchanged")
+                any_moved |= bool(d)
+            f[1] += any_moved
+            moved += any_moved
+            continue
         other = name if name in b else renamed(name, b)
         if other is None:
             print("GONE ", name)
