@@ -28,16 +28,25 @@ def _int64_rows(B: int, F: int, dev) -> torch.Tensor:
     return _new((B, F, 2), dev).view(torch.int64).view(B, F)
 
 
-def _expert_fused(r: int, d: int) -> bool:
-    """mi_mix_expert_fwd/bwd cover ranks 16 / 32 / 64 (the reference's configs use 64) and d % 4 == 0."""
-    return _kernels.PANEL_GEMM and r in (16, 32, 64) and d % 4 == 0
+def _aligned16(*ts) -> bool:
+    """Every given operand starts on a 16-byte boundary (None passes).  The float4 launchers (mi_cross_bwd_head,
+    mi_rowdot_multi, mi_mix_expert_*) return MI_ERR_UNSUPPORTED otherwise: a contiguous float32 VIEW that starts inside a
+    larger buffer passes _f32c untouched, so the guards in front of them decline on it the way gemm_panel does."""
+    return not any(t is not None and t.data_ptr() % 16 for t in ts)
+
+
+def _expert_fused(r: int, d: int, *operands) -> bool:
+    """mi_mix_expert_fwd/bwd cover ranks 16 / 32 / 64 (the reference's configs use 64), d % 4 == 0 and 16-byte aligned
+    operands."""
+    return _kernels.PANEL_GEMM and r in (16, 32, 64) and d % 4 == 0 and _aligned16(*operands)
 
 
 def _bwd_head(g, x0, lin, gate, E, b, dlin, dx0, accumulate, db, dgs, M, d, s):
     """dlin = g*x0, dx0 (+)= g*lin, db += sum_m dlin*rs(m), dgs[m] = dlin[m,:].b in one launch (mi_cross_bwd_head);
-    shapes it does not cover (d % 4, d > 1024) take the three separate passes."""
+    shapes and operands it does not cover (d % 4, d > 1024, a pointer off the 16-byte boundary) take the three separate
+    passes."""
     lib = _lib.load()
-    ok = d % 4 == 0 and d <= 1024
+    ok = d % 4 == 0 and d <= 1024 and _aligned16(g, x0, lin, b, dlin, dx0)
     if ok:
         _lib.check(lib.mi_cross_bwd_head(g.data_ptr(), x0.data_ptr(), lin.data_ptr(), _lib.ptr(gate), E, _lib.ptr(b),
                                          dlin.data_ptr(), dx0.data_ptr(), int(accumulate), db.data_ptr(), _lib.ptr(dgs), M, d, s),
@@ -140,13 +149,13 @@ class _DCNMixFn(torch.autograd.Function):
         for l in range(L):
             xl = xs[-1]
             gate = _new((M, E), dev)
-            if d % 4 == 0 and E <= 8:                                                          # g_e = x_l . G_e
+            if d % 4 == 0 and E <= 8 and _aligned16(xl, G):                                    # g_e = x_l . G_e
                 _lib.check(_lib.load().mi_rowdot_multi(xl.data_ptr(), d, G.data_ptr(), gate.data_ptr(), M, d, E,
                                                        _lib.stream_ptr(dev)), "mi_rowdot_multi")
             else:
                 gemm(xl, G, gate, M, E, d, d, d, E, transB=True)
             H1, H2, H2g = _new((M, Er), dev), _new((M, Er), dev), _new((M, Er), dev)
-            if _expert_fused(r, d):          # tanh(x_l V_e), tanh(. C_e), * g_e in one launch
+            if _expert_fused(r, d, xl, Vs[l], Cs[l], H1, H2, H2g):   # tanh(x_l V_e), tanh(. C_e), * g_e in one launch
                 _lib.check(_lib.load().mi_mix_expert_fwd(xl.data_ptr(), Vs[l].data_ptr(), Cs[l].data_ptr(), gate.data_ptr(),
                                                          H1.data_ptr(), H2.data_ptr(), H2g.data_ptr(), M, d, E, r,
                                                          _lib.stream_ptr(dev)), "mi_mix_expert_fwd")
@@ -210,7 +219,8 @@ class _DCNMixFn(torch.autograd.Function):
             _bwd_head(g, x0, T, gate, E, bs[l], dT, dx0, l != L - 1, db, dgsum, M, d, s)
             later.append(dict(A=H2g, B=dT, C=dU, M=Er, N=d, K=M, lda=Er, ldb=d, ldc=d))          # dU = H2g^T dT
             dgate, dZ2, dZ1 = _new((M, E), dev), _new((M, Er), dev), _new((M, Er), dev)
-            if _expert_fused(r, d):          # dT U^T, the gate / tanh backward and (dZ2_e C_e^T) * tanh' in one launch
+            # dT U^T, the gate / tanh backward and (dZ2_e C_e^T) * tanh' in one launch
+            if _expert_fused(r, d, dT, Us[l], Cs[l], H1, H2, dZ2, dZ1):
                 _lib.check(lib.mi_mix_expert_bwd(dT.data_ptr(), Us[l].data_ptr(), Cs[l].data_ptr(), gate.data_ptr(),
                                                  H1.data_ptr(), H2.data_ptr(), dgsum.data_ptr(), dgate.data_ptr(),
                                                  dZ2.data_ptr(), dZ1.data_ptr(), M, d, E, r, s), "mi_mix_expert_bwd")

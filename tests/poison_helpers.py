@@ -2631,6 +2631,126 @@ def _slot_deepfm_case(labels, B=33, F=5, D=16):
     return Case(f"slot_deepfm-fused-{'labels' if labels else 'nolabels'}-B{B}-F{F}-D{D}", run, check)
 
 
+# ---- sixth batch: the CrossNet fallbacks (tests/test_dcn_dispatch_gpu.py) ------------------------------------------------------
+def _cross_helper_cases():
+    """mi_cross_bwd_pre, mi_colsum (the gate as rowscale with nrs = 3, and rs_sum), mi_rowdot, mi_outer and mi_mix_gate_bwd
+    through the C-ABI on outputs from torch.empty (NaN under poison): the passes layer_dcn.py falls back to write everything
+    they own.  Integer-valued data against the formulas in float64, bit-exact as in test_dcn_dispatch_gpu.py (mi_outer: one
+    rounded multiply per element against the float32 product)."""
+    def ints(gen, *sh):
+        return torch.randint(-3, 4, sh, generator=gen).float()
+
+    def case(name, operands, launch, reference):
+        def run():
+            from recsys_benchmark_amd import _lib
+
+            t = {k: v.to(DEV) for k, v in operands().items()}
+            return launch(_lib, _lib.load(), _lib.stream_ptr(torch.device(DEV, torch.cuda.current_device())), t)
+
+        def check(result):
+            want = reference({k: v.double() for k, v in operands().items()})
+            assert set(want) == set(result), f"{name}: returned {sorted(result)} vs reference {sorted(want)}"
+            for k, v in want.items():
+                assert torch.equal(result[k].cpu().double(), v), f"{name}: {k}"
+
+        return Case(name, run, check, True)
+
+    def pre_ops(n=524288 + 259):
+        gen = torch.Generator().manual_seed(n)
+        return dict(g=ints(gen, n), x0=ints(gen, n), lin=ints(gen, n), prev=ints(gen, n))
+
+    def pre_launch(_lib, lib, st, t):
+        out, n = {}, t["g"].numel()
+        for acc in (0, 1):
+            dlin = torch.empty(n, device=DEV)
+            dx0 = t["prev"].clone() if acc else torch.empty(n, device=DEV)
+            _lib.check(lib.mi_cross_bwd_pre(t["g"].data_ptr(), t["x0"].data_ptr(), t["lin"].data_ptr(), dlin.data_ptr(), dx0.data_ptr(),
+                                            n, acc, st), "mi_cross_bwd_pre")
+            out.update({f"acc{acc}/dlin": dlin, f"acc{acc}/dx0": dx0})
+        return out
+
+    def pre_ref(t):
+        out = {}
+        for acc in (0, 1):
+            out.update({f"acc{acc}/dlin": t["g"] * t["x0"], f"acc{acc}/dx0": (t["prev"] if acc else 0) + t["g"] * t["lin"]})
+        return out
+
+    M, N, ldx, nrs = 257, 65, 70, 3
+
+    def colsum_ops():
+        gen = torch.Generator().manual_seed(M + N)
+        return dict(X=ints(gen, M, ldx), gate=ints(gen, M, nrs))
+
+    def colsum_launch(_lib, lib, st, t):
+        out, rs_sum = torch.zeros(N, device=DEV), torch.zeros(1, device=DEV)       # (both ADDED into: the caller's zero fill)
+        _lib.check(lib.mi_colsum(t["X"].data_ptr(), ldx, t["gate"].data_ptr(), nrs, out.data_ptr(), rs_sum.data_ptr(), M, N, st),
+                   "mi_colsum")
+        return dict(out=out, rs_sum=rs_sum)
+
+    def colsum_ref(t):
+        rs = t["gate"].sum(1)
+        return dict(out=(t["X"][:, :N] * rs[:, None]).sum(0), rs_sum=rs.sum().view(1))
+
+    Mr, Nr, ldr = 130, 65, 72
+
+    def rowdot_ops():
+        gen = torch.Generator().manual_seed(Mr + Nr)
+        return dict(X=ints(gen, Mr, ldr), v=ints(gen, Nr), bias=ints(gen, 1), addend=ints(gen, Mr))
+
+    def rowdot_launch(_lib, lib, st, t):
+        plain, full = torch.empty(Mr, device=DEV), torch.empty(Mr, device=DEV)
+        _lib.check(lib.mi_rowdot(t["X"].data_ptr(), ldr, t["v"].data_ptr(), None, None, plain.data_ptr(), Mr, Nr, st), "mi_rowdot")
+        _lib.check(lib.mi_rowdot(t["X"].data_ptr(), ldr, t["v"].data_ptr(), t["bias"].data_ptr(), t["addend"].data_ptr(),
+                                 full.data_ptr(), Mr, Nr, st), "mi_rowdot")
+        return dict(plain=plain, full=full)
+
+    def rowdot_ref(t):
+        base = t["X"][:, :Nr] @ t["v"]
+        return dict(plain=base, full=base + t["bias"] + t["addend"])
+
+    def outer_ops():
+        gen = torch.Generator().manual_seed(70 + 1028)
+        return dict(g=torch.randn(70, generator=gen), w=torch.randn(1028, generator=gen), g2=torch.randn(7, generator=gen),
+                    w2=torch.randn(5, generator=gen))
+
+    def outer_launch(_lib, lib, st, t):
+        wide, odd = torch.empty(70, 1028, device=DEV), torch.empty(7, 5, device=DEV)
+        _lib.check(lib.mi_outer(t["g"].data_ptr(), t["w"].data_ptr(), wide.data_ptr(), 70, 1028, st), "mi_outer")
+        _lib.check(lib.mi_outer(t["g2"].data_ptr(), t["w2"].data_ptr(), odd.data_ptr(), 7, 5, st), "mi_outer")
+        return dict(wide=wide, odd=odd)
+
+    def outer_ref(t):      # (the float32 product, exactly: float32 x float32 is exact in float64, rounded once on the way back)
+        return dict(wide=(t["g"][:, None] * t["w"][None]).float().double(), odd=(t["g2"][:, None] * t["w2"][None]).float().double())
+
+    Mg, Eg, rg = 130, 2, 80
+
+    def gate_ops():
+        gen = torch.Generator().manual_seed(Mg + Eg + rg)
+        return dict(dH=ints(gen, Mg, Eg * rg), H2=ints(gen, Mg, Eg * rg), gate=ints(gen, Mg, Eg), dgs=ints(gen, Mg))
+
+    def gate_launch(_lib, lib, st, t):
+        dgate, dZ2 = torch.empty(Mg, Eg, device=DEV), torch.empty(Mg, Eg * rg, device=DEV)
+        _lib.check(lib.mi_mix_gate_bwd(t["dH"].data_ptr(), t["H2"].data_ptr(), t["gate"].data_ptr(), t["dgs"].data_ptr(),
+                                       dgate.data_ptr(), dZ2.data_ptr(), Mg, Eg, rg, st), "mi_mix_gate_bwd")
+        return dict(dgate=dgate, dZ2=dZ2)
+
+    def gate_ref(t):
+        dh, h = t["dH"].view(Mg, Eg, rg), t["H2"].view(Mg, Eg, rg)
+        return dict(dgate=(dh * h).sum(2) + t["dgs"][:, None], dZ2=(dh * t["gate"][:, :, None] * (1 - h * h)).view(Mg, Eg * rg))
+
+    return [case("cross_bwd_pre-n524547", pre_ops, pre_launch, pre_ref),
+            case(f"colsum-gate-M{M}-N{N}-nrs{nrs}-rs_sum", colsum_ops, colsum_launch, colsum_ref),
+            case(f"rowdot-M{Mr}-N{Nr}", rowdot_ops, rowdot_launch, rowdot_ref),
+            case("outer-70x1028-7x5", outer_ops, outer_launch, outer_ref),
+            case(f"mix_gate_bwd-M{Mg}-E{Eg}-r{rg}", gate_ops, gate_launch, gate_ref)]
+
+
+def _build6():
+    # (heads whose every layer runs on the fallbacks: odd d, d > 1024, no fused experts, the gate product as a GEMM)
+    return [_dcn_head_case(33, 22, 2), _dcn_head_case(5, 1030, 1), _dcn_mix_case(50, 22, 3, 16, 2),
+            _dcn_mix_case(20, 40, 9, 8, 2)] + _cross_helper_cases()
+
+
 def _build5():
     cases = []
     for F, D in ((3, 4), (26, 16), (39, 16), (70, 8)):          # (pack_tables() covers D in {4, 8, 16})
@@ -2691,7 +2811,7 @@ def _build():
     cases += [_deepfm_case(labels, fused) for labels in (True, False) for fused in (True, False)]
     cases += [_auc_case(n) for n in (3, 257, 4097)]
     cases += [_gather_quant_case(q) for q in ("fp16", "int8", "int16")]
-    cases += _build2() + _build3() + _build4() + _build5()
+    cases += _build2() + _build3() + _build4() + _build5() + _build6()
     names = [c.name for c in cases]
     assert len(set(names)) == len(names), "duplicate case names"
     return cases

@@ -2,7 +2,8 @@
     python tools/fuzz.py [cases [first seed]]
 field sort, sparse Adam (all widths), dense Adam (mixed sizes / unaligned views), masked InfoNCE, gather+FM with both
 gradient forms, the fp32 MFMA GEMM at random small shapes, and the round-2 CrossNet kernels (panel / multi-problem GEMMs, the
-fused backward head, the per-expert kernels).  Stops at the first mismatch with the seed that reproduces it."""
+fused backward head, the per-expert kernels) and the CrossNet heads at widths off their fast path.  Stops at the first
+mismatch with the seed that reproduces it."""
 import os
 import sys
 
@@ -301,6 +302,48 @@ def crossnet_case(seed):
     close(dZ1.view(Me, Ee, re_), torch.einsum("mek,eck->mec", dz2, Cm.double()) * (1 - h1f * h1f), 1e-4, 1e-5, "expert dZ1", seed)
 
 
+def crossnet_offpath_case(seed):
+    """DCNHead and DCN_MixHead, forward and backward, at widths with NO multiple-of-4 constraint (d in 1..70, one time in five
+    1025..1040), E in 1..12, rank in 1..70, 0..3 layers — the fallbacks of layer_dcn.py's dispatch (three-pass backward head,
+    gate product as a GEMM, separate expert products, general-GEMM epilogues) — against the oracle in float64 with the
+    contract of tests/test_dcn_gpu.py: activations rtol 2e-5 / atol 2e-6, gradients rtol 2e-4 / atol 2e-5, atol scaled by
+    max(1, max|ref|).  Stock float32 on the CPU stays below 0.05 of that for the seeds tests/test_fuzz_gpu.py runs."""
+    from recsys_benchmark_amd.layer_dcn import DCN_MixHead, DCNHead
+
+    g = torch.Generator().manual_seed(seed)
+    ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))  # noqa: E731
+    wide = ri(0, 4) == 0
+    d = ri(1025, 1040) if wide else ri(1, 70)
+    E, r, L = ri(1, 12), ri(1, 70), ri(0, 3)
+    M = ri(1, 12) if wide else ri(1, 90)
+    torch.manual_seed(seed)
+    heads = (("dcn", DCNHead(L, d), ro.dcn_head), ("mix", DCN_MixHead(E, L, r, d), ro.dcn_mix_head))
+    with torch.no_grad():
+        for b in heads[1][1].biases:
+            b.copy_(torch.randn(b.shape, generator=g) * 0.1)
+    X = torch.randn(M, d, generator=g) * (0.05 if d > 100 else 0.3)
+    G = torch.randn(M, d, generator=g)
+    for kind, head, oracle in heads:
+        what = f"offpath {kind} head M={M} d={d} E={E} r={r} L={L}"
+        p = {k: v.detach().clone().double().requires_grad_(True) for k, v in head.state_dict().items()}
+        x = X.double().requires_grad_(True)
+        ref = oracle(x, p, L)
+        (ref * G.double()).sum().backward()
+        head.to(DEV)
+        xd = X.to(DEV).requires_grad_(True)
+        out = head(xd)
+        (out * G.to(DEV)).sum().backward()
+        named = dict(head.named_parameters())
+        items = [("out", out, ref.detach(), 2e-5, 2e-6), ("dx", xd.grad, x.grad, 2e-4, 2e-5)]
+        for k, v in p.items():
+            if (v.grad is None) != (named[k].grad is None):
+                raise SystemExit(f"MISMATCH {what}: {k} has a gradient on one side only; seed={seed}")
+            if v.grad is not None:
+                items.append((k, named[k].grad, v.grad, 2e-4, 2e-5))
+        for k, got, want, rtol, atol in items:
+            close(got, want, rtol, atol * max(1.0, float(want.abs().max())), f"{what} {k}", seed)
+
+
 ambiguous = []     # tail cases that match float64 only with a near-kink ReLU decision taken the other way
 
 
@@ -549,6 +592,7 @@ if __name__ == "__main__":
         crossnet_case(700000 + s)
         tail_case(900000 + s)
         tail_mixed_case(1100000 + s)
+        crossnet_offpath_case(1300000 + s)
         if s % 25 == 24:
             print(f"{s + 1} cases ok", flush=True)
     print(f"FUZZ_OK ({len(ambiguous)} tail cases matched float64 with a ReLU decision on the kink taken the other way: seeds {ambiguous[:8]})")
