@@ -1509,6 +1509,19 @@ MI_API int mi_tail_wgrad_gemm(const float *DY, const float *Zl, int32_t ld, cons
                               const float *bz, const float *de, const float *pZ, int32_t pld, const float *p_mu,
                               const float *p_sc, const float *p_be, float p_p, const uint8_t *p_keep, float *slab,
                               float *dW, int32_t M, int32_t N, int32_t K, void *stream);
+/* mi_tail_ring_plan: the schedule the products' main loop walks for a reduction of nst 32-wide slices, by host arithmetic
+ * only (nothing launched, no GPU needed): the very control flow the kernels compile, with a recorder in place of the
+ * loads, LDS writes and MFMAs.  role 0 = the producer waves, 1 = the consumer waves, 2 = the producer waves of the
+ * products whose operands use general addressing (one loop over all phases; the same schedule).  partial: the range is no multiple
+ * of 32 (its short slice is slice 0); dead_half: that slice ends inside its first half; pre: the consumers join
+ * statistics in front of the first LDS write (one extra barrier).  events: cap records of 6 int32 each,
+ *   (kind, slice, reg, slot, any, pos)   kind 0 ring barrier, 1 the extra barrier, 2 fetch (loads of `slice` into register
+ *   stage `reg`), 3 finish (stage `reg` transformed and written to LDS slot `slot`), 4 fragment read (half `reg` of
+ *   `slice` out of `slot`), 5 the MFMAs of fragment set `reg`;
+ *   any = 1: the form that may meet a partial slice; pos: the slice's position in the range (x 32 = its first index).
+ * *n = the number of events (also when it exceeds cap: nothing is written beyond cap). */
+MI_API int mi_tail_ring_plan(int32_t nst, int32_t partial, int32_t dead_half, int32_t pre, int32_t role, int32_t *events,
+                             int32_t cap, int32_t *n);
 
 /* ---- a9: DHEmbedding's MLP (src/models/embeddings/dh_embedding.py:100-117,345-356) -----------------------------------
  * Per layer Linear -> Mish (use_bn 0) | Linear -> BatchNorm1d -> Mish (use_bn 2, the default) | Linear -> Mish ->

@@ -211,6 +211,7 @@ SIGNATURES = {
     "mi_gemm_f32_multi_ride": [_p, _i32, _i32, _i32, _p, _p],
     "mi_gemm_f32_multi_plan": [_p, _i32, _i32, _i32, _p, _p, _p],
     "mi_gemm_f32_multi_slots": [_p, _i32, _i32, _i32, _p],
+    "mi_tail_ring_plan": [_i32, _i32, _i32, _i32, _i32, _p, _i32, _p],
     "mi_gemm_f32_panel": [_p, _i32, _p, _i32, _i32, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p],
     "mi_mix_expert_fwd": [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],
     "mi_mix_expert_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p],

@@ -1313,6 +1313,29 @@ bool vec_ok(const void *p, int ld) { return aligned16(p) && ld % 4 == 0; }
 
 }  // namespace
 
+// The ring's schedule as the host sees it: tail_gemm.hpp's walkers (the main loop's own control flow) over a recorder.
+namespace {
+struct RingRecorder {
+  int32_t *out;
+  int cap, n, nst;
+  bool partial, pre;
+  void put(int kind, int slice, int reg, int any) {
+    if (n < cap) {
+      int32_t *e = out + 6 * (int64_t)n;
+      e[0] = kind; e[1] = slice; e[2] = reg; e[3] = slice >= 0 ? tg::ring_slot(slice) : -1; e[4] = any;
+      e[5] = slice >= 0 && slice < nst ? tg::ring_at(nst, partial, slice) : -1;
+    }
+    ++n;
+  }
+  void barrier() { put(0, -1, -1, 0); }
+  void pre_barrier() { if (pre) put(1, -1, -1, 0); }
+  template <int S> void fetch(int slice, bool any) { put(2, slice, S, any); }
+  template <int S> void finish(int slice, bool any) { put(3, slice, S, any); }
+  template <int F> void read(int slice, int half) { put(4, slice, half, 0); }
+  template <int F> void mma() { put(5, -1, F, 0); }
+};
+}  // namespace
+
 extern "C" {
 
 static bool bn_fwd_view(const mi_tail_bn_fwd *m, BnFwd *out) {
@@ -1744,6 +1767,20 @@ int mi_tail_wgrad_gemm(const float *DY, const float *Zl, int32_t ld, const float
   const int64_t n4 = (int64_t)N * K / 4;
   MI_LAUNCH("tail_slab_sum", k_slab_sum, (int)((n4 + kBlock - 1) / kBlock), kBlock, stream, (const float *)slab, a.splits, n4, dW);
   return launch_status();
+}
+
+int mi_tail_ring_plan(int32_t nst, int32_t partial, int32_t dead_half, int32_t pre, int32_t role, int32_t *events, int32_t cap,
+                      int32_t *n) {
+  if (nst <= 0 || cap < 0 || (cap > 0 && !events) || !n || role < 0 || role > 2 || (dead_half && !partial)) return MI_ERR_INVALID_ARG;
+  RingRecorder r{events, cap, 0, nst, partial != 0, pre != 0};
+  if (role == 0) tg::ring_produce(nst, r);
+  else if (role == 2) tg::ring_produce_general(nst, r);
+  else {
+    tg::ring_consume_open(r);
+    tg::ring_consume(nst, dead_half != 0, r);
+  }
+  *n = r.n;
+  return MI_OK;
 }
 
 }  // extern "C"

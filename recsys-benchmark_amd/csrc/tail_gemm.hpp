@@ -52,6 +52,13 @@ __device__ __forceinline__ float4 vld4(lds_cfp p) {
 }
 __device__ __forceinline__ void vst4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+// "These four registers, as they are, here": an empty asm that takes and returns v.  The producers call it on the vectors of
+// a register stage right before a TRANSPOSING LDS write (16 registers re-paired for four ds_write_b128).  A stage lives
+// across the main loop's back edge, and hipcc moved the re-pairing across it, into the blocks that end on the edge: the
+// v_mov_b32 block then stood at the END of the phase that ISSUED the loads, behind s_waitcnt vmcnt(7)..(0) — a wait for
+// loads a few instructions old, once per trip — and both sets of registers were live (profiles/tail_ring_isa.txt; the
+// parent's "one phase in three ends on vmcnt(1) / (2)").  With the asm the values as loaded are what crosses the edge.
+__device__ __forceinline__ void hold(float4 &v) { asm("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
 // ---- dropout --------------------------------------------------------------------------------------------------------
 // The keep decisions of a layer are one BIT per element, written once per step by k_tail_dropmask (tail.hip) from a
@@ -148,7 +155,10 @@ struct LoadPlain {
   static constexpr bool kLean = true;
   const float *P;
   int ld;
-  struct Raw { float4 a; };
+  struct Raw {
+    float4 a;
+    __device__ __forceinline__ void hold_regs() { hold(a); }
+  };
   typedef NoConsts Consts;
   struct Win { rsrc_t p; };
   struct UBase { rsrc_t p; uint32_t soff; };
@@ -177,7 +187,11 @@ struct LoadActT {
   int ld;
   CP mu, sc, be;
   Drop drop;
-  struct Raw { float4 z; uint32_t keep; };
+  struct Raw {
+    float4 z;
+    uint32_t keep;
+    __device__ __forceinline__ void hold_regs() { hold(z); }
+  };
   struct Consts { float4 u, s, b; };
   struct Win { rsrc_t z, bits; CP mu, sc, be; };      // the keep bits of the same elements: one byte per 8
   struct UBase { rsrc_t z, bits; uint32_t soff, ksoff; CP mu, sc, be; };
@@ -234,7 +248,13 @@ struct LoadDzT {
   const float *DY, *Z;
   int ld;
   CP mu, al, bz, de;
-  struct Raw { float4 dy, z; };
+  struct Raw {
+    float4 dy, z;
+    __device__ __forceinline__ void hold_regs() {
+      hold(dy);
+      hold(z);
+    }
+  };
   struct Consts { float4 u, a, b, d; };
   struct Win { rsrc_t dy, z; CP mu, al, bz, de; };
   struct UBase { rsrc_t dy, z; uint32_t soff; CP mu, al, bz, de; };
@@ -445,6 +465,7 @@ struct OtStage {
 // General addressing (loaders without the lean interface: panel_gemm.hip's grouped operand).
 template <int ROWS, class L>
 struct OtOperandG {
+  static constexpr bool kExitFree = false;      // see ring_produce_general
   L ld;
   int out0, out_valid, red_end;
   __device__ __forceinline__ OtMap<ROWS, L> prep() const {
@@ -494,6 +515,7 @@ struct OtOperandG {
 template <int ROWS, class L>
 struct OtOperand {
   static_assert(L::kLean, "OtOperand needs a loader with the lean interface (else OtOperandG)");
+  static constexpr bool kExitFree = true;
   L ld;
   int out0, out_valid, red_end;
   __device__ __forceinline__ OtMap<ROWS, L> prep() const {
@@ -536,7 +558,11 @@ struct OtOperand {
     const auto ub = ld.ubase(m.win, red0, 0);
     float4 v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = ld.finish_u(st.raw[j], m.k, ub, m.tc[j]);
+    for (int j = 0; j < 4; ++j) {
+      typename L::Raw raw = st.raw[j];
+      raw.hold_regs();
+      v[j] = ld.finish_u(raw, m.k, ub, m.tc[j]);
+    }
     store_block(T, m, v);
   }
   // a slice that may be partial: rows beyond the end re-aimed at the last valid one, their values zeroed
@@ -571,6 +597,7 @@ struct NoPrep {};
 // General addressing (loaders without the lean interface).
 template <int ROWS, class L, int NP = kProd>
 struct KcOperandG {
+  static constexpr bool kExitFree = false;
   L ld;
   int row0, rows_valid, red_end;
   __device__ __forceinline__ NoPrep prep() const { return NoPrep{}; }
@@ -596,6 +623,7 @@ struct KcPrep {
 template <int ROWS, class L, int NP = kProd>
 struct KcOperand {
   static_assert(L::kLean, "KcOperand needs a loader with the lean interface (else KcOperandG)");
+  static constexpr bool kExitFree = true;
   static constexpr int NV = KcPrep<ROWS, L, NP>::NV;
   // a thread's chunks are NP / 8 rows apart: a multiple of 16 rows leaves the swizzle ((row >> 1) & 7) alone, so they lie a
   // CONSTANT NP / 8 * BK floats apart and one LDS address serves them all (ds_write_b128 offset:)
@@ -671,6 +699,7 @@ struct KcOperand {
 };
 template <int WIDTH, int S, class L>
 struct OcOperand {
+  static constexpr bool kExitFree = false;
   L ld;
   int out0, out_valid, red_end;
   __device__ __forceinline__ OcMap<WIDTH, L> prep() const { return oc_prepare<WIDTH, S>(ld, out0, out_valid); }
@@ -814,14 +843,15 @@ __device__ __forceinline__ void lds_barrier() {
 
 // The main loop over the BK slices [red_begin, red_end), one barrier per slice, roles split by wave:
 //   waves 4-7 (producers): in phase i they transform slice i+3 (fetched during phase i-3) and write it to LDS slot
-//     (i+3) % 4, then issue the global loads of slice i+6 into the register stage that just became free (three register
-//     stages with fixed roles: the loop is unrolled by three) — every load has three phases (~2 us) to land;
+//     (i+3) % 4, then issue the global loads of slice i+6 — if there is one — into the register stage that just became
+//     free (three register stages with fixed roles) — every load has three phases (~2 us) to land;
 //   waves 0-3 (consumers, one per SIMD): in phase i they run the 56 MFMAs of slice i out of slot i % 4.  The second
 //     half's fragments are read at the top of the phase and the first half of slice i+1 (written in phase i-2) in the
 //     middle of it, so the matrix pipe never waits for an LDS read across the barrier.
 // The element work of the operand loads (BatchNorm / ReLU / dropout bit) runs on the producers' VALU slots beside the
-// consumers' MFMAs (not for free: the f32 MFMA shares the vector issue, so it is kept to a few instructions per float4).  fetchR/fetchC(red0) issue the loads of one slice, finishR/finishC(T, stage, red0)
-// transform and write it.  Fetches past the last slice re-read the last slice (never written).
+// consumers' MFMAs (not for free: the f32 MFMA shares the vector issue, so it is kept to a few instructions per float4).
+// Which phase does what, for both roles, is "the ring's schedule" below (ring_produce / ring_consume); the operands'
+// fetch / finish say what issuing the loads of a slice and transforming + writing it are.
 // `pre` (optional): work the CONSUMER waves do while the producers' first loads are in flight — joining the statistics
 // behind the R operand's constants into LDS (tail.hip) — with one extra barrier between it and the producers' first
 // LDS write (which is where those constants are first read: kLateConsts loaders).
@@ -838,38 +868,205 @@ struct Pre {
 template <class F>
 __device__ __forceinline__ Pre<F> make_pre(F f) { return Pre<F>{f}; }
 
-// The consumers' phases: NF full sub-tiles + NG four-column groups per wave (static accumulator indices; main_loop_impl
-// picks the instance with a uniform branch outside the slice loop).  dead_half: the partial slice — index 0 — ends inside
-// its first half, so its second half is all zeros by construction: no fragment reads and no MFMAs for it.
-template <bool R_KC, bool C_KC, int NF, int NG>
-__device__ __forceinline__ void consume(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], float *lds, int nst, bool dead_half, int wave,
-                                        int lane) {
-  constexpr int rOff = R_KC ? kROffKC : kROffOC, cOff = C_KC ? kCOffKC : kCOffOC;
-  auto slot = [&](int i) { return lds + (i % kRing) * kStageFloats; };
-  Frags<NF, NG> f0, f1;
-  read_frags<R_KC, C_KC, NF, NG>(f0, slot(0) + rOff, slot(0) + cOff, wave, lane, 0);
+// ---- the ring's schedule ----------------------------------------------------------------------------------------------
+// ONE description of who does what in which phase, walked by BOTH roles on the device and by the host test
+// (mi_tail_ring_plan, tests/test_tail_ring_host.py) through a visitor: the walkers below are the control flow of the main
+// loop, the visitors only say what a fetch / finish / fragment read / barrier IS (device: the loads, LDS writes and MFMAs;
+// host: a record of the event).  A barrier-count mismatch between the roles is a hang, so neither role counts on its own.
+//   slice s (0 .. nst-1; the partial slice, if any, is slice 0) lives in LDS slot s % kRing and travels through register
+//   stage s % kStages;  phase i (between ring barriers i and i+1) finishes slice i + 3 and fetches slice i + 6 — where those
+//   exist — while the consumers run the MFMAs of slice i.  Barrier 0 closes the prologue (slices 0..2 finished, 3..5 in
+//   flight); both roles execute exactly 1 + nst ring barriers, plus the PRE barrier in front of the first finish.
+// Producers.  The shape of the control flow is what decides the s_waitcnt vmcnt counts hipcc can place: a count is the
+// MINIMUM over all paths that reach the wait.  The loop used to be `for (i = 0; i < nst; i += 3)` with `if (i + 3 < nst)`
+// around each finish, a clamped fetch of slice i + 6 in every phase and two `break`s; hipcc sent both break edges through
+// the latch, "this stage was the last one issued" merged into the header's state, and one phase in three waited for loads
+// issued ONE phase earlier (vmcnt(5)..(0) in the plain forward product where (17)..(12) was meant), a second one for loads
+// two phases old.  Now:
+//   steady state  whole triples with i + 9 <= nst: every phase finishes a slice and fetches one that exists; no exit, no
+//                 condition inside.  The header's two predecessors (prologue, latch) carry the same stage order.
+//   drain         the 6..8 phases behind it, straight-line, one instance per length (a uniform switch, so that no wait
+//                 sees a path on which a fetch was not issued): 0..2 phases that still fetch, three that only finish, three
+//                 that only arrive at the barrier.  No load is issued for a slice index >= nst (the clamped re-reads of the
+//                 last slice were 6-10 vector memory instructions per producer thread in each of the last six phases).
+//   nst < 6       one conditional straight line (small reductions; pessimistic waits there are once per product).
+constexpr int kStages = 3;      // register stages of the producers
+__host__ __device__ constexpr int ring_slot(int slice) { return slice % kRing; }
+// slice s covers reduction indices [ring_at * BK, + BK) of the range: the partial slice (the range's end) is slice 0
+__host__ __device__ constexpr int ring_at(int nst, bool partial, int s) { return partial ? (s == 0 ? nst - 1 : s - 1) : s; }
+__host__ __device__ constexpr int ring_steady(int nst) { return nst >= 9 ? (nst - 6) / 3 * 3 : 0; }      // phases run as whole triples
+template <int REM, class V>
+__host__ __device__ __forceinline__ void ring_drain(int i, V &v) {
+  static_assert(REM >= 6 && REM <= 8, "the drain is the last 6..8 phases");
+  v.template finish<0>(i + 3, false);
+  if constexpr (REM > 6) v.template fetch<0>(i + 6, false);
+  v.barrier();
+  v.template finish<1>(i + 4, false);
+  if constexpr (REM > 7) v.template fetch<1>(i + 7, false);
+  v.barrier();
+  v.template finish<2>(i + 5, false);
+  v.barrier();
+  if constexpr (REM > 6) v.template finish<0>(i + 6, false);
+  v.barrier();
+  if constexpr (REM > 7) v.template finish<1>(i + 7, false);
+  v.barrier();
+  v.barrier();
+  if constexpr (REM > 6) v.barrier();
+  if constexpr (REM > 7) v.barrier();
+}
+template <class V>
+__host__ __device__ __forceinline__ void ring_produce(int nst, V &v) {
+  if (nst >= 6) {
+    v.template fetch<0>(0, true);
+    v.template fetch<1>(1, false);
+    v.template fetch<2>(2, false);
+    v.pre_barrier();
+    v.template finish<0>(0, true);
+    v.template fetch<0>(3, false);
+    v.template finish<1>(1, false);
+    v.template fetch<1>(4, false);
+    v.template finish<2>(2, false);
+    v.template fetch<2>(5, false);
+    v.barrier();
+    int i = 0;
+    for (; i + 9 <= nst; i += 3) {
+      v.template finish<0>(i + 3, false);
+      v.template fetch<0>(i + 6, false);
+      v.barrier();
+      v.template finish<1>(i + 4, false);
+      v.template fetch<1>(i + 7, false);
+      v.barrier();
+      v.template finish<2>(i + 5, false);
+      v.template fetch<2>(i + 8, false);
+      v.barrier();
+    }
+    const int rem = nst - i;
+    if (rem == 6) ring_drain<6>(i, v);
+    else if (rem == 7) ring_drain<7>(i, v);
+    else ring_drain<8>(i, v);
+  } else {
+    v.template fetch<0>(0, true);
+    if (nst > 1) v.template fetch<1>(1, false);
+    if (nst > 2) v.template fetch<2>(2, false);
+    v.pre_barrier();
+    v.template finish<0>(0, true);
+    if (nst > 3) v.template fetch<0>(3, false);
+    if (nst > 1) v.template finish<1>(1, false);
+    if (nst > 4) v.template fetch<1>(4, false);
+    if (nst > 2) v.template finish<2>(2, false);
+    v.barrier();
+    if (nst > 3) v.template finish<0>(3, false);
+    v.barrier();
+    if (nst > 4) v.template finish<1>(4, false);
+    for (int i = 1; i < nst; ++i) v.barrier();
+  }
+}
+// Operands with GENERAL addressing (OtOperandG / KcOperandG / OcOperand: the weight-gradient product of deterministic mode,
+// the grouped panel operand) keep ONE loop over all phases with the conditions inside — the same schedule, phase by phase,
+// as ring_produce.  Their finishes run under lane masks and compute 64-bit addresses per access; in the exit-free form hipcc
+// re-paired all three stages' registers on the back edge (96 v_mov_b32 behind s_waitcnt vmcnt(0) once per trip) and the
+// widest instances (k_tail_wgrad<true, *>) went to scratch (profiles/tail_ring_isa.txt, "General addressing").  None of
+// them is on the training step's path.
+template <class V>
+__host__ __device__ __forceinline__ void ring_produce_general(int nst, V &v) {
+  v.template fetch<0>(0, true);
+  if (nst > 1) v.template fetch<1>(1, false);
+  if (nst > 2) v.template fetch<2>(2, false);
+  v.pre_barrier();
+  v.template finish<0>(0, true);
+  if (nst > 3) v.template fetch<0>(3, false);
+  if (nst > 1) v.template finish<1>(1, false);
+  if (nst > 4) v.template fetch<1>(4, false);
+  if (nst > 2) v.template finish<2>(2, false);
+  if (nst > 5) v.template fetch<2>(5, false);
+  v.barrier();
+  for (int i = 0; i < nst; i += 3) {
+    if (i + 3 < nst) v.template finish<0>(i + 3, false);
+    if (i + 6 < nst) v.template fetch<0>(i + 6, false);
+    v.barrier();
+    if (i + 1 >= nst) break;
+    if (i + 4 < nst) v.template finish<1>(i + 4, false);
+    if (i + 7 < nst) v.template fetch<1>(i + 7, false);
+    v.barrier();
+    if (i + 2 >= nst) break;
+    if (i + 5 < nst) v.template finish<2>(i + 5, false);
+    if (i + 8 < nst) v.template fetch<2>(i + 8, false);
+    v.barrier();
+  }
+}
+// Consumers.  In phase i: the second half's fragments of slice i are read at the top, the first half of slice i + 1 in the
+// middle, so the matrix pipe never waits for an LDS read across the barrier.  The read in the middle stays behind
+// `if (i + 1 < nst)`.  That join makes hipcc count the second half's waits as lgkmcnt(6)..(0) where (8) would do; the build
+// that read slot (i + 1) % kRing unconditionally and cleared a pending kernel-argument load in front of barrier 0 (the cause
+// of the flat lgkmcnt(0) at the top of a phase in the seven-sub-tile instance) had counted waits everywhere and measured
+// no gain on top of the producers' change (0.2079-0.2080 ms against 0.2071-0.2079, profiles/tail_ring_ab.txt): taken out.
+template <class V>
+__host__ __device__ __forceinline__ void ring_consume_open(V &v) {
+  v.pre_barrier();      // (PRE active) the constants the consumers joined are in LDS before the producers' first finish
+  v.barrier();          // ring barrier 0: slices 0..2 are in their slots
+}
+template <class V>
+__host__ __device__ __forceinline__ void ring_consume(int nst, bool dead_half, V &v) {
+  v.template read<0>(0, 0);
   int i = 0;
-  if (dead_half) {
-    __builtin_amdgcn_sched_barrier(0);
-    mma_half(acc, accg, f0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (1 < nst) read_frags<R_KC, C_KC, NF, NG>(f0, slot(1) + rOff, slot(1) + cOff, wave, lane, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    consumer_barrier();
+  if (dead_half) {      // the partial slice ends inside its first half: no fragment reads and no MFMAs for the second
+    v.template mma<0>();
+    if (1 < nst) v.template read<0>(1, 0);
+    v.barrier();
     i = 1;
   }
   for (; i < nst; ++i) {
-    const float *T = slot(i), *Tn = slot(i + 1);
-    read_frags<R_KC, C_KC, NF, NG>(f1, T + rOff, T + cOff, wave, lane, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma_half(acc, accg, f0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (i + 1 < nst) read_frags<R_KC, C_KC, NF, NG>(f0, Tn + rOff, Tn + cOff, wave, lane, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    mma_half(acc, accg, f1);
-    __builtin_amdgcn_sched_barrier(0);
+    v.template read<1>(i, 1);
+    v.template mma<0>();
+    if (i + 1 < nst) v.template read<0>(i + 1, 0);
+    v.template mma<1>();
+    v.barrier();
+  }
+}
+
+// The consumers' phases: NF full sub-tiles + NG four-column groups per wave (static accumulator indices; main_loop_impl
+// picks the instance with a uniform branch outside the slice loop).  dead_half: the partial slice — index 0 — ends inside
+// its first half, so its second half is all zeros by construction: no fragment reads and no MFMAs for it.
+template <class PRE>
+struct ConsumerOpen {
+  const PRE &pre;
+  __device__ __forceinline__ void pre_barrier() {
+    if constexpr (PRE::kActive) {
+      pre();
+      producer_barrier();              // (lgkmcnt(0): the constants are in LDS) pairs with the producers' extra barrier
+    }
+    __builtin_amdgcn_s_setprio(3);     // the matrix pipe's wave wins the issue arbitration against the producer beside it
+  }
+  __device__ __forceinline__ void barrier() {
     consumer_barrier();
   }
+};
+template <bool R_KC, bool C_KC, int NF, int NG>
+struct ConsumerRing {
+  static constexpr int rOff = R_KC ? kROffKC : kROffOC, cOff = C_KC ? kCOffKC : kCOffOC;
+  floatx4 (&acc)[NSUB];
+  floatx4 (&accg)[NGRP];
+  float *lds;
+  int wave, lane;
+  Frags<NF, NG> f0, f1;
+  template <int F>
+  __device__ __forceinline__ void read(int slice, int half) {
+    const float *T = lds + ring_slot(slice) * kStageFloats;
+    read_frags<R_KC, C_KC, NF, NG>(F == 0 ? f0 : f1, T + rOff, T + cOff, wave, lane, half);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  template <int F>
+  __device__ __forceinline__ void mma() {
+    mma_half(acc, accg, F == 0 ? f0 : f1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void barrier() { consumer_barrier(); }
+};
+template <bool R_KC, bool C_KC, int NF, int NG>
+__device__ __forceinline__ void consume(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], float *lds, int nst, bool dead_half, int wave,
+                                        int lane) {
+  ConsumerRing<R_KC, C_KC, NF, NG> v{acc, accg, lds, wave, lane};
+  ring_consume(nst, dead_half, v);
 }
 // nfull = 0..6 full sub-tiles + the group: every tile width 16 nfull + 4, no fallback among them.
 template <int NF>
@@ -881,6 +1078,71 @@ __device__ __forceinline__ void consume_cover(floatx4 (&acc)[NSUB], floatx4 (&ac
   }
 }
 
+// The producers' side of the schedule: fetch<S> issues the loads of a slice into register stage S, finish<S> transforms the
+// stage and writes it to the slice's slot.  any: the *_any forms (slice 0 only: the one that may be partial).
+template <bool R_KC, bool C_KC, bool PRE_ACTIVE, class OR, class OC, class PR, class PC>
+struct ProducerRing {
+  static constexpr int rOff = R_KC ? kROffKC : kROffOC, cOff = C_KC ? kCOffKC : kCOffOC;
+  typedef decltype(((const OR *)nullptr)->fetch(*(const PR *)nullptr, 0)) StageR;
+  typedef decltype(((const OC *)nullptr)->fetch(*(const PC *)nullptr, 0)) StageC;
+  const OR &opR;
+  const OC &opC;
+  const PR &pR;
+  const PC &pC;
+  float *lds;
+  int red_begin, nst;
+  bool partial;
+  StageR r0, r1, r2;
+  StageC c0, c1, c2;
+  // first reduction index of slice s: the partial slice (the range's end) is walked first, the full ones follow in order
+  __device__ __forceinline__ int at(int s) const { return red_begin + ring_at(nst, partial, s) * BK; }
+  template <int S>
+  __device__ __forceinline__ StageR &stR() {
+    if constexpr (S == 0) return r0;
+    else if constexpr (S == 1) return r1;
+    else return r2;
+  }
+  template <int S>
+  __device__ __forceinline__ StageC &stC() {
+    if constexpr (S == 0) return c0;
+    else if constexpr (S == 1) return c1;
+    else return c2;
+  }
+  template <int S>
+  __device__ __forceinline__ void fetch(int slice, bool any) {
+    static_assert(S >= 0 && S < kStages, "three register stages");
+    const int red0 = at(slice);
+    if (any) {
+      stR<S>() = opR.fetch_any(pR, red0);
+      stC<S>() = opC.fetch_any(pC, red0);
+    } else {
+      stR<S>() = opR.fetch(pR, red0);
+      stC<S>() = opC.fetch(pC, red0);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // see finish
+  }
+  template <int S>
+  __device__ __forceinline__ void finish(int slice, bool any) {
+    float *T = lds + ring_slot(slice) * kStageFloats;
+    const int red0 = at(slice);
+    if (any) {
+      opR.finish_any(T + rOff, stR<S>(), pR, red0);
+      opC.finish_any(T + cOff, stC<S>(), pC, red0);
+    } else {
+      opR.finish(T + rOff, stR<S>(), pR, red0);
+      opC.finish(T + cOff, stC<S>(), pC, red0);
+    }
+    // A stage's loads are issued where the schedule says, behind the finish that frees the stage.  Straight-line code lets
+    // hipcc's scheduler pull fetches up over finishes (the prologue's fetches of slices 3 and 4 over the finishes of
+    // slices 0..2: five stages in registers instead of three; profiles/tail_ring_isa.txt, "Resources").
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void pre_barrier() {
+    if constexpr (PRE_ACTIVE) producer_barrier();      // the consumers have joined the constants
+  }
+  __device__ __forceinline__ void barrier() { producer_barrier(); }
+};
+
 template <bool R_KC, bool C_KC, int NS, bool COVER, class OR, class OC, class PRE>
 __device__ __forceinline__ void main_loop_impl(floatx4 (&acc)[NSUB], floatx4 (&accg)[NGRP], Cover cv, float *lds, int red_begin,
                                                int red_end, const OR &opR, const OC &opC, const PRE &pre) {
@@ -889,16 +1151,11 @@ __device__ __forceinline__ void main_loop_impl(floatx4 (&acc)[NSUB], floatx4 (&a
   const int nst = (red_end - red_begin + BK - 1) / BK;
   if (nst <= 0) return;
   // Slice ORDER: a sum does not care, so the partial slice (if the range is not a multiple of BK) is walked FIRST —
-  // index 0, handled by the prologue's *_any calls — and every slice the steady state touches is a full one.  Indices
-  // past the end repeat the last index (never written); with a single, partial slice that is the partial one again,
-  // which only the *_any forms may read: `lone` routes every access through them (tiny reductions only).
+  // index 0, handled by the prologue's *_any calls — and every slice the steady state touches is a full one (ProducerRing::at).
+  // A single, partial slice takes the unpipelined `lone` step below (tiny reductions only).
   const bool partial = (red_end - red_begin) % BK != 0;
   const bool lone = partial && nst == 1;
   const bool dead_half = partial && (red_end - red_begin) % BK <= BK / 2;      // the partial slice's upper 16 indices are zeros
-  auto at = [&](int i) {
-    const int ii = i < nst ? i : nst - 1;
-    return red_begin + (partial ? (ii == 0 ? nst - 1 : ii - 1) : ii) * BK;
-  };
   auto slot = [&](int i) { return lds + (i % kRing) * kStageFloats; };
   if (lone) {
     // a reduction shorter than one slice: one unpipelined step through the *_any forms (the pipeline below would
@@ -933,69 +1190,13 @@ __device__ __forceinline__ void main_loop_impl(floatx4 (&acc)[NSUB], floatx4 (&a
     // ---------------------------------------------------------------------------------------------- producers
     const auto pR = opR.prep();
     const auto pC = opC.prep();
-    auto fetchR = [&](int red0) { return opR.fetch(pR, red0); };
-    auto fetchC = [&](int red0) { return opC.fetch(pC, red0); };
-    auto finishR = [&](float *T, const auto &st, int red0) { opR.finish(T, st, pR, red0); };
-    auto finishC = [&](float *T, const auto &st, int red0) { opC.finish(T, st, pC, red0); };
-    // slices 0..2 straight into their slots, slices 3..5 left in flight in the three register stages
-    auto r0 = opR.fetch_any(pR, at(0));
-    auto c0 = opC.fetch_any(pC, at(0));
-    auto r1 = fetchR(at(1));
-    auto c1 = fetchC(at(1));
-    auto r2 = fetchR(at(2));
-    auto c2 = fetchC(at(2));
-    if constexpr (PRE::kActive) producer_barrier();      // the consumers have joined the constants
-    opR.finish_any(slot(0) + rOff, r0, pR, at(0));
-    opC.finish_any(slot(0) + cOff, c0, pC, at(0));
-    r0 = fetchR(at(3));
-    c0 = fetchC(at(3));
-    if (nst > 1) {
-      finishR(slot(1) + rOff, r1, at(1));
-      finishC(slot(1) + cOff, c1, at(1));
-    }
-    r1 = fetchR(at(4));
-    c1 = fetchC(at(4));
-    if (nst > 2) {
-      finishR(slot(2) + rOff, r2, at(2));
-      finishC(slot(2) + cOff, c2, at(2));
-    }
-    r2 = fetchR(at(5));
-    c2 = fetchC(at(5));
-    producer_barrier();
-    for (int i = 0; i < nst; i += 3) {
-      // phase i: (r0, c0) = slice i+3, (r1, c1) = slice i+4, (r2, c2) = slice i+5
-      if (i + 3 < nst) {
-        finishR(slot(i + 3) + rOff, r0, at(i + 3));
-        finishC(slot(i + 3) + cOff, c0, at(i + 3));
-      }
-      r0 = fetchR(at(i + 6));
-      c0 = fetchC(at(i + 6));
-      producer_barrier();
-      if (i + 1 >= nst) break;
-      if (i + 4 < nst) {
-        finishR(slot(i + 4) + rOff, r1, at(i + 4));
-        finishC(slot(i + 4) + cOff, c1, at(i + 4));
-      }
-      r1 = fetchR(at(i + 7));
-      c1 = fetchC(at(i + 7));
-      producer_barrier();
-      if (i + 2 >= nst) break;
-      if (i + 5 < nst) {
-        finishR(slot(i + 5) + rOff, r2, at(i + 5));
-        finishC(slot(i + 5) + cOff, c2, at(i + 5));
-      }
-      r2 = fetchR(at(i + 8));
-      c2 = fetchC(at(i + 8));
-      producer_barrier();
-    }
+    ProducerRing<R_KC, C_KC, PRE::kActive, OR, OC, decltype(pR), decltype(pC)> v{opR, opC, pR, pC, lds, red_begin, nst, partial};
+    if constexpr (OR::kExitFree && OC::kExitFree) ring_produce(nst, v);
+    else ring_produce_general(nst, v);
   } else {
     // ---------------------------------------------------------------------------------------------- consumers
-    if constexpr (PRE::kActive) {
-      pre();
-      producer_barrier();              // (lgkmcnt(0): the constants are in LDS) pairs with the producers' extra barrier
-    }
-    __builtin_amdgcn_s_setprio(3);     // the matrix pipe's wave wins the issue arbitration against the producer beside it
-    consumer_barrier();
+    ConsumerOpen<PRE> open{pre};
+    ring_consume_open(open);
     if (COVER && cv.rem != 0) {
       if constexpr (COVER) consume_cover<0>(acc, accg, lds, nst, dead_half, wave, lane, cv.nfull);
     } else consume<R_KC, C_KC, NS, 0>(acc, accg, lds, nst, dead_half, wave, lane);
