@@ -259,16 +259,18 @@ __global__ __launch_bounds__(kBlock) void k_tt_last_bwd_core(LastArgs a, const f
     float rc[kLastRegs], rg;
     {
       const int64_t l = order[first];
-      fetch_run(a.src + a.src_row[l] * a.src_stride, HK, lane, !a.valid || a.valid[l], rc);
-      rg = lane < D ? g[l * D + lane] : 0.f;
+      const bool ok = !a.valid || a.valid[l];       // an invalid lookup contributes nothing, whatever its g row holds
+      fetch_run(a.src + a.src_row[l] * a.src_stride, HK, lane, ok, rc);
+      rg = (lane < D && ok) ? g[l * D + lane] : 0.f;
     }
     for (long long r = 0; r < cnt; ++r) {
       spill_run(c, HK, lane, rc);
       if (lane < D) gl[lane] = rg;
       wave_lds_sync();
       const int64_t ln = order[first + (r + 1 < cnt ? r + 1 : r)];
-      fetch_run(a.src + a.src_row[ln] * a.src_stride, HK, lane, !a.valid || a.valid[ln], rc);
-      rg = lane < D ? g[ln * D + lane] : 0.f;
+      const bool okn = !a.valid || a.valid[ln];
+      fetch_run(a.src + a.src_row[ln] * a.src_stride, HK, lane, okn, rc);
+      rg = (lane < D && okn) ? g[ln * D + lane] : 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (lane + u * kWave < Kq) {

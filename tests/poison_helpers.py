@@ -2466,6 +2466,11 @@ def _build4():
     # (128 floats per row: wider than a wave's 64 outputs, so the last level is a grouped product like the others)
     cases += [_tt_case("grouped-4cores", 20000, [8, 12, 4], [10, 10, 20, 10], [2, 2, 1, 4], (6000,)), _tt_planner_case(),
               _tt_case("grouped-wide-rows", 20000, [8, 8], [25, 25, 32], [4, 4, 8], (4500,), D=128),
+              # off D = 16: the last-level kernels at a full wave of outputs; the last level as a GEMM with two cores; and just
+              # across the last-level kernels' limit (H*K = 4 * 132 = 528 > 512) at D = 16
+              _tt_case("grouped-fast-D64", 20000, [8, 16], [25, 25, 32], [4, 4, 4], (4500,), D=64),
+              _tt_case("grouped-gemm-last-2cores", 20000, [8], [200, 100], [4, 12], (4500,), D=48),
+              _tt_case("grouped-HK528", 20000, [8, 132], [25, 25, 32], [2, 2, 4], (4500,)),
               _tt_init_case("ttinit_approx_uniform_r2x3"), _dhe_hash_case()]
     cases += [_optembed_cf_retrain_case("feature"), _optembed_cf_retrain_case("field"), _optembed_cf_draw_case(), _cerp_num_params_case()]
     cases += [_dual_fm_empty_case(kind, geo) for kind, geo in (("mult", 3), ("soft", 7), ("mask", 7))]

@@ -22,16 +22,18 @@ SEEDS = list(range(25))
 
 
 @pytest.mark.parametrize("family", ["one", "gemm_case", "lookup_case", "crossnet_case", "tail_case", "tail_mixed_case",
-                                    "crossnet_offpath_case"])
+                                    "crossnet_offpath_case", "tt_case"])
 def test_fuzz_family_for_fixed_seeds(fuzz, family):
     """`one`: field sort + sparse / dense Adam + masked InfoNCE + gather+FM; `gemm_case`: the fp32 MFMA GEMM at random small
     shapes; `lookup_case`: dual (QR / CERP) gathers, SpMM, routing; `crossnet_case`: panel / multi-problem GEMMs, fused
     backward head, per-expert kernels (exact on integer-valued data); `tail_case`: the fused MLP tail against float64;
     `tail_mixed_case`: the same with every hidden layer's BatchNorm / Dropout / bias drawn on its own; `crossnet_offpath_case`:
-    both CrossNet heads at widths, expert counts and ranks off the fast path of their dispatch, against float64."""
+    both CrossNet heads at widths, expert counts and ranks off the fast path of their dispatch, against float64; `tt_case`: the
+    grouped TT-Rec lookup at random core counts, q / p shapes, ranks and id distributions against float64 and against the
+    per-lookup kernels."""
     fn = getattr(fuzz, family)
     base = {"one": 1000, "gemm_case": 100000, "lookup_case": 500000, "crossnet_case": 700000, "tail_case": 900000,
-            "tail_mixed_case": 1100000, "crossnet_offpath_case": 1300000}[family]
+            "tail_mixed_case": 1100000, "crossnet_offpath_case": 1300000, "tt_case": 1500000}[family]
     for s in SEEDS:
         try:
             fn(base + s)

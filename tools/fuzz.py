@@ -2,7 +2,8 @@
     python tools/fuzz.py [cases [first seed]]
 field sort, sparse Adam (all widths), dense Adam (mixed sizes / unaligned views), masked InfoNCE, gather+FM with both
 gradient forms, the fp32 MFMA GEMM at random small shapes, and the round-2 CrossNet kernels (panel / multi-problem GEMMs, the
-fused backward head, the per-expert kernels) and the CrossNet heads at widths off their fast path.  Stops at the first
+fused backward head, the per-expert kernels), the CrossNet heads at widths off their fast path, and the grouped TT-Rec lookup
+over random core counts, shapes and ranks.  Stops at the first
 mismatch with the seed that reproduces it."""
 import os
 import sys
@@ -344,6 +345,56 @@ def crossnet_offpath_case(seed):
             close(got, want, rtol, atol * max(1.0, float(want.abs().max())), f"{what} {k}", seed)
 
 
+def tt_case(seed):
+    """tt_lookup on the grouped form (n in 4096..9000 lookups): 2..4 cores, q shapes and ranks drawn inside tt_grouped_supported
+    (row widths 4..128, both forms of the last level), p shapes with N at or below their product, uniform or u**6-skewed ids —
+    forward and every core gradient against the oracle in float64 with the contract of tests/test_tt_grouped_gpu.py (forward
+    rtol 1e-4 / atol 1e-5, core gradients rtol 1e-3 / atol 1e-4), and the grouped form against the per-lookup kernels on the
+    same batch."""
+    g = torch.Generator().manual_seed(seed)
+    ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))  # noqa: E731
+    nc = ri(2, 4)
+    while True:
+        qs = [(1, 2, 4, 8)[ri(0, 3)] for _ in range(nc - 1)] + [(4, 8)[ri(0, 1)]]
+        D = 1
+        for q in qs:
+            D *= q
+        if D <= 128:
+            break
+    ranks = [1] + [4 * ri(1, 8) for _ in range(nc - 1)] + [1]
+    hi = {2: 90, 3: 24, 4: 10}[nc]
+    ps = [ri(2, hi) for _ in range(nc)]
+    big = 1
+    for p in ps:
+        big *= p
+    N = max(1, big - ri(0, min(big - 1, 50)))
+    n = ri(4096, 9000)
+    if not _kernels.tt_grouped_supported(n, qs, ranks):
+        raise SystemExit(f"MISMATCH tt: the draw qs={qs} ranks={ranks} is outside the grouped form; seed={seed}")
+    u = torch.rand(n, generator=g)
+    idx = (N * (u ** 6 if ri(0, 1) else u)).long().clamp_(0, N - 1)
+    cores = [torch.randn(1, ps[c], ranks[c] * qs[c] * ranks[c + 1], generator=g) * 0.1 for c in range(nc)]
+    G = torch.randn(n, D, generator=g)
+    what = f"tt n={n} N={N} ps={ps} qs={qs} ranks={ranks}"
+    c64 = [c.double().requires_grad_(True) for c in cores]
+    ref = ro.tt_forward(idx, ps, qs, ranks, c64)
+    (ref * G.double()).sum().backward()
+    got = {}
+    for form in ("grouped", "per-lookup"):
+        cd = [c.to(DEV).requires_grad_(True) for c in cores]
+        args = (idx.to(DEV), N, tuple(ps), tuple(qs), tuple(ranks), *cd)
+        out = _kernels.tt_lookup(idx.to(DEV), cd, N, ps, qs, ranks) if form == "grouped" else _kernels.TTLookup.apply(*args)
+        (out * G.to(DEV)).sum().backward()
+        got[form] = (out, [c.grad for c in cd])
+        close(out, ref, 1e-4, 1e-5, f"{what} {form} forward", seed)
+        for i, c in enumerate(cd):
+            close(c.grad.view(c64[i].shape), c64[i].grad, 1e-3, 1e-4, f"{what} {form} grad core {i}", seed)
+    close(got["grouped"][0], got["per-lookup"][0], 1e-4, 1e-5, f"{what} grouped vs per-lookup forward", seed)
+    for i, (a, b) in enumerate(zip(got["grouped"][1], got["per-lookup"][1])):
+        close(a, b, 1e-3, 1e-4, f"{what} grouped vs per-lookup grad core {i}", seed)
+    _kernels._lib.check_index_errors()
+
+
 ambiguous = []     # tail cases that match float64 only with a near-kink ReLU decision taken the other way
 
 
@@ -593,6 +644,7 @@ if __name__ == "__main__":
         tail_case(900000 + s)
         tail_mixed_case(1100000 + s)
         crossnet_offpath_case(1300000 + s)
+        tt_case(1500000 + s)
         if s % 25 == 24:
             print(f"{s + 1} cases ok", flush=True)
     print(f"FUZZ_OK ({len(ambiguous)} tail cases matched float64 with a ReLU decision on the kink taken the other way: seeds {ambiguous[:8]})")
